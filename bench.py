@@ -2,7 +2,7 @@
 """bench.py — the BASELINE.json metric on MI355X: GFLOP/s + GB/s (vs the HBM roofline) of the
 GrB_mxv / GrB_mxm hot path on synthetic R-MAT.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input: one FP64 PLUS_TIMES `A.mxv(x)` (GrB_mxv through
@@ -14,9 +14,15 @@ the C ABI) with every operand already resident in HBM — `value`, `ms_per_step`
           pygraphblas_amd/csrc/grb_dist.cpp) while the diagonal block of the row block is multiplied, then the off-diagonal
           block.  value = 2·(entries of all ranks)·K / max-over-ranks time.  The other mode's SpMV is reported beside it
           (`spmv_strong` / `spmv_weak`) with per-phase times (exchange, diagonal block, off-diagonal block).
-The timed region is run `--blocks` times (default 5), each block EXACTLY K steps between barrier + synchronize; the line
-reports the median block (`ms_per_step_blocks` lists all of them).
-Beside the step the JSON line carries, every one with its own `roofline`:
+A plain run sets up, runs W warm-up steps, times EXACTLY K steps in one block between barrier + synchronize and prints the
+line (`value`, `ms_per_step`, `gbps_algorithmic`); nothing else runs on the GPU.  `--dump-outputs DIR` then writes what the
+last timed step computed — the tuples of `w` a caller of `A.mxv(x)` receives — as DIR/w_indices.npy and DIR/w_values.npy
+(float64; with N > 1 one pair per rank, w_rank<r>_*; a fixed seeded sample of the tuples if they exceed 64 MB).  The inputs
+are a pure function of the arguments (counter-based R-MAT and values, fixed seeds), so two builds compare output for output.
+`--full` adds everything else, as before it: the timed region is run `--blocks` times (default 5), each block EXACTLY K steps,
+and the line reports the median block (`ms_per_step_blocks` lists all of them); the step's `roofline` from K more launches
+timed on the library's stream, the CPU baseline, the per-phase times for N > 1 and, beside the step, every one
+with its own `roofline`:
   spmv_extra        what the plan of the SpMV kernel costs, the rate without a plan, the rate on permuted labels   [N = 1]
   mxm               configs[3]: triangle count L.mxm(L, PLUS_PAIR, mask=L).reduce_int() on R-MAT-22, bit-exact; for N > 1
                     the rows of L and of the mask in flop-balanced blocks, L replicated, INT64 all-reduce          [every N]
@@ -80,14 +86,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of exactly --steps steps; the median block is reported")
+    ap.add_argument("--full", action="store_true", help="also the roofline, CPU baseline, per-phase times and the sub-objects (a plain run times the step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (w's tuples) as DIR/<name>.npy")
+    ap.add_argument("--blocks", type=int, default=None, help="with --full: timed blocks of exactly --steps steps (default 5); the median block is reported")
     ap.add_argument("--scale", type=int, default=22, help="R-MAT scale (22 = the BASELINE config): per GPU for weak scaling, of the whole graph for strong")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak", help="what the headline step does for N > 1")
     ap.add_argument("--pr-scale", type=int, default=25, help="scale of the pagerank_scale25 sub-object (configs[4])")
     ap.add_argument("--aa-scale", type=int, default=18, help="scale of the unmasked A @ A sub-object")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed step (no sub-objects)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the timed step (no sub-objects)")
     args = ap.parse_args()
+    if not args.full and (args.blocks is not None or args.no_cpu_baseline or args.no_extras):
+        ap.error("--blocks, --no-cpu-baseline and --no-extras apply to --full runs only")
+    blocks = (5 if args.blocks is None else args.blocks) if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -181,12 +192,8 @@ def main():
     weak_scale, strong_scale = args.scale + log2w, args.scale
     head_scale = weak_scale if (args.scaling == "weak" or world == 1) else strong_scale
     head = SpmvJob(cx, head_scale)
-    res = head.run(args.steps, args.warmup, args.blocks)
+    res = head.run(args.steps, args.warmup, blocks, kernel_timing=args.full, dump_dir=args.dump_outputs)
     n, nnz_total = head.n, res["nnz_total"]
-    traffic, traffic_source = (None, None)
-    if world == 1 and head_scale == 22:       # the PMC passes were collected on this exact workload, in their own runs
-        traffic, traffic_source = static_traffic("spmv_pmc_traffic.json")
-    roofline = roof(res["alg_bytes"], res["kernel_ms"] * 1e-3, traffic=traffic, traffic_source=traffic_source, kernel=res["plan"], kernel_ms=round(res["kernel_ms"], 4))
     out = {
         "metric": "GFLOPS + GB/s (vs roofline) for mxv/mxm on R-MAT-22, 1/2/4/8 GPU",
         "value": round(res["gflops"], 2), "unit": "GFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -197,15 +204,20 @@ def main():
                    "n": n, "nnz": nnz_total, "semiring": "PLUS_TIMES_FP64", "parallelism": f"rowblock{world}", "transport": transport_note if world > 1 else "none (one GPU)",
                    "graph_build_s": round(head.t_gen, 2), "device": info["name"]},
         "ms_per_step_blocks": [round(b, 4) for b in res["blocks_ms"]],
-        "timing": f"median of {len(res['blocks_ms'])} blocks of exactly {args.steps} steps, each between barrier + synchronize (max over ranks)",
+        "timing": (f"median of {len(res['blocks_ms'])} blocks of exactly {args.steps} steps, each between barrier + synchronize (max over ranks)" if args.full else
+                   f"one block of exactly {args.steps} steps between barrier + synchronize (max over ranks)"),
         "gbps_algorithmic": round(res["alg_bytes_total"] / (res["ms_per_step"] * 1e-3) / 1e9, 1),
-        "roofline": roofline,
     }
-    if world > 1:
+    if args.full:
+        traffic, traffic_source = (None, None)
+        if world == 1 and head_scale == 22:       # the PMC passes were collected on this exact workload, in their own runs
+            traffic, traffic_source = static_traffic("spmv_pmc_traffic.json")
+        out["roofline"] = roof(res["alg_bytes"], res["kernel_ms"] * 1e-3, traffic=traffic, traffic_source=traffic_source, kernel=res["plan"], kernel_ms=round(res["kernel_ms"], 4))
+    if args.full and world > 1:
         out["phases"] = head.phases(min(args.steps, 20))
 
     # ---- CPU baseline (rank 0, N=1 only): the oracle's typed OpenMP loop on a bounded sample ------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         A, x, w = head.mats[0], head.x, head.w
         rp, ci, av = A.to_csr()
@@ -226,7 +238,7 @@ def main():
         out["parity_vs_oracle"] = "ok (pattern exact, values rtol 1e-6)" if ok else "MISMATCH"
         del rp, ci, av, xh, y, pres
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if world == 1:
             out["spmv_extra"] = spmv_extra(cx, head, res)
         bounds_head = head.bounds
@@ -309,7 +321,7 @@ class SpmvJob:
         else:
             self.mats[0].mxv(self.x, semiring=self.sr, out=self.w)
 
-    def run(self, steps, warmup, blocks):
+    def run(self, steps, warmup, blocks, kernel_timing=True, dump_dir=None):
         cx = self.cx
         lib, torch = cx.lib, cx.torch
         # the matrix's first product runs kernel W, the second builds kernel X's plan (the library's plan policy): both inside the warm-up
@@ -329,18 +341,34 @@ class SpmvJob:
             cx.barrier()
             blocks_ms.append(cx.max_over_ranks(time.perf_counter() - t0) / steps * 1e3)
         ms_per_step = sorted(blocks_ms)[len(blocks_ms) // 2]
+        if dump_dir is not None:
+            self.dump(dump_dir)
         nnz_total = int(cx.sum_over_ranks(float(self.nnz)))
         # roofline of the dominant kernel(s): HIP events on the library's stream around K launches
         kms = []
-        for _ in range(max(1, min(blocks, 3))):
+        for _ in range(max(1, min(blocks, 3)) if kernel_timing else 0):
             torch.cuda.synchronize()
             lib.GrBX_timer_start()
             for _ in range(steps):
                 self.step()
             m = C.c_float(0); lib.GrBX_timer_stop(C.byref(m)); kms.append(m.value / steps)
-        kernel_ms = sorted(kms)[len(kms) // 2]
+        kernel_ms = sorted(kms)[len(kms) // 2] if kms else None
         return {"ms_per_step": ms_per_step, "blocks_ms": blocks_ms, "gflops": 2.0 * nnz_total / (ms_per_step * 1e-3) / 1e9, "nnz_total": nnz_total, "kernel_ms": kernel_ms,
                 "alg_bytes": self.alg_bytes, "alg_bytes_total": int(cx.sum_over_ranks(float(self.alg_bytes))), "plan": plan}
+
+    def dump(self, dump_dir, budget=64_000_000):
+        """w's tuples after the last timed step (what `A.mxv(x)` gives its caller), as float64 .npy files; a fixed seeded sample
+        of the tuples when this rank's share of the 64 MB budget cannot hold them all."""
+        np = self.cx.np
+        I, X = self.w.to_arrays()
+        cap = budget // self.cx.world // 16
+        if len(I) > cap:
+            keep = np.sort(np.random.default_rng(12345).choice(len(I), size=cap, replace=False))
+            I, X = I[keep], X[keep]
+        os.makedirs(dump_dir, exist_ok=True)
+        tag = "w" if self.cx.world == 1 else f"w_rank{self.cx.rank}"
+        np.save(os.path.join(dump_dir, f"{tag}_indices.npy"), I.astype(np.float64))
+        np.save(os.path.join(dump_dir, f"{tag}_values.npy"), X.astype(np.float64))
 
     def phases(self, reps):
         """Per-phase times of the N > 1 step on this rank, each measured alone (HIP events on the library's stream; the exchange

@@ -217,6 +217,37 @@ def test_library_rccl_path_with_a_communicator_of_one(gb, gpu):
         assert lib.GrBX_dist_finalize() == 0
 
 
+def test_bench_py_plain_run_times_the_step_only_and_dumps_what_it_computed(gpu, tmp_path):
+    """A plain `bench.py` (no --full): one block of exactly --steps steps and none of the roofline, CPU baseline or sub-objects;
+    `--dump-outputs` writes the last timed step's `w` as float64 .npy files, which match the oracle's A @ x on the same R-MAT
+    graph and the dump of a second run with the same arguments."""
+    import json, subprocess
+    from pygraphblas_amd import rmat
+    from oracle import oracle as O
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--scale", "16", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=300, cwd=ROOT)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-3000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 2 and len(d["ms_per_step_blocks"]) == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "GFLOP/s" and d["dtype"] == "f64" and d["higher_is_better"] is True and d["config"]["n"] == 1 << 16
+        assert not {"roofline", "cpu_baseline", "spmv_extra", "mxm", "bfs", "pagerank", "sssp", "aa", "bc"} & set(d), sorted(d)
+        I, X = np.load(out / "w_indices.npy"), np.load(out / "w_values.npy")
+        assert I.dtype == np.float64 and X.dtype == np.float64 and len(I) == len(X)
+        dumps.append((I, X))
+    rp, col = rmat.csr_torch(16, "cpu", seed=42)
+    vals = rmat.values_torch(int(col.numel()), "cpu", seed=43)
+    x = rmat.values_torch(1 << 16, "cpu", seed=44)
+    y, pres = O.fast_spmv(rp.numpy().view(np.uint32), col.numpy().view(np.uint32), vals.numpy(), x.numpy())
+    for I, X in dumps:
+        assert np.array_equal(I, np.flatnonzero(pres).astype(np.float64))
+        assert np.allclose(X, y[pres != 0], rtol=1e-9, atol=0)
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.allclose(dumps[0][1], dumps[1][1], rtol=1e-12, atol=0)
+
+
 @pytest.mark.parametrize("scaling", ["weak", "strong", "weak-through-the-library-exchange-path"])
 def test_bench_py_runs_its_two_rank_path_on_one_gpu(gpu, scaling):
     """`bench.py --gpus 2` — what the driver launches for the scaling curve — end to end on this box: two ranks on GPU 0
@@ -233,7 +264,7 @@ def test_bench_py_runs_its_two_rank_path_on_one_gpu(gpu, scaling):
         scaling = "weak"
     port = 29800 + (os.getpid() % 1000) + (7 if scaling == "strong" else 0) + (13 if fake else 0)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--blocks", "2", "--scale", "17", "--pr-scale", "16", "--scaling", scaling],
+                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--blocks", "2", "--scale", "17", "--pr-scale", "16", "--scaling", scaling],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-3000:]

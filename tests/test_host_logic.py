@@ -177,11 +177,12 @@ def test_from_tsv_matches_reference_doctest(tmp_path):
     assert (list(I), list(J), list(V)) == (_DOC_I, _DOC_J, _DOC_V)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/docs/test_mm.mm"), reason="reference checkout not mounted (GPU box)")
 def test_readers_on_the_reference_fixture_files():
-    M = gb.Matrix.from_mm("/root/reference/docs/test_mm.mm")
+    """The reference's docs/test_mm.mm and docs/test_tsvfile.tsv, copied byte for byte to tests/golden/."""
+    golden = os.path.join(os.path.dirname(__file__), "golden")
+    M = gb.Matrix.from_mm(os.path.join(golden, "reference_docs_test_mm.mm"))
     assert M.type is gb.INT64 and [list(x) for x in M.to_lists()] == [_DOC_I, _DOC_J, _DOC_V]
-    T = gb.Matrix.from_tsv("/root/reference/docs/test_tsvfile.tsv", gb.INT32, 7, 7)
+    T = gb.Matrix.from_tsv(os.path.join(golden, "reference_docs_test_tsvfile.tsv"), gb.INT32, 7, 7)
     assert [list(x) for x in T.to_lists()] == [_DOC_I, _DOC_J, _DOC_V]
 
 

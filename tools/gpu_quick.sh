@@ -4,7 +4,7 @@ set -u
 tag=${1:-q}; out=gpurun_out/$tag; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 timeout 300 python -m pytest tests/test_baseline_configs_gpu.py -m gpu -x -q 2>&1 | tail -2
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o bench -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline > "$out/bench_line_under_rocprof.json" 2> "$out/prof.err"
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o bench -- python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline > "$out/bench_line_under_rocprof.json" 2> "$out/prof.err"
 python - "$out" <<'PY'
 import csv,sys,glob,json
 out=sys.argv[1]

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 timeout 900 python -m pytest tests -m gpu -x -q --timeout 600 --durations=6 > "$out/pytest_gpu.log" 2>&1; echo "pytest rc=$?" >> "$out/pytest_gpu.log"
 tail -12 "$out/pytest_gpu.log"
 timeout 120 python tools/bfs_probe.py > "$out/bfs_timeline.txt" 2>&1; cat "$out/bfs_timeline.txt" | head -40
-timeout 500 python bench.py > "$out/bench_line.json" 2> "$out/bench.err"; echo "bench rc=$?"; tail -3 "$out/bench.err"
+timeout 500 python bench.py --full > "$out/bench_line.json" 2> "$out/bench.err"; echo "bench rc=$?"; tail -3 "$out/bench.err"
 python - "$out" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]+"/bench_line.json").read().strip().splitlines()[-1])
