@@ -11,7 +11,11 @@
 // tuples); the HBM image is rebuilt lazily the next time a kernel needs it.  Semantics: C API 1.3: T is
 // formed, then C<M,replace> = accum(C, T); for assign the mask spans all of C (GrB_assign), for row / column assign only that
 // row / column.
+//
+// The three extract entry points have a second route: when the operand lives in HBM (or is large) they run the kernels of
+// grb_extract.hip and the device write-back instead — see `extract_on_device` below.  Assign and kronecker have the host route only.
 #include "grb_opcommon.hpp"
+#include "grb_extract.hpp"
 #include <array>
 #include <map>
 
@@ -159,6 +163,87 @@ Line assigned_line(const Line& cur, int ccode, GrB_Vector u, GrB_BinaryOp accum)
 }
 bool strictly_increasing(const std::vector<uint64_t>& v) { for (size_t k = 1; k < v.size(); k++) if (v[k] <= v[k - 1]) return false; return true; }
 
+// ---- extract: which route ---------------------------------------------------------------------------------------------------------
+// The device route (grb_extract.hip) is taken when a HIP device is present, every container of the call has an HBM layout (not hypersparse,
+// not complex; the operand not a bitmap-only batch matrix) and the operand either lives in HBM only or holds at least
+// EXTRACT_DEVICE_MIN_ENTRIES entries (the measured crossover against this file's host route, upload included: DESIGN.md §8).  Small
+// host-resident containers — notebook slices — keep the host route.  GRB_MI355X_EXTRACT=0 forces the host route, =1 the device route
+// wherever it is legal; GRB_MI355X_EXTRACT_BISECT=1 makes a column list bisect instead of using its table (both read per call: test hooks).
+constexpr uint64_t EXTRACT_DEVICE_MIN_ENTRIES = 10000;
+int extract_env() { const char* e = getenv("GRB_MI355X_EXTRACT"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }
+bool extract_bisect_env() { const char* e = getenv("GRB_MI355X_EXTRACT_BISECT"); return e && atoi(e) != 0; }
+bool dev_capable(GrB_Matrix A) { return !A || (!is_hyper(A) && A->type->code < T_FC32 && !A->iso_full); }
+bool dev_capable(GrB_Vector v) { return !v || (!is_hyper(v) && v->type->code < T_FC32 && !v->iso_full); }
+bool extract_on_device(GrB_Matrix A, bool others_capable) {
+  const int env = extract_env();
+  if (env == 0 || !device_ok() || !others_capable || !dev_capable(A) || mat_bitmap_only(A)) return false;
+  if (env == 1) return true;
+  if (A->dev_valid && !A->host_valid) return true;                      // it lives in HBM: it is not downloaded for this
+  return A->host_valid && mat_nvals(A) >= EXTRACT_DEVICE_MIN_ENTRIES;   // (the count of a valid host mirror: no device work)
+}
+bool extract_on_device(GrB_Vector u, bool others_capable) {
+  const int env = extract_env();
+  if (env == 0 || !device_ok() || !others_capable || !dev_capable(u)) return false;
+  if (env == 1) return true;
+  vec_gate(u);                                                          // deferred work that involves u is completed first, as every reader does
+  if (u->dev_valid && !u->host_valid) return true;
+  return u->host_valid && vec_nvals(u) >= EXTRACT_DEVICE_MIN_ENTRIES;
+}
+const char* const EXTRACT_DIM_MSG_V = "extract: output size must equal the number of indices";
+
+void extract_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, const GrB_Index* I, GrB_Index ni, const DescView& dv) {
+  ExIdx idx; extract_parse(idx, I, ni, u->n, "extract");
+  if (w->n != idx.n || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, EXTRACT_DIM_MSG_V);
+  if (accum) check_binop(accum, "accum");
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, w->n, allow_buf, &nothing);
+  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  vec_to_device(u);
+  const uint64_t n = idx.n; const size_t ts = u->type->size;
+  DevBuf keep, tval(n * ts + 8), tpres(n + 1);
+  extract_upload(idx, keep);
+  extract_vector(ts, u->dval.p, u->dpres.as<uint8_t>(), idx, tval.p, tpres.as<uint8_t>());
+  if (keep.p) GRB_HIP(hipStreamSynchronize(stream()));                  // (the uploaded list returns to the pool)
+  g_last_plan = std::string("extract_vector<index=") + (idx.kind == EX_ALL ? "all" : idx.kind == EX_LIST ? "list" : "range") + "> k_extract_vector ";
+  vector_write_back(w, u->type->code, tval, tpres, allow, accum, dv.replace, false);
+}
+
+void extract_col_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Matrix A, const GrB_Index* I, GrB_Index ni, GrB_Index j, const DescView& dv, uint64_t ar) {
+  ExIdx idx; extract_parse(idx, I, ni, ar, "extract");
+  if (w->n != idx.n || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, EXTRACT_DIM_MSG_V);
+  if (accum) check_binop(accum, "accum");
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, w->n, allow_buf, &nothing);
+  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  mat_to_device(A);
+  const uint64_t n = idx.n; const size_t ts = A->type->size;
+  DevBuf keep, tval(n * ts + 8), tpres(n + 1);
+  extract_upload(idx, keep);
+  extract_line(A->csr, ts, dv.tran0, (uint32_t)j, idx, tval.p, tpres.as<uint8_t>());
+  if (keep.p) GRB_HIP(hipStreamSynchronize(stream()));
+  const bool scatter = dv.tran0 && idx.kind == EX_ALL;
+  g_last_plan = std::string("extract_col<") + (dv.tran0 ? "row of the CSR" : "column of the CSR") + ",index=" + (idx.kind == EX_ALL ? "all" : idx.kind == EX_LIST ? "list" : "range") + "> " +
+                (scatter ? "k_extract_row_scatter " : "k_extract_lookup ");
+  vector_write_back(w, A->type->code, tval, tpres, allow, accum, dv.replace, false);
+}
+
+void extract_matrix_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, const DescView& dv,
+                           uint64_t ar, uint64_t ac) {
+  ExIdx ri, ci; extract_parse(ri, I, ni, ar, "extract"); extract_parse(ci, J, nj, ac, "extract");
+  if (C->nrows != ri.n || C->ncols != ci.n || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "extract: output shape must be |I| x |J|");
+  if (accum) check_binop(accum, "accum");
+  if (!Mask && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }      // no mask + complement: nothing may be written
+  mat_to_device(A);
+  const size_t ts = A->type->size;
+  DevBuf keep_i, keep_j; extract_upload(ri, keep_i); extract_upload(ci, keep_j);
+  // op(A)(I, J) = (A(J, I))^T under GrB_DESC_T0: the (smaller) result is transposed, never A
+  ExtractPlan plan; DevCSR T, Tt;
+  extract_csr(A->csr, ts, dv.tran0 ? ci : ri, dv.tran0 ? ri : ci, extract_bisect_env(), T, plan);
+  if (dv.tran0) { csr_transpose(T, ts, Tt); T.clear(); }
+  g_last_plan = std::string("extract_matrix<cols=") + plan.cols + ",rowsort=" + (plan.rowsort ? "1" : "0") + ",transpose=" + (dv.tran0 ? "1" : "0") + "> k_extract_rows<count> k_extract_rows<fill> ";
+  matrix_write_back(C, dv.tran0 ? Tt : T, A->type->code, Mask, dv, accum, false);
+}
+
 }  // namespace
 
 extern "C" {
@@ -168,6 +253,7 @@ GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
   return guarded(w, [&] {
     check_v(u, "extract"); if (mask) check_v(mask, "extract");
     const DescView dv(desc);
+    if (extract_on_device(u, dev_capable(w) && dev_capable(mask))) { extract_vector_device(w, mask, accum, u, I, ni, dv); return; }
     const Sel idx(I, ni, u->n, "extract");
     if (w->n != idx.size() || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "extract: output size must equal the number of indices");
     Map U = load(u), T, C = load(w), Mm; if (mask) Mm = load(mask);
@@ -185,6 +271,7 @@ GrB_Info GrB_Col_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp
     const DescView dv(desc);
     const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
     if (j >= ac) fail(GrB_INVALID_INDEX, "extract: column index out of range");
+    if (extract_on_device(A, dev_capable(w) && dev_capable(mask))) { extract_col_device(w, mask, accum, A, I, ni, j, dv, ar); return; }
     const Sel idx(I, ni, ar, "extract");
     if (w->n != idx.size() || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "extract: output size must equal the number of indices");
     const Line col = line_of(A, dv.tran0, j);                             // (index in op(A)'s column j, value), sorted
@@ -206,6 +293,7 @@ GrB_Info GrB_Matrix_extract(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binar
     check_m(A, "extract"); if (Mask) check_m(Mask, "extract");
     const DescView dv(desc);
     const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
+    if (extract_on_device(A, dev_capable(C) && dev_capable(Mask))) { extract_matrix_device(C, Mask, accum, A, I, ni, J, nj, dv, ar, ac); return; }
     const Sel ri(I, ni, ar, "extract"), ci(J, nj, ac, "extract");
     if (C->nrows != ri.size() || C->ncols != ci.size() || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "extract: output shape must be |I| x |J|");
     if (!Mask && !dv.mask_comp && !accum && ri.increasing() && ci.increasing()) {       // a slice `A[a:b, c:d]` into a fresh output: one pass over A's tuples

@@ -11,6 +11,7 @@
 // the C<M,replace> = accum(C,T) write-back, so the output may alias any input.
 #include "grb_opcommon.hpp"
 #include "grb_matops.hpp"
+#include "grb_extract.hpp"
 
 using namespace grb;
 
@@ -44,8 +45,9 @@ void adopt(GrB_Matrix C, DevCSR& T, int tcode) {
   C->csr.valid = true; C->dev_valid = true; C->host_valid = false;
 }
 
-// C<M,replace> = accum(C, T).  `t_masked`: T already has no entry the mask forbids.
-void matrix_write_back(GrB_Matrix C, DevCSR& T, int tcode, GrB_Matrix M, const DescView& dv, GrB_BinaryOp accum, bool t_masked) {
+}  // namespace
+// C<M,replace> = accum(C, T).  `t_masked`: T already has no entry the mask forbids.  (Declared in grb_extract.hpp: the extract entry points of grb_host_ops.cpp end in it too.)
+void grb::matrix_write_back(GrB_Matrix C, DevCSR& T, int tcode, GrB_Matrix M, const DescView& dv, GrB_BinaryOp accum, bool t_masked) {
   if (accum) check_binop(accum, "accum");
   if (!M && dv.mask_comp) {      // no mask + complement: nothing may be written
     if (dv.replace) GrB_Matrix_clear(C);
@@ -76,6 +78,7 @@ void matrix_write_back(GrB_Matrix C, DevCSR& T, int tcode, GrB_Matrix M, const D
                 accum ? accum->opcode : -1, out);
   adopt(C, out, ecode);
 }
+namespace {
 
 void check_mat(GrB_Matrix A, const char* what) { if (!check_obj(A)) fail(GrB_UNINITIALIZED_OBJECT, std::string(what) + ": uninitialised matrix"); }
 

@@ -150,7 +150,7 @@ class Vector:
         return out.value
 
     def extract(self, index, out=None, mask=None, accum=None, desc=None):
-        """`out<mask> = accum(out, self(I))` (reference: vector.py:1549-1575); host-mirror operation of the library."""
+        """`out<mask> = accum(out, self(I))` (reference: vector.py:1549-1575); a gather kernel when `self` lives in HBM or is large, the host mirror otherwise."""
         from .matrix import build_range
         I, ni, size, keep = build_range(index, self.size - 1)
         if out is None:
