@@ -1,0 +1,233 @@
+// grb_assign.hip — index-list assign in HBM: the operand moved into C's coordinates (CSR in, CSR out), the entries of C inside I x J flagged, w(I) = u on bitmaps.
+//
+// Index arguments arrive as ExIdx (grb_extract.hpp), never expanded: GrB_ALL and the GxB_RANGE / GxB_STRIDE / GxB_BACKWARDS triples are evaluated — and inverted —
+// in closed form by the kernels; an explicit list is uploaded once (4 bytes per index) and its inverse is one table of `dim` uint32, scattered with plain stores.
+// A list that names an index twice is found by reading the table back through the list (inv[I[k]] != k for the k that lost) and is left to the host route.
+//
+// T = A in C's coordinates (assign_relocate):
+//   rows     source row a becomes row I[a]: len[I[a]] = length of row a, one exclusive scan over C's rows is T's row pointer.  The rows are a permutation, so a
+//            non-increasing I needs no sort.
+//   entries  ONE THREAD PER ENTRY of A (its row from csr_row_indices): dst = rowptr_T[I[a]] + (p - rowptr_A[a]), column J[col]: a hub row of 10^5 entries is
+//            10^5 threads like any other 10^5 entries — no parts, no long-row path; reads and writes are contiguous within a row.
+//   columns  a strictly increasing J keeps every row sorted; any other J gets the segmented row sort of the extract fill (rocPRIM, (column, position) pairs,
+//            then one gather of the values).
+//   traffic  (12 + ts) bytes read and (4 + ts) written per entry of A, 8 bytes per row of C.
+// No atomics anywhere: every output position has exactly one writer.
+#include "grb_assign.hpp"
+#include "grb_device.hpp"
+#include "grb_matops.hpp"
+
+namespace grb {
+
+void segmented_sort_pairs_u32(const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t n, uint32_t nseg, const uint32_t* begins, const uint32_t* ends, int end_bit);   // grb_prims.hip
+
+namespace {
+
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+
+template <int TS> struct WordOf { typedef typename std::conditional<TS == 8, uint64_t, typename std::conditional<TS == 4, uint32_t, typename std::conditional<TS == 2, uint16_t, uint8_t>::type>::type>::type type; };
+
+// index argument on the device, both ways
+struct DIdx { int kind; uint32_t lo, step; uint64_t n; const uint32_t* list; const uint32_t* inv; };
+__device__ __forceinline__ uint32_t idx_at(const DIdx& x, uint64_t k) {
+  switch (x.kind) {
+    case EX_ALL: return (uint32_t)k;
+    case EX_RANGE: return x.lo + (uint32_t)k * x.step;
+    case EX_BACK: return x.lo - (uint32_t)k * x.step;
+    default: return x.list[k];
+  }
+}
+// the k with I[k] == i, or NONE
+__device__ __forceinline__ uint32_t idx_inv(const DIdx& x, uint32_t i) {
+  switch (x.kind) {
+    case EX_ALL: return i;
+    case EX_RANGE: case EX_BACK: {
+      const bool side = x.kind == EX_BACK ? i <= x.lo : i >= x.lo;
+      const uint32_t d = x.kind == EX_BACK ? x.lo - i : i - x.lo, q = d / x.step;
+      return (side && q * x.step == d && q < x.n) ? q : NONE;
+    }
+    default: return x.inv[i];
+  }
+}
+DIdx didx(const ExIdx& x, const DevBuf* inv = nullptr) { return DIdx{x.kind, x.lo, x.step ? x.step : 1u, x.n, x.list, inv ? inv->as<uint32_t>() : nullptr}; }
+
+inline int grid_of(uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (int)b; }
+inline void check_ts(size_t ts) { if (ts != 1 && ts != 2 && ts != 4 && ts != 8) fail(GrB_DOMAIN_MISMATCH, "assign: values of this size have no device route"); }
+#define GRB_AS_TS(ts, CALL) switch (ts) { case 1: { constexpr int TS = 1; CALL; } break; case 2: { constexpr int TS = 2; CALL; } break; case 4: { constexpr int TS = 4; CALL; } break; default: { constexpr int TS = 8; CALL; } break; }
+
+// ---- the inverse table of a list, and the repeat test ------------------------------------------------------------------
+__global__ void k_assign_inv_scatter(const uint32_t* __restrict__ list, uint64_t n, uint32_t* __restrict__ inv) {
+  for (uint64_t k = blockIdx.x * 256ull + threadIdx.x; k < n; k += gridDim.x * 256ull) inv[list[k]] = (uint32_t)k;      // a repeated index: any writer wins
+}
+__global__ void k_assign_inv_check(const uint32_t* __restrict__ list, uint64_t n, const uint32_t* __restrict__ inv, uint32_t* __restrict__ repeat) {
+  for (uint64_t k = blockIdx.x * 256ull + threadIdx.x; k < n; k += gridDim.x * 256ull) if (inv[list[k]] != (uint32_t)k) *repeat = 1u;      // (every writer stores the same value)
+}
+
+// ---- relocate -----------------------------------------------------------------------------------------------------------
+__global__ void k_assign_rowlen(DIdx I, uint64_t ar, const uint32_t* __restrict__ arp, uint32_t* __restrict__ len) {
+  for (uint64_t a = blockIdx.x * 256ull + threadIdx.x; a < ar; a += gridDim.x * 256ull) len[idx_at(I, a)] = arp[a + 1] - arp[a];
+}
+template <int TS>
+__global__ void k_assign_move(uint64_t nnz, const uint32_t* __restrict__ rowidx, const uint32_t* __restrict__ arp, const uint32_t* __restrict__ acol, const uint8_t* __restrict__ aval, DIdx I, DIdx J,
+                              const uint32_t* __restrict__ trp, uint32_t* __restrict__ ocol, uint8_t* __restrict__ oval) {
+  typedef typename WordOf<TS>::type W;
+  for (uint64_t p = blockIdx.x * 256ull + threadIdx.x; p < nnz; p += gridDim.x * 256ull) {
+    const uint32_t a = rowidx[p];
+    const uint64_t dst = (uint64_t)trp[idx_at(I, a)] + (p - arp[a]);
+    ocol[dst] = idx_at(J, acol[p]); ((W*)oval)[dst] = ((const W*)aval)[p];
+  }
+}
+__global__ void k_assign_iota(uint32_t* p, uint64_t n) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) p[i] = (uint32_t)i;
+}
+template <int TS> __global__ void k_assign_gather(const uint32_t* __restrict__ perm, uint64_t n, const uint8_t* __restrict__ val, uint8_t* __restrict__ oval) {
+  typedef typename WordOf<TS>::type W;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) ((W*)oval)[i] = ((const W*)val)[perm[i]];
+}
+
+// ---- the region of C ----------------------------------------------------------------------------------------------------
+__global__ void k_assign_region_keep(uint64_t nnz, const uint32_t* __restrict__ rowidx, const uint32_t* __restrict__ col, DIdx I, DIdx J, uint8_t* __restrict__ keep) {
+  for (uint64_t p = blockIdx.x * 256ull + threadIdx.x; p < nnz; p += gridDim.x * 256ull)
+    keep[p] = (idx_inv(I, rowidx[p]) != NONE && idx_inv(J, col[p]) != NONE) ? 0 : 1;
+}
+
+// ---- w<allow, replace>(I) = accum(w(I), u): one pass over the n positions of w --------------------------------------------
+template <class T, bool MATH>
+__global__ void k_assign_vector(uint64_t n, T* __restrict__ wval, uint8_t* __restrict__ wpres, const uint8_t* __restrict__ allow, DIdx I, const T* __restrict__ uval, const uint8_t* __restrict__ upres,
+                                int accum, bool replace) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
+    const bool ok = allow ? allow[i] != 0 : true;
+    if (ok) {
+      const uint32_t k = idx_inv(I, (uint32_t)i);
+      if (k == NONE) continue;                                               // outside the region: Z == w there
+      const bool up = upres[k] != 0;
+      if (accum >= 0) {
+        if (up) {
+          if (wpres[i]) wval[i] = apply_binop<T, true, MATH>(accum, wval[i], uval[k]);
+          else { wval[i] = uval[k]; wpres[i] = 1; }
+        }
+      } else {
+        if (up) wval[i] = uval[k];
+        wpres[i] = up ? 1 : 0;
+      }
+    } else if (replace) {
+      wpres[i] = 0;
+    }
+  }
+}
+
+template <class D, class S>
+__global__ void k_assign_cast_touched(uint64_t n, D* __restrict__ dst, const S* __restrict__ src, const uint8_t* __restrict__ allow, DIdx I, const uint8_t* __restrict__ upres) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
+    if (allow && !allow[i]) continue;
+    const uint32_t k = idx_inv(I, (uint32_t)i);
+    if (k != NONE && upres[k]) dst[i] = cast_to<D, S>(src[i]);
+  }
+}
+
+// ---- a bitmap as a CSR of one row or one column ------------------------------------------------------------------------------
+__global__ void k_assign_pres_u32(const uint8_t* __restrict__ pres, uint64_t n, uint32_t* __restrict__ out) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i <= n; i += gridDim.x * 256ull) out[i] = (i < n && pres[i]) ? 1u : 0u;
+}
+template <int TS>
+__global__ void k_assign_line_fill(uint64_t n, const uint8_t* __restrict__ lval, const uint8_t* __restrict__ lpres, const uint32_t* __restrict__ pos, bool as_row, uint32_t* __restrict__ ocol, uint8_t* __restrict__ oval) {
+  typedef typename WordOf<TS>::type W;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull)
+    if (lpres[i]) { const uint32_t o = pos[i]; ocol[o] = as_row ? (uint32_t)i : 0u; ((W*)oval)[o] = ((const W*)lval)[i]; }
+}
+__global__ void k_assign_two(uint32_t* p, uint32_t total) { if (threadIdx.x == 0 && blockIdx.x == 0) { p[0] = 0; p[1] = total; } }
+
+}  // namespace
+
+bool assign_inverse(const ExIdx& x, uint64_t dim, DevBuf& inv) {
+  if (x.kind != EX_LIST) return true;
+  if (dim > ASSIGN_TABLE_MAX_DIM) return false;
+  inv.alloc((dim + 1) * 4);                                                  // [dim]: the repeat flag
+  GRB_HIP(hipMemsetAsync(inv.p, 0xFF, dim * 4, stream()));
+  GRB_HIP(hipMemsetAsync(inv.as<uint32_t>() + dim, 0, 4, stream()));
+  if (!x.n) return true;
+  hipLaunchKernelGGL(k_assign_inv_scatter, dim3(grid_of(x.n)), dim3(256), 0, stream(), x.list, x.n, inv.as<uint32_t>());
+  hipLaunchKernelGGL(k_assign_inv_check, dim3(grid_of(x.n)), dim3(256), 0, stream(), x.list, x.n, inv.as<uint32_t>(), inv.as<uint32_t>() + dim);
+  uint32_t repeat = 0;
+  GRB_HIP(hipMemcpyAsync(&repeat, inv.as<uint32_t>() + dim, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+  return repeat == 0;
+}
+
+void assign_relocate(const DevCSR& A, size_t ts, const ExIdx& I, const ExIdx& J, uint32_t crows, uint32_t ccols, DevCSR& T, AssignPlan& plan) {
+  check_ts(ts);
+  if (A.nrows != I.n || A.ncols != J.n) fail(GrB_PANIC, "assign: operand shape does not match the index arguments");      // (the entry points checked it: the kernels' bounds depend on it)
+  const uint64_t nnz = A.nnz;
+  T.clear(); T.nrows = crows; T.ncols = ccols; T.nnz = nnz;
+  T.rowptr.alloc(((size_t)crows + 1) * 4); T.col.alloc(nnz * 4 + 4); T.val.alloc(nnz * ts + 8);
+  plan.rowsort = false;
+  if (!nnz) { GRB_HIP(hipMemsetAsync(T.rowptr.p, 0, ((size_t)crows + 1) * 4, stream())); T.valid = true; return; }
+  const DIdx di = didx(I), dj = didx(J);
+  DevBuf len(((size_t)crows + 1) * 4), rowidx(nnz * 4 + 4);
+  GRB_HIP(hipMemsetAsync(len.p, 0, ((size_t)crows + 1) * 4, stream()));
+  hipLaunchKernelGGL(k_assign_rowlen, dim3(grid_of(I.n)), dim3(256), 0, stream(), di, I.n, A.rowptr.as<uint32_t>(), len.as<uint32_t>());
+  exclusive_scan_u32(len.as<uint32_t>(), T.rowptr.as<uint32_t>(), (uint64_t)crows + 1);
+  csr_row_indices(A, rowidx.as<uint32_t>());
+  const bool rowsort = !J.increasing && J.n > 1;
+  DevBuf ucol, uval;                                                         // unsorted columns / values when the rows are sorted afterwards
+  if (rowsort) { ucol.alloc(nnz * 4); uval.alloc(nnz * ts); }
+  uint32_t* oc = rowsort ? ucol.as<uint32_t>() : T.col.as<uint32_t>(); uint8_t* ov = rowsort ? uval.as<uint8_t>() : T.val.as<uint8_t>();
+  GRB_AS_TS(ts, hipLaunchKernelGGL((k_assign_move<TS>), dim3(grid_of(nnz)), dim3(256), 0, stream(), nnz, rowidx.as<uint32_t>(), A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), A.val.as<uint8_t>(), di, dj,
+                                   T.rowptr.as<uint32_t>(), oc, ov));
+  if (rowsort) {
+    DevBuf iota(nnz * 4), perm(nnz * 4);
+    hipLaunchKernelGGL(k_assign_iota, dim3(grid_of(nnz)), dim3(256), 0, stream(), iota.as<uint32_t>(), nnz);
+    int bits = 1; while (bits < 32 && (1ull << bits) < (uint64_t)ccols) bits++;
+    segmented_sort_pairs_u32(ucol.as<uint32_t>(), T.col.as<uint32_t>(), iota.as<uint32_t>(), perm.as<uint32_t>(), nnz, crows, T.rowptr.as<uint32_t>(), T.rowptr.as<uint32_t>() + 1, bits);
+    GRB_AS_TS(ts, hipLaunchKernelGGL((k_assign_gather<TS>), dim3(grid_of(nnz)), dim3(256), 0, stream(), perm.as<uint32_t>(), nnz, uval.as<uint8_t>(), T.val.as<uint8_t>()));
+  }
+  GRB_HIP(hipStreamSynchronize(stream()));                                   // temporaries are released on scope exit; the pool is stream-ordered
+  plan.rowsort = rowsort;
+  T.valid = true;
+}
+
+void assign_region_keep(const DevCSR& C, const ExIdx& I, const DevBuf& inv_i, const ExIdx& J, const DevBuf& inv_j, uint8_t* keep) {
+  if (!C.nnz) return;
+  DevBuf rowidx(C.nnz * 4 + 4);
+  csr_row_indices(C, rowidx.as<uint32_t>());
+  hipLaunchKernelGGL(k_assign_region_keep, dim3(grid_of(C.nnz)), dim3(256), 0, stream(), C.nnz, rowidx.as<uint32_t>(), C.col.as<uint32_t>(), didx(I, &inv_i), didx(J, &inv_j), keep);
+  GRB_HIP(hipStreamSynchronize(stream()));
+}
+
+void assign_vector(int code, uint64_t n, void* wval, uint8_t* wpres, const uint8_t* allow, const ExIdx& I, const DevBuf& inv, const void* uval, const uint8_t* upres, int accum, bool replace) {
+  if (!n) return;
+  const DIdx di = didx(I, &inv);
+  dispatch_type(code, [&]<class T>() {
+    if (accum >= 0 && binop_needs_math(accum)) hipLaunchKernelGGL((k_assign_vector<T, true>), dim3(grid_of(n)), dim3(256), 0, stream(), n, (T*)wval, wpres, allow, di, (const T*)uval, upres, accum, replace);
+    else hipLaunchKernelGGL((k_assign_vector<T, false>), dim3(grid_of(n)), dim3(256), 0, stream(), n, (T*)wval, wpres, allow, di, (const T*)uval, upres, accum, replace);
+  });
+}
+
+void assign_cast_touched(int dst_code, void* dst, int src_code, const void* src, uint64_t n, const uint8_t* allow, const ExIdx& I, const DevBuf& inv, const uint8_t* upres) {
+  if (!n) return;
+  const DIdx di = didx(I, &inv);
+  dispatch_type(src_code, [&]<class S>() {
+    dispatch_type(dst_code, [&]<class D>() {
+      hipLaunchKernelGGL((k_assign_cast_touched<D, S>), dim3(grid_of(n)), dim3(256), 0, stream(), n, (D*)dst, (const S*)src, allow, di, upres);
+    });
+  });
+}
+
+void assign_line_to_csr(size_t ts, uint64_t n, const void* lval, const uint8_t* lpres, bool as_row, DevCSR& T) {
+  check_ts(ts);
+  T.clear(); T.nrows = as_row ? 1u : (uint32_t)n; T.ncols = as_row ? (uint32_t)n : 1u;
+  DevBuf flags((n + 1) * 4), pos_buf;
+  hipLaunchKernelGGL(k_assign_pres_u32, dim3(grid_of(n + 1)), dim3(256), 0, stream(), lpres, n, flags.as<uint32_t>());
+  // a column's entry positions ARE its row pointer: the scan goes straight into it
+  if (as_row) { pos_buf.alloc((n + 1) * 4); T.rowptr.alloc(8); } else T.rowptr.alloc((n + 1) * 4);
+  uint32_t* pos = as_row ? pos_buf.as<uint32_t>() : T.rowptr.as<uint32_t>();
+  exclusive_scan_u32(flags.as<uint32_t>(), pos, n + 1);
+  uint32_t total = 0;
+  GRB_HIP(hipMemcpyAsync(&total, pos + n, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+  T.nnz = total; T.col.alloc((size_t)total * 4 + 4); T.val.alloc((size_t)total * ts + 8);
+  if (as_row) hipLaunchKernelGGL(k_assign_two, dim3(1), dim3(64), 0, stream(), T.rowptr.as<uint32_t>(), total);
+  if (total) { GRB_AS_TS(ts, hipLaunchKernelGGL((k_assign_line_fill<TS>), dim3(grid_of(n)), dim3(256), 0, stream(), n, (const uint8_t*)lval, lpres, pos, as_row, T.col.as<uint32_t>(), T.val.as<uint8_t>())); }
+  GRB_HIP(hipStreamSynchronize(stream()));
+  T.valid = true;
+}
+
+}  // namespace grb

@@ -1,4 +1,4 @@
-// grb_host_ops.cpp — index-list extract / assign and kronecker, on the host mirror.
+// grb_host_ops.cpp — index-list extract / assign (host mirror, or HBM for device-resident and large containers) and kronecker (host mirror).
 //
 //   GrB_Vector_extract, GrB_Col_extract, GrB_Matrix_extract     <- Vector / Matrix slicing  (pygraphblas/vector.py:1526-1573, matrix.py:2807-2990)
 //   GrB_Vector_assign, GrB_Row_assign, GrB_Col_assign, GrB_Matrix_assign <- slice assignment (vector.py:1447-1492, matrix.py:2992-3130)
@@ -13,9 +13,12 @@
 // row / column.
 //
 // The three extract entry points have a second route: when the operand lives in HBM (or is large) they run the kernels of
-// grb_extract.hip and the device write-back instead — see `extract_on_device` below.  Assign and kronecker have the host route only.
+// grb_extract.hip and the device write-back instead — see `extract_on_device` below.  The four container forms of assign have one too
+// (grb_assign.hip, `assign_on_device`).  Kronecker has the host route only.
 #include "grb_opcommon.hpp"
 #include "grb_extract.hpp"
+#include "grb_assign.hpp"
+#include "grb_matops.hpp"
 #include <array>
 #include <map>
 
@@ -362,6 +365,133 @@ void region_update(Map& C, int ccode, const Map& A, int acode, const std::vector
   for (auto& kv : upd) if (kv.second.first && mk.allows(mkey(kv.first))) out[kv.first] = kv.second.second;
   C.swap(out);
 }
+
+// ---- assign: which route ----------------------------------------------------------------------------------------------------------
+// The device route (grb_assign.hip) is taken when a HIP device is present, every container of the call has an HBM layout (dev_capable; none a
+// bitmap-only batch matrix), the operand is not the output, a mask object accompanies a complemented mask, and C either lives in HBM only or C or
+// the operand holds at least N entries, N measured per entry point against this file's host route, upload included.
+// Small host-resident containers — notebook slices — keep the host route.  GRB_MI355X_ASSIGN=0 forces the host route, =1 the device route wherever it
+// is legal (read per call: a test hook).  A list that names an index twice is found on the device and handed back to the host route (which takes the
+// last occurrence): the `*_device` functions return false for it, before anything was written.
+constexpr uint64_t ASSIGN_DEVICE_MIN_ENTRIES = 30000;            // GrB_Matrix_assign
+constexpr uint64_t ASSIGN_ROW_DEVICE_MIN_ENTRIES = 3000000;      // GrB_Row_assign: the host replaces the row's run of tuples in place, cheap up to ~1e6 entries
+constexpr uint64_t ASSIGN_COL_DEVICE_MIN_ENTRIES = 100000;       // GrB_Col_assign: the host's one merge pass
+constexpr uint64_t ASSIGN_VEC_DEVICE_MIN_ENTRIES = 500;          // GrB_Vector_assign: the host route is map-based for every shape (the smallest size measured; the device route won all)
+int assign_env() { const char* e = getenv("GRB_MI355X_ASSIGN"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }
+uint64_t entries_known(GrB_Vector u) { return u->host_valid ? vec_nvals(u) : (u->dnvals_known ? u->dnvals : 0); }      // (no device work for a count)
+// `operand_entries`: asked only after the variable, the device and the residency of C have not decided
+template <class F> bool assign_on_device(GrB_Matrix C, bool others_capable, uint64_t min_entries, F&& operand_entries) {
+  const int env = assign_env();
+  if (env == 0 || !device_ok() || !others_capable || !dev_capable(C) || mat_bitmap_only(C)) return false;
+  if (env == 1) return true;
+  if (C->dev_valid && !C->host_valid) return true;                      // it lives in HBM: it is not downloaded for this
+  return mat_nvals(C) >= min_entries || operand_entries() >= min_entries;
+}
+template <class F> bool assign_on_device(GrB_Vector w, bool others_capable, uint64_t min_entries, F&& operand_entries) {
+  const int env = assign_env();
+  if (env == 0 || !device_ok() || !others_capable || !dev_capable(w)) return false;
+  if (env == 1) return true;
+  if (w->dev_valid && !w->host_valid) return true;
+  return entries_known(w) >= min_entries || operand_entries() >= min_entries;
+}
+bool mat_capable(GrB_Matrix A) { return dev_capable(A) && !(A && mat_bitmap_only(A)); }
+const char* kind_name(const ExIdx& x) { return x.kind == EX_ALL ? "all" : x.kind == EX_LIST ? "list" : "range"; }
+const char* accum_name(GrB_BinaryOp accum) { return accum ? accum->name : "none"; }
+
+// C(I, J) := T (T in C's coordinates, nothing outside I x J), then C<M, replace> = that: Z = (C without its entries inside I x J) u T, written back
+// without an accumulator.  csr_compact and csr_ewise(SECOND) of the tree; the two patterns are disjoint.
+void region_replace(GrB_Matrix C, GrB_Matrix Mask, const DescView& dv, DevCSR& T, int tcode, const ExIdx& ri, const DevBuf& inv_i, const ExIdx& ci, const DevBuf& inv_j) {
+  const int ccode = C->type->code; const size_t cs = C->type->size;
+  if (!C->csr.nnz) { matrix_write_back(C, T, tcode, Mask, dv, nullptr, false); return; }
+  DevBuf keep(C->csr.nnz + 1); DevCSR Rest;
+  assign_region_keep(C->csr, ri, inv_i, ci, inv_j, keep.as<uint8_t>());
+  csr_compact(C->csr, C->csr.val.p, cs, keep.as<uint8_t>(), Rest);
+  if (!Rest.nnz) { matrix_write_back(C, T, tcode, Mask, dv, nullptr, false); return; }
+  if (!T.nnz) { matrix_write_back(C, Rest, ccode, Mask, dv, nullptr, false); return; }
+  DevBuf tc; const void* tv = cast_values(ccode, tcode, T.val.p, T.nnz, tc);
+  DevCSR Z; csr_ewise(ccode, Rest, Rest.val.p, T, tv, B_SECOND, true, Z);
+  matrix_write_back(C, Z, ccode, Mask, dv, nullptr, false);
+}
+
+bool assign_matrix_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, const DescView& dv) {
+  ExIdx ri, ci; extract_parse(ri, I, ni, C->nrows, "assign"); extract_parse(ci, J, nj, C->ncols, "assign");
+  const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
+  if (ar != ri.n || ac != ci.n || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "assign: the matrix must be |I| x |J|");
+  if (accum) check_binop(accum, "accum");
+  DevBuf keep_i, keep_j, inv_i, inv_j; extract_upload(ri, keep_i); extract_upload(ci, keep_j);
+  if (!assign_inverse(ri, C->nrows, inv_i) || !assign_inverse(ci, C->ncols, inv_j)) return false;
+  mat_to_device(C); mat_to_device(A);
+  // op(A) under GrB_DESC_T0: the operand (the smaller side) is transposed, never C
+  const DevCSR& Ad = dv.tran0 ? mat_csc(A) : A->csr;
+  DevCSR T; AssignPlan plan;
+  assign_relocate(Ad, A->type->size, ri, ci, (uint32_t)C->nrows, (uint32_t)C->ncols, T, plan);
+  g_last_plan = std::string("assign_matrix<rows=") + kind_name(ri) + ",cols=" + kind_name(ci) + ",rowsort=" + (plan.rowsort ? "1" : "0") + ",transpose=" + (dv.tran0 ? "1" : "0") + ",accum=" + accum_name(accum) +
+                "> k_assign_rowlen k_assign_move " + (accum ? "" : "k_assign_region_keep ");
+  if (accum) matrix_write_back(C, T, A->type->code, Mask, dv, accum, false);      // accum(C, T) on the union of the patterns: entries of C inside the region that A lacks are kept
+  else region_replace(C, Mask, dv, T, A->type->code, ri, inv_i, ci, inv_j);
+  return true;
+}
+
+// line<allow, replace>(I) = accum(line(I), u) on a bitmap of type `lcode`, in place: u's values go through the accumulator's domain as the host's `combine` does
+void line_assign(int lcode, uint64_t n, void* lval, uint8_t* lpres, const uint8_t* allow, const ExIdx& idx, const DevBuf& inv, GrB_Vector u, GrB_BinaryOp accum, bool replace) {
+  const int ecode = accum ? accum->xtype->code : lcode;
+  DevBuf uc, lc;
+  const void* uv = cast_values(ecode, u->type->code, u->dval.p, u->n, uc);
+  if (ecode == lcode) { assign_vector(lcode, n, lval, lpres, allow, idx, inv, uv, u->dpres.as<uint8_t>(), accum ? accum->opcode : -1, replace); }
+  else {
+    lc.alloc(n * type_size(ecode) + 1);
+    vec_cast_values(ecode, lc.p, lcode, lval, n);
+    assign_vector(ecode, n, lc.p, lpres, allow, idx, inv, uv, u->dpres.as<uint8_t>(), accum->opcode, replace);
+    assign_cast_touched(lcode, lval, ecode, lc.p, n, allow, idx, inv, u->dpres.as<uint8_t>());      // only what the assign wrote comes back: every other value of the line keeps its bits
+  }
+  GRB_HIP(hipStreamSynchronize(stream()));                              // (the cast copies return to the pool)
+}
+
+bool assign_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, const GrB_Index* I, GrB_Index ni, const DescView& dv) {
+  ExIdx idx; extract_parse(idx, I, ni, w->n, "assign");
+  if (u->n != idx.n || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "assign: the vector's size must equal the number of indices");
+  if (accum) check_binop(accum, "accum");
+  DevBuf keep, inv; extract_upload(idx, keep);
+  if (!assign_inverse(idx, w->n, inv)) return false;
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, w->n, allow_buf, &nothing);
+  vec_to_device(u); vec_to_device(w);
+  line_assign(w->type->code, w->n, w->dval.p, w->dpres.as<uint8_t>(), allow, idx, inv, u, accum, dv.replace);
+  vec_invalidate_host(w);
+  w->fe_lb = 0; w->fe_lb_key = 0; w->dnvals_known = false; w->dnvals = 0;
+  g_last_plan = std::string("assign_vector<index=") + kind_name(idx) + ",accum=" + accum_name(accum) + "> k_assign_vector ";
+  return true;
+}
+
+// C(i, J) = u (`is_row`) or C(I, j) = u: the line of C as a bitmap, the vector kernel on it under the vector mask, then the line put back as a region of C
+bool assign_line_device(GrB_Matrix C, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, bool is_row, uint64_t fixed, const GrB_Index* L, GrB_Index nl, const DescView& dv) {
+  const uint64_t len = is_row ? C->ncols : C->nrows;
+  const char* const msg = is_row ? "assign: the vector's size must equal the number of column indices" : "assign: the vector's size must equal the number of row indices";
+  ExIdx idx; extract_parse(idx, L, nl, len, "assign");
+  if (u->n != idx.n || (mask && mask->n != len)) fail(GrB_DIMENSION_MISMATCH, msg);
+  if (accum) check_binop(accum, "accum");
+  if (!len) return false;
+  DevBuf keep, inv; extract_upload(idx, keep);
+  if (!assign_inverse(idx, len, inv)) return false;
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, len, allow_buf, &nothing);
+  mat_to_device(C); vec_to_device(u);
+  const int ccode = C->type->code; const size_t cs = C->type->size;
+  ExIdx all; all.kind = EX_ALL; all.n = len;
+  DevBuf lval(len * cs + 8), lpres(len + 1);
+  extract_line(C->csr, cs, is_row, (uint32_t)fixed, all, lval.p, lpres.as<uint8_t>());
+  line_assign(ccode, len, lval.p, lpres.as<uint8_t>(), allow, idx, inv, u, accum, dv.replace);
+  DevCSR Tl, T; AssignPlan plan;
+  assign_line_to_csr(cs, len, lval.p, lpres.as<uint8_t>(), is_row, Tl);
+  ExIdx one; one.kind = EX_RANGE; one.lo = (uint32_t)fixed; one.step = 1; one.n = 1;
+  const ExIdx& ri = is_row ? one : all; const ExIdx& ci = is_row ? all : one;
+  assign_relocate(Tl, cs, ri, ci, (uint32_t)C->nrows, (uint32_t)C->ncols, T, plan);
+  g_last_plan = std::string(is_row ? "assign_row<index=" : "assign_col<index=") + kind_name(idx) + ",accum=" + accum_name(accum) + "> " + (is_row ? "k_extract_row_scatter" : "k_extract_lookup") +
+                " k_assign_vector k_assign_line_fill k_assign_move k_assign_region_keep ";
+  const DevBuf none_i, none_j;
+  region_replace(C, nullptr, DescView(nullptr), T, ccode, ri, none_i, ci, none_j);
+  return true;
+}
 }  // namespace
 // the whole-container fast paths forward to eWiseAdd without the caller's descriptor: only when it asks for nothing they would
 // drop (a complemented mask without a mask object allows no writes at all; an invalid descriptor is the general path's error)
@@ -374,6 +504,8 @@ GrB_Info GrB_Vector_assign(GrB_Vector w, const GrB_Vector mask, const GrB_Binary
   return guarded(w, [&] {
     check_v(u, "assign"); if (mask) check_v(mask, "assign");
     const DescView dv(desc);
+    vec_gate(w); vec_gate(u);                                            // deferred work that involves them is completed first, as every reader does
+    if (u != w && (mask || !dv.mask_comp) && assign_on_device(w, dev_capable(u) && dev_capable(mask), ASSIGN_VEC_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }) && assign_vector_device(w, mask, accum, u, I, ni, dv)) return;
     const auto idx = indices(I, ni, w->n, "assign");
     if (u->n != idx.size() || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "assign: the vector's size must equal the number of indices");
     Map C = load(w), U = load(u), Mm; if (mask) Mm = load(mask);
@@ -395,6 +527,7 @@ GrB_Info GrB_Matrix_assign(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binary
   return guarded(C, [&] {
     check_m(A, "assign"); if (Mask) check_m(Mask, "assign");
     const DescView dv(desc);
+    if (A != C && (Mask || !dv.mask_comp) && assign_on_device(C, mat_capable(A) && mat_capable(Mask), ASSIGN_DEVICE_MIN_ENTRIES, [&] { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }) && assign_matrix_device(C, Mask, accum, A, I, ni, J, nj, dv)) return;
     const auto ri = indices(I, ni, C->nrows, "assign"), ci = indices(J, nj, C->ncols, "assign");
     const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
     if (ar != ri.size() || ac != ci.size() || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "assign: the matrix must be |I| x |J|");
@@ -439,6 +572,8 @@ GrB_Info GrB_Row_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp 
     check_v(u, "assign"); if (mask) check_v(mask, "assign");
     const DescView dv(desc);
     if (i >= C->nrows) fail(GrB_INVALID_INDEX, "assign: row index out of range");
+    vec_gate(u);
+    if ((mask || !dv.mask_comp) && assign_on_device(C, dev_capable(u) && dev_capable(mask), ASSIGN_ROW_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }) && assign_line_device(C, mask, accum, u, true, i, J, nj, dv)) return;
     if (!mask && !dv.mask_comp && J == GrB_ALL && u->n == C->ncols && C->type->code < T_FC32 && u->type->code < T_FC32) {   // `M[i] = v`: the row's run of tuples is replaced in place (GrB_ALL is never listed: C may be 2^60 wide)
       mat_to_host(C);
       const auto r = row_range(C, i); Line cur; cur.reserve(r.second - r.first);
@@ -463,6 +598,8 @@ GrB_Info GrB_Col_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp 
     check_v(u, "assign"); if (mask) check_v(mask, "assign");
     const DescView dv(desc);
     if (j >= C->ncols) fail(GrB_INVALID_INDEX, "assign: column index out of range");
+    vec_gate(u);
+    if ((mask || !dv.mask_comp) && assign_on_device(C, dev_capable(u) && dev_capable(mask), ASSIGN_COL_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }) && assign_line_device(C, mask, accum, u, false, j, I, ni, dv)) return;
     if (!mask && !dv.mask_comp && I == GrB_ALL && u->n == C->nrows && C->type->code < T_FC32 && u->type->code < T_FC32) {   // `M[:, j] = v`: one merge pass over the tuples (GrB_ALL is never listed)
       replace_line(C, false, j, assigned_line(line_of(C, false, j), C->type->code, u, accum));
       return;

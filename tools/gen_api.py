@@ -467,7 +467,7 @@ GrB_Info GrBX_timer_start(void);                   /* hipEventRecord on the libr
 GrB_Info GrBX_timer_stop(float *milliseconds);     /* hipEventRecord + synchronize + elapsed */
 GrB_Info GrBX_device_info(char *name, int name_len, int *compute_units, size_t *hbm_bytes);
 GrB_Info GrBX_memory_in_use(size_t *bytes);
-GrB_Info GrBX_last_kernel_plan(char *buf, int len); /* which kernels the last hot-path call launched; the device route of an index-list extract leaves "extract_matrix<cols=all|range|table|bisect,rowsort=0|1,transpose=0|1> ...", "extract_col<...>" or "extract_vector<...>" */
+GrB_Info GrBX_last_kernel_plan(char *buf, int len); /* which kernels the last hot-path call launched; the device route of an index-list extract leaves "extract_matrix<cols=all|range|table|bisect,rowsort=0|1,transpose=0|1> ...", "extract_col<...>" or "extract_vector<...>", that of an index-list assign "assign_matrix<rows=..,cols=..,rowsort=0|1,transpose=0|1,accum=..> ...", "assign_row<...>", "assign_col<...>" or "assign_vector<index=..,accum=..>" */
 GrB_Info GrBX_last_plan_build_ms(float *milliseconds); /* device time of the most recent SpMV plan build (kernel X), 0 if none */
 GrB_Info GrBX_lazy_stats(uint64_t *chains, uint64_t *nodes, uint64_t *fills_folded, uint64_t *reduces_fused); /* non-blocking mode: element-wise chain kernels run, operations they carried, `w(:) = s` fills folded into a product's store, reductions fused into a chain */
 GrB_Info GrBX_chain_jit_stats(uint64_t *compiled, uint64_t *launched); /* deferred element-wise chains compiled with hipRTC (grb_chain_jit.cpp): kernels compiled, launches through them */
