@@ -149,6 +149,7 @@ template <class E> __device__ __forceinline__ E xt_readlane(E v, int src) {     
 // Cache policy: default.  (Measured: sc0 or sc1 on these loads change nothing; nt makes them leave the L2 and the whole
 // product 0.285 -> 0.392 ms — the L2 residency of the panel's lines is what the design lives on.)
 typedef uint32_t xt_v2u __attribute__((ext_vector_type(2)));
+#define XT_K __attribute__((address_space(4)))      // constant address space: a load at a wave-uniform address goes through the scalar data cache (plan arrays only: they never change during a launch)
 #ifndef XT_GATHER_AUX
 #define XT_GATHER_AUX 0
 #endif
@@ -238,7 +239,15 @@ __global__ __launch_bounds__(W * 64, 1) void k_spmv_tiles(const XtCall<T> call, 
   __syncthreads();                                      // (every wave is done with the table and the chunk counter of the stream before)
   if (threadIdx.x == 0) s_next = 0;
   const bool use_a = sr.uses_a() && a.aval != nullptr, use_u = sr.uses_u();
-  if (use_u) for (uint32_t h = threadIdx.x; h < a.nhot; h += XT_WAVES_ * 64) s_hot[h] = wp_ld(a.xhot + h);      // the table's contents, gathered from u once per call
+  // the table's contents, gathered from u once per call (k_xp_hot_gather): ALL of a thread's loads are in flight before its first LDS write (a loop of
+  // load, wait, write made every wave pay one memory latency per pass, 19 for FP64), and the writes come behind the first tiles' column loads below.
+  // Loads behind the table's end are out of the descriptor's range: no request.  HB registers hold a batch; one batch is the whole table for 4- and
+  // 8-byte types.
+  constexpr int HB = sizeof(T) == 8 ? 20 : 40, HSTEP = XT_WAVES_ * 64;
+  const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.xhot, (short)0, (int)(use_u ? a.nhot * (uint32_t)sizeof(T) : 0u), 0x00020000);
+  T hreg[HB];
+#pragma unroll
+  for (int i = 0; i < HB; i++) hreg[i] = xt_buf_load<T>(h_rsrc, (threadIdx.x + (uint32_t)(i * HSTEP)) * (uint32_t)sizeof(T));
   constexpr bool ZSLOT = !xt_fmt<T>::C16;               // the plan left the table's last slot free (32-bit entry words are this type's own format, not a measurement variant)
   if constexpr (!C16 && ZSLOT) { if (threadIdx.x == 0) { T z; __builtin_memset(&z, 0, sizeof(T)); s_hot[H - 1] = z; } }      // the zero slot (nhot <= H - 1)
   // (16-bit words: the range covers whole tiles — the plan pads them with zeros — because the range check works on dwords and an
@@ -249,7 +258,7 @@ __global__ __launch_bounds__(W * 64, 1) void k_spmv_tiles(const XtCall<T> call, 
   const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.aval, (short)0, (int)(!a.aval ? 0u : (VB == (int)sizeof(T) ? a.nnz * (uint32_t)sizeof(T) : a.ntiles * (uint32_t)WP_ENT * (uint32_t)VB)), 0x00020000);
   // (narrow plane: the range covers whole tiles — the plan's padding is zeros — because a lane's four values are ONE 8-byte load and the range check would
   //  cut the last lane's live values off with the panel's end; the wide plane's loads are checked dword by dword)
-  __syncthreads();
+  __syncthreads();                                      // (the chunk counter is zero for every wave: the first tiles below may already draw dynamic chunks.  The table is NOT filled yet)
   // Work split (see k_spmv_wavepipe): chunk ids [0, dyn0) are static ranges of s0 chunks dealt to (workgroup, wave), ids >= dyn0
   // are handed out one at a time by the workgroup's LDS counter; workgroup j of the panel owns those congruent to j.
   const uint32_t K = a.tiles_per_chunk, nchunks = (K + a.ntiles - 1) / K;
@@ -279,13 +288,16 @@ __global__ __launch_bounds__(W * 64, 1) void k_spmv_tiles(const XtCall<T> call, 
   static_assert(!C16 || WP_PER == 4, "the 16-bit column plane packs a lane's four words in two dwords");
   auto load_cols = [&](XtStage<T>& s) __attribute__((always_inline)) {
     const bool ok = s.tile != WP_NONE;
+    // the tile's metadata is the same in all 64 lanes: it comes through the scalar data cache into scalar registers (a load from the constant
+    // address space at a wave-uniform index), not as a vector-memory instruction whose lanes all fetch the same 8 bytes
+    const uint32_t ut = (uint32_t)__builtin_amdgcn_readfirstlane((int)(ok ? s.tile : 0u));
     if constexpr (C16) {
       xt_stream_load<uint32_t, 2>(c_rsrc, ok ? (s.tile * (uint32_t)WP_ENT + lane * WP_PER) * 2u : 0xFFFFFFFFu, s.h);
-      const uint2 ti = *(const uint2*)(a.tinfo + 2u * (ok ? s.tile : 0u));
+      const xt_v2u ti = ((const XT_K xt_v2u*)(uintptr_t)a.tinfo)[ut];
       s.rf = ti.x; s.cb = ti.y;
     } else {
       xt_stream_load<uint32_t, WP_PER>(c_rsrc, ok ? (s.tile * (uint32_t)WP_ENT + lane * WP_PER) * 4u : 0xFFFFFFFFu, s.c);
-      s.rf = wp_ld(a.trow + (ok ? s.tile : 0u));
+      s.rf = ((const XT_K uint32_t*)(uintptr_t)a.trow)[ut];
     }
   };
   // 16-bit format, one tile behind load_cols: the lane's cold entries are consecutive halfwords of `extras` (entry order =
@@ -364,7 +376,19 @@ __global__ __launch_bounds__(W * 64, 1) void k_spmv_tiles(const XtCall<T> call, 
 #endif
   T carry = sr.identity; bool carry_has = false;        // partial of the sub-row the current tile starts in (wave-uniform)
 #pragma unroll
-  for (int d = 0; d < D + 2; d++) { S[d].tile = next_tile(); load_cols(S[d]); }
+  for (int d = 0; d < D + 2; d++) { S[d].tile = next_tile(); load_cols(S[d]); }      // (they do not read the table: requested before it is written)
+  // the table's LDS writes, behind the barrier at the top of the stream (every wave is done with the table of the stream before)
+#pragma unroll
+  for (int i = 0; i < HB; i++) { const uint32_t h = threadIdx.x + (uint32_t)(i * HSTEP); if (use_u && h < a.nhot) s_hot[h] = hreg[i]; }
+  if constexpr (H > HB * HSTEP) {                       // (1- and 2-byte types: the rest of the table, a batch at a time)
+    for (uint32_t base = (uint32_t)(HB * HSTEP); use_u && base < a.nhot; base += (uint32_t)(HB * HSTEP)) {
+#pragma unroll
+      for (int i = 0; i < HB; i++) hreg[i] = xt_buf_load<T>(h_rsrc, (base + threadIdx.x + (uint32_t)(i * HSTEP)) * (uint32_t)sizeof(T));
+#pragma unroll
+      for (int i = 0; i < HB; i++) { const uint32_t h = base + threadIdx.x + (uint32_t)(i * HSTEP); if (h < a.nhot) s_hot[h] = hreg[i]; }
+    }
+  }
+  __syncthreads();                                      // the table is complete
 #pragma unroll
   for (int d = 0; d < D + 1; d++) load_extras(S[d]);
 #pragma unroll
