@@ -118,7 +118,7 @@ const char* bin_expr(int op, bool f32) {           // z = f(x, y) on T: grb_ops.
 }
 const char* un_expr(int op) {                       // apply_unop<T> for floating-point T
   switch (op) {
-    case U_IDENTITY: case U_BNOT: return "x"; case U_AINV: return "(T)0 - x"; case U_MINV: return "(T)1 / x"; case U_LNOT: return "(T)(x == 0)";
+    case U_IDENTITY: case U_BNOT: return "x"; case U_AINV: return "-x"; case U_MINV: return "(T)1 / x"; case U_LNOT: return "(T)(x == 0)";
     case U_ONE: return "(T)1"; case U_ABS: return "(T)fabs((double)x)";
     default: return nullptr;
   }

@@ -120,8 +120,26 @@ template <class T> GRB_HD T int_div(T x, T y) {
 }
 
 template <class T> GRB_HD T int_pow(T x, T y) {
-  // SuiteSparse computes integer pow through double pow() and a saturating cast back.
-  return cast_to<T, double>(pow((double)x, (double)y));
+  // SuiteSparse computes integer pow through double pow() and a saturating cast back.  The device's pow() is not correctly rounded
+  // (pow(3, 1) came back just below 3, which the cast truncates to 2), so the correctly rounded value is formed exactly: |x|^y in
+  // 64 bits, rounded to double once by the conversion; a magnitude of 2^64 or more saturates in every integer type anyway.
+  typedef typename std::make_unsigned<T>::type U;
+  bool neg = false; uint64_t b;
+  if constexpr (std::is_signed<T>::value) { neg = x < 0 && ((uint64_t)y & 1); b = x < 0 ? (uint64_t)0 - (uint64_t)(int64_t)x : (uint64_t)x; }
+  else b = (uint64_t)x;
+  if (y == 0) return (T)1;                                             // pow(x, 0) = 1 for every x
+  if (std::is_signed<T>::value && y < 0) {                             // pow(0, y < 0) = +inf; |x| = 1 keeps its sign by parity; |x| > 1 truncates to 0
+    if (b == 0) return std::numeric_limits<T>::max();
+    return b == 1 ? (neg ? (T)-1 : (T)1) : (T)0;
+  }
+  uint64_t e = (uint64_t)(U)y, m = 1; bool over = false;
+  if (b <= 1) m = b;
+  else while (e) {                                                     // (b >= 2: at most 64 multiplications before the magnitude leaves 64 bits)
+    if (__builtin_mul_overflow(m, b, &m)) { over = true; break; }
+    e--;
+  }
+  const double d = over ? INFINITY : (double)m;
+  return cast_to<T, double>(neg ? -d : d);
 }
 
 template <class T> GRB_HD T wrap_add(T a, T b) {
@@ -250,13 +268,14 @@ template <class T, bool MATH = true> GRB_HD T apply_unop(int op, T x) {
   if constexpr (is_bool<T>::value) {
     switch (op) {
       case U_LNOT: return bool8(!(bool)x);
-      case U_ONE: return bool8(true);
-      default: return x;  // IDENTITY, AINV, MINV, ABS are identity on BOOL
+      case U_ONE: case U_MINV: return bool8(true);  // MINV(x) = DIV(true, x), and DIV is FIRST on BOOL [upstream semantics]
+      default: return x;  // IDENTITY, AINV, ABS are identity on BOOL
     }
   } else {
     switch (op) {
       case U_IDENTITY: return x;
-      case U_AINV: return wrap_sub((T)0, x);
+      case U_AINV:
+        if constexpr (std::is_floating_point<T>::value) return -x; else return wrap_sub((T)0, x);   // (0 - x would turn -(+0) into +0)
       case U_MINV:
         if constexpr (std::is_floating_point<T>::value) return (T)1 / x; else return int_div((T)1, x);
       case U_LNOT: return (T)(x == 0);
@@ -281,8 +300,8 @@ template <class T, bool MATH = true> GRB_HD T apply_unop(int op, T x) {
         case U_ATANH: return (T)atanh(d);
         case U_SIGNUM: return (T)(d != d ? d : (d > 0) - (d < 0));
         case U_CEIL: return (T)ceil(d);  case U_FLOOR: return (T)floor(d); case U_ROUND: return (T)round(d);
-        case U_TRUNC: return (T)trunc(d); case U_EXP2: return (T)exp2(d); case U_EXPM1: return (T)expm1(d);
-        case U_LOG10: return (T)log10(d); case U_LOG1P: return (T)log1p(d); case U_LGAMMA: return (T)lgamma(d);
+        case U_TRUNC: return (T)trunc(d); case U_EXP2: return (T)exp2(d); case U_EXPM1: return (T)(d == 0 ? d : expm1(d));   // (the device expm1 / log1p return +0 for -0; C99 F.9.3: +-0 -> +-0)
+        case U_LOG10: return (T)log10(d); case U_LOG1P: return (T)(d == 0 ? d : log1p(d)); case U_LGAMMA: return (T)lgamma(d);
         case U_TGAMMA: return (T)tgamma(d); case U_ERF: return (T)erf(d); case U_ERFC: return (T)erfc(d);
         case U_FREXPX: { int e; return (T)frexp(d, &e); }
         case U_FREXPE: { int e; (void)frexp(d, &e); return (T)e; }

@@ -180,7 +180,8 @@ static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_
   const int xc = op->xtype->code;
   // one pass when everything works in w's own type (round 6): the mask read in place, T(i) in a register, the write-back in the same store
   {
-    static const bool off = getenv("GRB_MI355X_EWISE_FUSED") && atoi(getenv("GRB_MI355X_EWISE_FUSED")) == 0;      // measurement / test hook
+    const char* fe = getenv("GRB_MI355X_EWISE_FUSED");
+    const bool off = fe && atoi(fe) == 0;      // measurement / test hook (read per call, like GRB_MI355X_CHAIN_JIT)
     const int wc = w->type->code;
     const bool same = xc == wc && op->ytype->code == wc && op->ztype->code == wc && u->type->code == wc && v->type->code == wc && wc < T_FC32 &&
                       (!accum || (check_obj(accum) && accum->xtype->code == wc && accum->ytype->code == wc && accum->ztype->code == wc)) &&
