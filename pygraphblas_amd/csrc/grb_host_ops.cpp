@@ -1,8 +1,8 @@
-// grb_host_ops.cpp — index-list extract / assign (host mirror, or HBM for device-resident and large containers) and kronecker (host mirror).
+// grb_host_ops.cpp — index-list extract / assign and kronecker (host mirror, or HBM for device-resident and large containers).
 //
 //   GrB_Vector_extract, GrB_Col_extract, GrB_Matrix_extract     <- Vector / Matrix slicing  (pygraphblas/vector.py:1526-1573, matrix.py:2807-2990)
 //   GrB_Vector_assign, GrB_Row_assign, GrB_Col_assign, GrB_Matrix_assign <- slice assignment (vector.py:1447-1492, matrix.py:2992-3130)
-//   GrB_Matrix_kronecker_BinaryOp                               <- Matrix.kronecker         (matrix.py:2728-2805)
+//   GrB_Matrix_kronecker_BinaryOp / _Monoid / _Semiring, GxB_kron <- Matrix.kronecker, Matrix.kronpow (matrix.py:2739-2805, 1732-1757)
 //   GxB_{Matrix,Vector}_apply_BinaryOp1st/2nd                   <- apply_first / apply_second with a Scalar (matrix.py:1999-2004, 2034-2039)
 //
 // None of these is on the hot path (mxm / mxv / vxm and the O(n) / O(nnz) operations of the BFS, PageRank and
@@ -14,10 +14,12 @@
 //
 // The three extract entry points have a second route: when the operand lives in HBM (or is large) they run the kernels of
 // grb_extract.hip and the device write-back instead — see `extract_on_device` below.  The four container forms of assign have one too
-// (grb_assign.hip, `assign_on_device`).  Kronecker has the host route only.
+// (grb_assign.hip, `assign_on_device`), and so has Kronecker (grb_kron.hip, `kron_on_device`): a product of two 8 000-entry matrices is
+// 6.4e7 entries — one streaming store pass in HBM, out of reach for the map-based host route.
 #include "grb_opcommon.hpp"
 #include "grb_extract.hpp"
 #include "grb_assign.hpp"
+#include "grb_kron.hpp"
 #include "grb_matops.hpp"
 #include <array>
 #include <map>
@@ -492,6 +494,45 @@ bool assign_line_device(GrB_Matrix C, GrB_Vector mask, GrB_BinaryOp accum, GrB_V
   region_replace(C, nullptr, DescView(nullptr), T, ccode, ri, none_i, ci, none_j);
   return true;
 }
+
+// ---- kronecker: which route -------------------------------------------------------------------------------------------------------
+// The device route (grb_kron.hip) is taken when a HIP device is present, C, both operands and the mask have an HBM layout (mat_capable), neither
+// operand is the output, a mask object accompanies a complemented mask, the product fits the 32-bit device layout (ar br and ac bc follow from C's
+// own shape; nnz(A) nnz(B) <= KRON_MAX_ENTRIES) and either C or an operand lives in HBM only (it is not downloaded for this) or the product has at
+// least KRON_DEVICE_MIN_ENTRIES entries (the crossover against this file's host route, upload included: DESIGN.md §8).  The 3 x 3 docstring
+// examples keep the host route.  GRB_MI355X_KRON=0 forces the host route, =1 the device route wherever it is legal (read per call: a test hook).
+// GRB_MI355X_KRON_TIME=1 puts HIP events around the fill kernel; GrBX_kron_fill_ms returns what they measured (tools/kron_probe.py).
+constexpr uint64_t KRON_DEVICE_MIN_ENTRIES = 1000;              // provisional: reasoned from the assign route's fixed cost, not yet measured
+thread_local float g_kron_fill_ms = 0.0f;
+int kron_env() { const char* e = getenv("GRB_MI355X_KRON"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }
+bool hbm_only(GrB_Matrix A) { return A->dev_valid && !A->host_valid; }
+uint64_t entries_of(GrB_Matrix A) { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }      // (the count of a valid host mirror, or of the device CSR: no device work)
+bool kron_on_device(GrB_Matrix C, GrB_Matrix Mask, GrB_Matrix A, GrB_Matrix B, const DescView& dv) {
+  const int env = kron_env();
+  if (env == 0 || !device_ok() || !mat_capable(C) || !mat_capable(A) || !mat_capable(B) || !mat_capable(Mask)) return false;
+  if (A == C || B == C || (!Mask && dv.mask_comp)) return false;
+  if (C->nrows > GRB_DIM_DEVICE_MAX || C->ncols > GRB_DIM_DEVICE_MAX) return false;
+  const uint64_t na = entries_of(A), nb = entries_of(B);
+  if (na > KRON_MAX_ENTRIES || nb > KRON_MAX_ENTRIES || na * nb > KRON_MAX_ENTRIES) return false;      // (each factor < 2^32: the product cannot wrap)
+  if (env == 1) return true;
+  if (hbm_only(C) || hbm_only(A) || hbm_only(B)) return true;
+  return na * nb >= KRON_DEVICE_MIN_ENTRIES;
+}
+void kron_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, const DescView& dv) {
+  if (accum) check_binop(accum, "accum");
+  mat_to_device(A); mat_to_device(B);
+  // op(A) / op(B) under GrB_DESC_T0 / T1: the cached transposes of the (small) operands, never a transposed T
+  const DevCSR& Ad = dv.tran0 ? mat_csc(A) : A->csr; const DevCSR& Bd = dv.tran1 ? mat_csc(B) : B->csr;
+  const int oc = op->xtype->code;                                       // T's type is the operator's domain, comparisons included, as on the host route
+  DevBuf acast, bcast;
+  const void* av = binop_uses_x(op->opcode) ? cast_values(oc, A->type->code, Ad.val.p, Ad.nnz, acast) : nullptr;
+  const void* bv = binop_uses_y(op->opcode) ? cast_values(oc, B->type->code, Bd.val.p, Bd.nnz, bcast) : nullptr;
+  const char* te = getenv("GRB_MI355X_KRON_TIME"); const bool timed = te && atoi(te) != 0;
+  DevCSR T;
+  kron_csr(oc, op->opcode, Ad, av, Bd, bv, T, timed ? &g_kron_fill_ms : nullptr);
+  g_last_plan = std::string("kronecker<op=") + op->name + ",transpose0=" + (dv.tran0 ? "1" : "0") + ",transpose1=" + (dv.tran1 ? "1" : "0") + ",accum=" + accum_name(accum) + "> k_kron_rowptr k_kron_fill ";
+  matrix_write_back(C, T, oc, Mask, dv, accum, false);
+}
 }  // namespace
 // the whole-container fast paths forward to eWiseAdd without the caller's descriptor: only when it asks for nothing they would
 // drop (a complemented mask without a mask object allows no writes at all; an invalid descriptor is the general path's error)
@@ -621,6 +662,7 @@ GrB_Info GrB_Matrix_kronecker_BinaryOp(GrB_Matrix C, const GrB_Matrix Mask, cons
     const DescView dv(desc);
     const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols, br = dv.tran1 ? B->ncols : B->nrows, bc = dv.tran1 ? B->nrows : B->ncols;
     if (C->nrows != ar * br || C->ncols != ac * bc || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "kronecker: dimensions do not conform");
+    if (kron_on_device(C, Mask, A, B, dv)) { kron_device(C, Mask, accum, op, A, B, dv); return; }
     Map Am = load(A, dv.tran0), Bm = load(B, dv.tran1), T, Cm = load(C, false), Mm; if (Mask) Mm = load(Mask, false);
     const int oc = op->xtype->code, zc = op->ztype->code;
     for (auto& a : Am) for (auto& b : Bm) {
@@ -633,6 +675,19 @@ GrB_Info GrB_Matrix_kronecker_BinaryOp(GrB_Matrix C, const GrB_Matrix Mask, cons
     store(C, Cm);
   });
 }
+// the C API 1.3 / SuiteSparse 5.1 spellings: a monoid stands for its operator, a semiring for its multiplier
+GrB_Info GrB_Matrix_kronecker_Monoid(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
+  if (!op) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
+  return GrB_Matrix_kronecker_BinaryOp(C, Mask, accum, op->op, A, B, desc);
+}
+GrB_Info GrB_Matrix_kronecker_Semiring(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
+  if (!op) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
+  return GrB_Matrix_kronecker_BinaryOp(C, Mask, accum, op->mul, A, B, desc);
+}
+GrB_Info GxB_kron(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
+  return GrB_Matrix_kronecker_BinaryOp(C, Mask, accum, op, A, B, desc);
+}
+GrB_Info GrBX_kron_fill_ms(float* ms) { if (!ms) return GrB_NULL_POINTER; *ms = g_kron_fill_ms; return GrB_SUCCESS; }
 
 
 // apply with the bound operand in a GxB_Scalar: forwarded to the typed entry point of the scalar's type

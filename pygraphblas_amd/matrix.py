@@ -494,6 +494,19 @@ class Matrix:
         check(lib.GrB_Matrix_kronecker_BinaryOp(out._h, mh, ah, C.c_void_p(op.get_op()), self._h, other._h, dh), out)
         return out
 
+    def kronpow(self, exponent):
+        """"Kronecker power": 0 gives the identity of the matrix's type, 1 the matrix itself, otherwise a copy is replaced by its
+        Kronecker product with itself `exponent - 1` times — the reference's loop as it stands (matrix.py:1732-1757), so the
+        dimension is nrows ** (2 ** (exponent - 1)).  Each squaring is one pass of the device kernels once the product is large."""
+        if exponent == 0:
+            return Matrix.identity(self.type, self.nrows)
+        if exponent == 1:
+            return self
+        result = self.dup()
+        for _ in range(1, exponent):
+            result = result.kronecker(result)
+        return result
+
     def get(self, i, j, default=None):
         try:
             return self[i, j]

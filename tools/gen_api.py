@@ -467,7 +467,7 @@ GrB_Info GrBX_timer_start(void);                   /* hipEventRecord on the libr
 GrB_Info GrBX_timer_stop(float *milliseconds);     /* hipEventRecord + synchronize + elapsed */
 GrB_Info GrBX_device_info(char *name, int name_len, int *compute_units, size_t *hbm_bytes);
 GrB_Info GrBX_memory_in_use(size_t *bytes);
-GrB_Info GrBX_last_kernel_plan(char *buf, int len); /* which kernels the last hot-path call launched; the device route of an index-list extract leaves "extract_matrix<cols=all|range|table|bisect,rowsort=0|1,transpose=0|1> ...", "extract_col<...>" or "extract_vector<...>", that of an index-list assign "assign_matrix<rows=..,cols=..,rowsort=0|1,transpose=0|1,accum=..> ...", "assign_row<...>", "assign_col<...>" or "assign_vector<index=..,accum=..>" */
+GrB_Info GrBX_last_kernel_plan(char *buf, int len); /* which kernels the last hot-path call launched; the device route of an index-list extract leaves "extract_matrix<cols=all|range|table|bisect,rowsort=0|1,transpose=0|1> ...", "extract_col<...>" or "extract_vector<...>", that of an index-list assign "assign_matrix<rows=..,cols=..,rowsort=0|1,transpose=0|1,accum=..> ...", "assign_row<...>", "assign_col<...>" or "assign_vector<index=..,accum=..>", that of a Kronecker product "kronecker<op=..,transpose0=0|1,transpose1=0|1,accum=..> k_kron_rowptr k_kron_fill" */
 GrB_Info GrBX_last_plan_build_ms(float *milliseconds); /* device time of the most recent SpMV plan build (kernel X), 0 if none */
 GrB_Info GrBX_lazy_stats(uint64_t *chains, uint64_t *nodes, uint64_t *fills_folded, uint64_t *reduces_fused); /* non-blocking mode: element-wise chain kernels run, operations they carried, `w(:) = s` fills folded into a product's store, reductions fused into a chain */
 GrB_Info GrBX_chain_jit_stats(uint64_t *compiled, uint64_t *launched); /* deferred element-wise chains compiled with hipRTC (grb_chain_jit.cpp): kernels compiled, launches through them */
@@ -477,8 +477,9 @@ GrB_Info GrBX_Vector_iseq(bool *equal, const GrB_Vector u, const GrB_Vector v); 
 GrB_Info GrBX_xcd_mapping(char *buf, int len);      /* how workgroups of a full-chip launch map to XCDs ("roundrobin8", or what was observed) */
 /* The exchange steps of the row-partitioned path (one process per GPU; RCCL over xGMI; grb_dist.cpp).  The reference has no
  * distributed code: these replace nothing in it, they are what BASELINE.json's north star adds (SURVEY.md section 8e). */
-/* Index-list extract / assign, kronecker and apply with a GxB_Scalar operand: the element-wise container surface, computed on the
- * host mirror like setElement (grb_host_ops.cpp) — not part of the HIP hot path. */
+/* Index-list extract / assign, kronecker and apply with a GxB_Scalar operand: the element-wise container surface (grb_host_ops.cpp).
+ * Small host-resident containers are computed on the host mirror like setElement; extract, assign and kronecker run in HBM
+ * (grb_extract.hip, grb_assign.hip, grb_kron.hip) for device-resident and large ones. */
 GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index *I, GrB_Index ni, const GrB_Descriptor desc);
 GrB_Info GrB_Col_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index *I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc);
 GrB_Info GrB_Matrix_extract(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index *I, GrB_Index ni, const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc);
@@ -487,6 +488,10 @@ GrB_Info GrB_Matrix_assign(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binary
 GrB_Info GrB_Row_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, GrB_Index i, const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc);
 GrB_Info GrB_Col_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index *I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc);
 GrB_Info GrB_Matrix_kronecker_BinaryOp(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc);
+GrB_Info GrB_Matrix_kronecker_Monoid(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc);   /* the monoid's operator */
+GrB_Info GrB_Matrix_kronecker_Semiring(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc);   /* the semiring's multiplier */
+GrB_Info GxB_kron(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc);   /* the SuiteSparse 3 spelling of the BinaryOp form */
+GrB_Info GrBX_kron_fill_ms(float *milliseconds);   /* device time of k_kron_fill in the most recent device-route Kronecker product of this thread, measured when GRB_MI355X_KRON_TIME=1 (0 otherwise) */
 GrB_Info GxB_Matrix_diag(GrB_Matrix C, const GrB_Vector v, int64_t k, const GrB_Descriptor desc);   /* Matrix.from_diag, pygraphblas/matrix.py:333-375 (host mirror) */
 GrB_Info GxB_Vector_diag(GrB_Vector v, const GrB_Matrix A, int64_t k, const GrB_Descriptor desc);   /* Matrix.vector_diag, pygraphblas/matrix.py:2225-2277 (host mirror) */
 GrB_Info GxB_Matrix_apply_BinaryOp1st(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GxB_Scalar x, const GrB_Matrix A, const GrB_Descriptor desc);
