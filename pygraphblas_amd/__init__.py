@@ -22,12 +22,15 @@ from .types import (BOOL, INT8, UINT8, INT16, UINT16, INT32, UINT32, INT64, UINT
                     Semiring, UnaryOp, promote)
 from .matrix import Matrix  # noqa: E402
 from .vector import Vector  # noqa: E402
+from . import userop  # noqa: E402
+from .userop import unary_op, binary_op  # noqa: E402
 
 GxB_INDEX_MAX = _capi.constants["GxB_INDEX_MAX"]
 device_info = _capi.device_info
 last_kernel_plan = _capi.last_kernel_plan
 
 __all__ = ["lib", "Matrix", "Vector", "types", "descriptor", "Accum", "BinaryOp", "Monoid", "Semiring", "UnaryOp", "promote",
+           "userop", "unary_op", "binary_op",
            "BOOL", "INT8", "UINT8", "INT16", "UINT16", "INT32", "UINT32", "INT64", "UINT64", "FP32", "FP64",
            "GraphBLASException", "NoValue", "UninitializedObject", "InvalidObject", "NullPointer", "InvalidValue",
            "InvalidIndex", "DomainMismatch", "DimensionMismatch", "OutputNotEmpty", "OutOfMemory", "InsufficientSpace",

@@ -21,6 +21,7 @@
 // ahead-of-time shapes (round 4's behaviour; tests/test_nonblocking_gpu.py compares them).
 #include "grb_opcommon.hpp"
 #include "grb_lazy.hpp"
+#include "grb_jit.hpp"
 #include <dlfcn.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -255,34 +256,45 @@ static void write_file_atomically(const std::string& path, const std::vector<cha
   if (!ok || rename(tmp.c_str(), path.c_str()) != 0) (void)unlink(tmp.c_str());
 }
 
-// source -> loaded function (from the disk cache, else through hipRTC); runs WITHOUT the table's lock
-static bool build_kernel(const std::string& src, hipModule_t* mod, hipFunction_t* fn, bool* from_disk) {
+// source -> loaded function (from the disk cache, else through hipRTC); runs WITHOUT the table's lock.  Shared with the other run-time compiled kernels
+// (grb_jit.hpp): `entry` names the kernel, `file_prefix` the cache file ("chain" here), `log` receives the compiler's log of a failed compilation.
+bool jit_available() { std::lock_guard<std::mutex> lk(g_mu); return g_rtc.bind(); }      // (the table's lock: the chain path binds under it too)
+bool jit_build_kernel(const std::string& src, const char* entry, const char* file_prefix, hipModule_t* mod, hipFunction_t* fn, bool* from_disk, std::string* log) {
   *from_disk = false; *mod = nullptr; *fn = nullptr;
   const std::string& arch = device_arch();
   int vmaj = 0, vmin = 0; if (g_rtc.Version) (void)g_rtc.Version(&vmaj, &vmin);
   const std::string dir = cache_dir();
-  char name[64]; snprintf(name, sizeof(name), "/chain-%016llx.co", (unsigned long long)fnv1a(src + "|" + arch + "|" + std::to_string(vmaj) + "." + std::to_string(vmin) + "|O3,fp-contract=off"));
+  char name[96]; snprintf(name, sizeof(name), "/%s-%016llx.co", file_prefix, (unsigned long long)fnv1a(src + "|" + arch + "|" + std::to_string(vmaj) + "." + std::to_string(vmin) + "|O3,fp-contract=off"));
   const std::string path = dir.empty() ? std::string() : dir + name;
   std::vector<char> code;
   if (!path.empty() && read_file(path, code)) {
-    if (hipModuleLoadData(mod, code.data()) == hipSuccess && hipModuleGetFunction(fn, *mod, "grb_chain") == hipSuccess) { *from_disk = true; return true; }
+    if (hipModuleLoadData(mod, code.data()) == hipSuccess && hipModuleGetFunction(fn, *mod, entry) == hipSuccess) { *from_disk = true; return true; }
     (void)hipGetLastError(); if (*mod) { (void)hipModuleUnload(*mod); *mod = nullptr; } *fn = nullptr;      // (a stale or truncated file: compile and overwrite it)
     code.clear();
   }
   hiprtcProgram prog = nullptr;
   const std::string archopt = "--offload-arch=" + arch;
+  const std::string file = std::string("grb_") + file_prefix + ".hip";
   const char* opts[] = {archopt.c_str(), "-O3", "-ffp-contract=off"};        // (no fused multiply-adds the ahead-of-time kernels would not form either: their steps are separate operator calls)
-  bool ok = g_rtc.CreateProgram(&prog, src.c_str(), "grb_chain.hip", 0, nullptr, nullptr) == 0 && g_rtc.CompileProgram(prog, 3, opts) == 0;
+  bool ok = g_rtc.CreateProgram(&prog, src.c_str(), file.c_str(), 0, nullptr, nullptr) == 0 && g_rtc.CompileProgram(prog, 3, opts) == 0;
   if (ok) { size_t sz = 0; ok = g_rtc.GetCodeSize(prog, &sz) == 0 && sz > 0; if (ok) { code.resize(sz); ok = g_rtc.GetCode(prog, code.data()) == 0; } }
-  else if (prog && getenv("GRB_MI355X_VERBOSE")) { size_t ls = 0; if (g_rtc.GetProgramLogSize(prog, &ls) == 0 && ls > 1) { std::vector<char> log(ls); g_rtc.GetProgramLog(prog, log.data()); fprintf(stderr, "grb chain jit: %s\n%s\n", log.data(), src.c_str()); } }
+  else if (prog && (log || getenv("GRB_MI355X_VERBOSE"))) {
+    size_t ls = 0;
+    if (g_rtc.GetProgramLogSize(prog, &ls) == 0 && ls > 1) {
+      std::vector<char> text(ls + 1, 0); g_rtc.GetProgramLog(prog, text.data());
+      if (log) *log = text.data();
+      if (getenv("GRB_MI355X_VERBOSE")) fprintf(stderr, "grb %s jit: %s\n%s\n", file_prefix, text.data(), src.c_str());
+    }
+  }
   if (prog) g_rtc.DestroyProgram(&prog);
   if (ok) {
-    ok = hipModuleLoadData(mod, code.data()) == hipSuccess && hipModuleGetFunction(fn, *mod, "grb_chain") == hipSuccess;
+    ok = hipModuleLoadData(mod, code.data()) == hipSuccess && hipModuleGetFunction(fn, *mod, entry) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); if (*mod) { (void)hipModuleUnload(*mod); *mod = nullptr; } *fn = nullptr; }      // (the module was leaked when only the lookup failed)
   }
   if (ok && !path.empty()) write_file_atomically(path, code);
   return ok;
 }
+static bool build_kernel(const std::string& src, hipModule_t* mod, hipFunction_t* fn, bool* from_disk) { return jit_build_kernel(src, "grb_chain", "chain", mod, fn, from_disk, nullptr); }
 
 // Launches the chain through its compiled kernel when there is one (or when this call is the one that compiles it); false: the caller runs the
 // interpreter.  `grid` workgroups of 256 threads; `partial` receives the per-workgroup partials of a reduction.  `tcode`: the chain's value type.

@@ -11,6 +11,7 @@
 #include "grb_api.hpp"
 #include "grb_device.hpp"
 #include "grb_matops.hpp"
+#include "grb_userop.hpp"
 #include <algorithm>
 #include <numeric>
 #include <string.h>
@@ -300,6 +301,7 @@ static void build_tuples(GrB_Type type, const GrB_Index* I, const GrB_Index* J, 
                          GrB_Index nrows, GrB_Index ncols, GrB_BinaryOp dup, std::vector<GrB_Index>& hi,
                          std::vector<GrB_Index>* hj, std::vector<uint8_t>& hx) {
   const size_t ts = type->size; const size_t xs = type_size(xcode);
+  if (dup && check_obj(dup) && is_user(dup)) userop_refuse(dup->name, "the dup operator of build");
   for (GrB_Index k = 0; k < n; k++) {
     if (I[k] >= nrows || (J && J[k] >= ncols)) fail(GrB_INDEX_OUT_OF_BOUNDS, "build: index out of bounds");
   }

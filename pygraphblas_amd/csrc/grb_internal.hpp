@@ -41,8 +41,9 @@ enum { GxB_DEFAULT = 0, GrB_REPLACE = 1, GrB_COMP = 2, GrB_TRAN = 3, GrB_STRUCTU
 #define GXB_INDEX_MAX ((GrB_Index)1 << 60)
 
 struct GrB_Type_opaque { uint64_t magic; int code; size_t size; char name[32]; };
-struct GrB_UnaryOp_opaque { uint64_t magic; int opcode; GrB_Type_opaque* xtype; GrB_Type_opaque* ztype; char name[40]; void* fn; };
-struct GrB_BinaryOp_opaque { uint64_t magic; int opcode; GrB_Type_opaque* xtype; GrB_Type_opaque* ytype; GrB_Type_opaque* ztype; char name[40]; void* fn; };
+// `defn`: a user-defined operator (GxB_UnaryOp_new / GxB_BinaryOp_new, grb_userop.cpp; opcode >= U_USER / B_USER) owns a copy of its C definition; nullptr for built-ins
+struct GrB_UnaryOp_opaque { uint64_t magic; int opcode; GrB_Type_opaque* xtype; GrB_Type_opaque* ztype; char name[40]; void* fn; char* defn; };
+struct GrB_BinaryOp_opaque { uint64_t magic; int opcode; GrB_Type_opaque* xtype; GrB_Type_opaque* ytype; GrB_Type_opaque* ztype; char name[40]; void* fn; char* defn; };
 struct GrB_Monoid_opaque { uint64_t magic; GrB_BinaryOp_opaque* op; uint8_t identity[16]; bool has_terminal; uint8_t terminal[16]; char name[48]; bool builtin; };
 struct GrB_Semiring_opaque { uint64_t magic; GrB_Monoid_opaque* add; GrB_BinaryOp_opaque* mul; char name[56]; bool builtin; };
 struct GrB_Descriptor_opaque { uint64_t magic; int outp, mask, inp0, inp1, axb, nthreads, sort; double chunk; bool builtin; char name[16]; };

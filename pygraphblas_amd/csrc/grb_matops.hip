@@ -147,31 +147,70 @@ template <class T, bool MATH> __global__ void k_merge_fill(uint64_t n, const uns
     ocol[w] = (uint32_t)k; oval[w] = v;
   }
 }
-void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int op, bool is_union, DevCSR& out) {
+// the aligned form of the fill: no operator, both operands' values at the output's positions and a flag "both present" (csr_ewise_aligned)
+template <class W> __global__ void k_merge_align(uint64_t n, const unsigned long long* __restrict__ key, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ e,
+                                                 const uint32_t* __restrict__ pos, const W* __restrict__ aval, const W* __restrict__ bval, uint32_t* __restrict__ ocol, W* __restrict__ xval,
+                                                 W* __restrict__ yval, uint8_t* __restrict__ bothf) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) if (e[i]) {
+    const uint32_t w = pos[i]; const unsigned long long k = key[i]; const uint32_t x = idx[i];
+    const bool both = i + 1 < n && key[i + 1] == k;
+    W xv, yv;
+    if (both) { const uint32_t x2 = idx[i + 1]; const uint32_t xa = (x & 0x80000000u) ? x2 : x, xb = (x & 0x80000000u) ? x : x2;
+                xv = aval[xa & 0x7FFFFFFFu]; yv = bval[xb & 0x7FFFFFFFu]; }
+    else xv = yv = (x & 0x80000000u) ? bval[x & 0x7FFFFFFFu] : aval[x];
+    ocol[w] = (uint32_t)k; xval[w] = xv; yval[w] = yv; bothf[w] = both ? 1 : 0;
+  }
+}
+// the merge of the two patterns up to the output's row pointers and entry count; km / im / e / pos describe the merged sequence for the fill kernels
+struct EwiseMerge { DevBuf km, im, e, pos; uint64_t n = 0; };
+static bool ewise_merge(const DevCSR& A, const DevCSR& B, bool is_union, DevCSR& out, EwiseMerge& mg) {
   const uint32_t nrows = A.nrows; const uint64_t na = A.nnz, nb = B.nnz, n = na + nb;
   if (na >= 0x7FFFFFF0ull || nb >= 0x7FFFFFF0ull) fail(GrB_INSUFFICIENT_SPACE, "eWise: more than 2^31 entries in one operand");
   out.clear(); out.nrows = nrows; out.ncols = A.ncols;
   out.rowptr.alloc(((size_t)nrows + 1) * 4);
-  if (!n) { GRB_HIP(hipMemsetAsync(out.rowptr.p, 0, ((size_t)nrows + 1) * 4, stream())); out.nnz = 0; out.col.alloc(8); out.val.alloc(8); out.valid = true; return; }
-  DevBuf ka(na * 8 + 8), kb(nb * 8 + 8), ia(na * 4 + 4), ib(nb * 4 + 4), km(n * 8 + 8), im(n * 4 + 4), e((n + 1) * 4 + 4), pos((n + 1) * 4 + 4);
+  mg.n = n;
+  if (!n) { GRB_HIP(hipMemsetAsync(out.rowptr.p, 0, ((size_t)nrows + 1) * 4, stream())); out.nnz = 0; out.col.alloc(8); out.val.alloc(8); out.valid = true; return false; }
+  DevBuf ka(na * 8 + 8), kb(nb * 8 + 8), ia(na * 4 + 4), ib(nb * 4 + 4);
+  mg.km.alloc(n * 8 + 8); mg.im.alloc(n * 4 + 4); mg.e.alloc((n + 1) * 4 + 4); mg.pos.alloc((n + 1) * 4 + 4);
   { DevBuf rowidx((na > nb ? na : nb) * 4 + 4);
     if (na) { csr_row_indices(A, rowidx.as<uint32_t>()); hipLaunchKernelGGL(k_entry_keys, dim3(grid_n(na)), dim3(256), 0, stream(), na, rowidx.as<uint32_t>(), A.col.as<uint32_t>(), 0u, (unsigned long long*)ka.p, ia.as<uint32_t>()); }
     if (nb) { csr_row_indices(B, rowidx.as<uint32_t>()); hipLaunchKernelGGL(k_entry_keys, dim3(grid_n(nb)), dim3(256), 0, stream(), nb, rowidx.as<uint32_t>(), B.col.as<uint32_t>(), 0x80000000u, (unsigned long long*)kb.p, ib.as<uint32_t>()); }
     GRB_HIP(hipStreamSynchronize(stream())); }
-  merge_pairs_u64((const uint64_t*)ka.p, (const uint64_t*)kb.p, (uint64_t*)km.p, ia.as<uint32_t>(), ib.as<uint32_t>(), im.as<uint32_t>(), na, nb);
-  hipLaunchKernelGGL(k_merge_emit, dim3(grid_n(n + 1)), dim3(256), 0, stream(), n, (const unsigned long long*)km.p, is_union, e.as<uint32_t>());
-  exclusive_scan_u32(e.as<uint32_t>(), pos.as<uint32_t>(), n + 1);
-  hipLaunchKernelGGL(k_merge_rowptr, dim3(grid_n((uint64_t)nrows + 1)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), B.rowptr.as<uint32_t>(), nrows, pos.as<uint32_t>(), out.rowptr.as<uint32_t>());
+  merge_pairs_u64((const uint64_t*)ka.p, (const uint64_t*)kb.p, (uint64_t*)mg.km.p, ia.as<uint32_t>(), ib.as<uint32_t>(), mg.im.as<uint32_t>(), na, nb);
+  hipLaunchKernelGGL(k_merge_emit, dim3(grid_n(n + 1)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, is_union, mg.e.as<uint32_t>());
+  exclusive_scan_u32(mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), n + 1);
+  hipLaunchKernelGGL(k_merge_rowptr, dim3(grid_n((uint64_t)nrows + 1)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), B.rowptr.as<uint32_t>(), nrows, mg.pos.as<uint32_t>(), out.rowptr.as<uint32_t>());
   uint32_t total = 0;
-  GRB_HIP(hipMemcpyAsync(&total, pos.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+  GRB_HIP(hipMemcpyAsync(&total, mg.pos.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
   out.nnz = total;
+  return true;
+}
+void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int op, bool is_union, DevCSR& out) {
+  EwiseMerge mg;
+  if (!ewise_merge(A, B, is_union, out, mg)) return;
+  const uint64_t n = mg.n, total = out.nnz;
   dispatch_type(code, [&]<class T>() {
     out.col.alloc((size_t)total * 4 + 4); out.val.alloc((size_t)total * sizeof(T) + 8);
-#define GRB_EW_FILL(MATH) hipLaunchKernelGGL((k_merge_fill<T, MATH>), dim3(grid_n(n)), dim3(256), 0, stream(), n, (const unsigned long long*)km.p, im.as<uint32_t>(), e.as<uint32_t>(), pos.as<uint32_t>(), \
+#define GRB_EW_FILL(MATH) hipLaunchKernelGGL((k_merge_fill<T, MATH>), dim3(grid_n(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
                                              (const T*)aval, (const T*)bval, op, out.col.as<uint32_t>(), out.val.as<T>())
     if (binop_needs_math(op)) GRB_EW_FILL(true); else GRB_EW_FILL(false);
 #undef GRB_EW_FILL
   });
+  GRB_HIP(hipGetLastError());
+  GRB_HIP(hipStreamSynchronize(stream()));       // the temporaries return to the pool
+  out.valid = true;
+}
+void csr_ewise_aligned(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, bool is_union, DevCSR& out, DevBuf& xval, DevBuf& yval, DevBuf& both) {
+  EwiseMerge mg;
+  const size_t ts = (size_t)type_size(code);
+  if (!ewise_merge(A, B, is_union, out, mg)) { xval.alloc(16); yval.alloc(16); both.alloc(16); return; }
+  const uint64_t n = mg.n, total = out.nnz;
+  out.col.alloc((size_t)total * 4 + 4); out.val.alloc((size_t)total * ts + 16);
+  xval.alloc((size_t)total * ts + 16); yval.alloc((size_t)total * ts + 16); both.alloc((size_t)total + 16);
+#define GRB_EW_ALIGN(W) hipLaunchKernelGGL((k_merge_align<W>), dim3(grid_n(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
+                                           (const W*)aval, (const W*)bval, out.col.as<uint32_t>(), xval.as<W>(), yval.as<W>(), both.as<uint8_t>())
+  switch (ts) { case 1: GRB_EW_ALIGN(uint8_t); break; case 2: GRB_EW_ALIGN(uint16_t); break; case 4: GRB_EW_ALIGN(uint32_t); break; default: GRB_EW_ALIGN(uint64_t); break; }
+#undef GRB_EW_ALIGN
   GRB_HIP(hipGetLastError());
   GRB_HIP(hipStreamSynchronize(stream()));       // the temporaries return to the pool
   out.valid = true;

@@ -9,6 +9,9 @@ namespace grb {
 void csr_writeback(int code, uint32_t nrows, const DevCSR& C, const DevCSR& Tm, const DevCSR* M, int mcode, bool mstruct, bool mcomp,
                    bool replace, int accum, DevCSR& out);
 void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int op, bool is_union, DevCSR& out);
+// the pattern of the union / intersection alone, with both operands' values moved to the output's positions (grb_userop.cpp evaluates a user-defined operator over
+// them): xval[w] / yval[w] hold A's / B's value of output entry w; where only one operand has the entry (union) both hold that value and both[w] = 0.
+void csr_ewise_aligned(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, bool is_union, DevCSR& out, DevBuf& xval, DevBuf& yval, DevBuf& both);
 void csr_compact(const DevCSR& A, const void* aval, size_t ts, const uint8_t* keep, DevCSR& out);
 void select_positional_flags(const DevCSR& A, int sel, int64_t k, uint8_t* keep);
 void mask_flags(const DevCSR& Tm, const DevCSR& M, int mcode, bool mstruct, bool mcomp, uint8_t* keep);

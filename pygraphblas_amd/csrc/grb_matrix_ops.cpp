@@ -154,8 +154,37 @@ void do_transpose(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Matrix A, 
   matrix_write_back(C, T, A->type->code, M, dv, accum, false);
 }
 
+// a user-defined operator (grb_userop.cpp) has no HBM-less route: hypersparse and complex containers are refused, naming the operator
+void user_needs_layout(const char* opname, bool hyper, bool cplx) {
+  if (hyper) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": hypersparse containers (a dimension beyond the device layout) are out of its scope");
+  if (cplx) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": complex containers are out of its scope");
+}
+
+// eWiseAdd / eWiseMult with a user-defined operator: the merge of the two patterns moves both operands' values to the output's positions
+// (csr_ewise_aligned), the operator's compiled kernel streams over them, the write-back is the one of every other operation
+void do_ewise_user(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, bool is_union) {
+  user_needs_layout(op->name, is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B),
+                    C->type->code >= T_FC32 || A->type->code >= T_FC32 || B->type->code >= T_FC32 || (M && M->type->code >= T_FC32));
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc);
+  const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
+  const uint64_t br = dv.tran1 ? B->ncols : B->nrows, bc = dv.tran1 ? B->nrows : B->ncols;
+  if (ar != br || ac != bc || C->nrows != ar || C->ncols != ac || (M && (M->nrows != ar || M->ncols != ac))) fail(GrB_DIMENSION_MISMATCH, "eWise: dimensions do not conform");
+  if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
+  const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);
+  const int xc = op->xtype->code;
+  DevBuf acast, bcast, xv, yv, both;
+  const void* av = cast_values(xc, A->type->code, Ad.val.p, Ad.nnz, acast);
+  const void* bv = cast_values(xc, B->type->code, Bd.val.p, Bd.nnz, bcast);
+  DevCSR T;
+  csr_ewise_aligned(xc, Ad, av, Bd, bv, is_union, T, xv, yv, both);
+  userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, T.nnz, xv.p, nullptr, yv.p, nullptr, is_union ? both.as<uint8_t>() : nullptr, nullptr, T.val.p, nullptr);
+  matrix_write_back(C, T, xc, M, dv, accum, false);
+}
+
 void do_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, bool is_union) {
   need_device(); check_mat(A, "eWise"); check_mat(B, "eWise"); if (M) check_mat(M, "eWise");
+  if (check_obj(op) && is_user(op)) { do_ewise_user(C, M, accum, op, A, B, desc, is_union); return; }
   check_binop(op, "eWise");
   if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mat_ewise(C, M, accum, op, A, B, desc, is_union); return; }
   const DescView dv(desc);
@@ -211,6 +240,27 @@ void do_apply(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, int mode, int opco
   DevBuf ac; const void* av = cast_values(xcode, A->type->code, S.val.p, S.nnz, ac);
   uint8_t s[16] = {0}; if (scalar) cast_scalar(xcode, s, scode, scalar);
   vec_apply(xcode, S.nnz, av, nullptr, mode, opcode, s, T.val.p, nullptr);
+  T.valid = true;
+  matrix_write_back(C, T, xcode, M, dv, accum, false);
+}
+
+// apply with a user-defined operator: kind UK_APPLY (unary) or UK_BIND1ST / UK_BIND2ND (binary with a bound scalar)
+void do_apply_user(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, int kind, const char* name, const char* defn, int xcode, const void* scalar, int scode, GrB_Matrix A, GrB_Descriptor desc) {
+  need_device(); check_mat(A, "apply"); if (M) check_mat(M, "apply");
+  user_needs_layout(name, is_hyper(C) || is_hyper(M) || is_hyper(A), C->type->code >= T_FC32 || A->type->code >= T_FC32 || (M && M->type->code >= T_FC32) || scode >= T_FC32);
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc);
+  const uint64_t r = dv.tran0 ? A->ncols : A->nrows, c = dv.tran0 ? A->nrows : A->ncols;
+  if (C->nrows != r || C->ncols != c || (M && (M->nrows != r || M->ncols != c))) fail(GrB_DIMENSION_MISMATCH, "apply: dimensions do not conform");
+  if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
+  const DevCSR& S = operand(A, dv.tran0);
+  DevCSR T; T.nrows = S.nrows; T.ncols = S.ncols; T.nnz = S.nnz;
+  T.rowptr.alloc(((size_t)S.nrows + 1) * 4); T.col.alloc(S.nnz * 4 + 4); T.val.alloc(S.nnz * type_size(xcode) + 16);
+  GRB_HIP(hipMemcpyAsync(T.rowptr.p, S.rowptr.p, ((size_t)S.nrows + 1) * 4, hipMemcpyDeviceToDevice, stream()));
+  if (S.nnz) GRB_HIP(hipMemcpyAsync(T.col.p, S.col.p, S.nnz * 4, hipMemcpyDeviceToDevice, stream()));
+  DevBuf ac; const void* av = cast_values(xcode, A->type->code, S.val.p, S.nnz, ac);
+  uint8_t s[16] = {0}; if (scalar) cast_scalar(xcode, s, scode, scalar);
+  userop_run(kind, name, defn, xcode, S.nnz, av, nullptr, nullptr, nullptr, nullptr, s, T.val.p, nullptr);
   T.valid = true;
   matrix_write_back(C, T, xcode, M, dv, accum, false);
 }
@@ -348,7 +398,8 @@ GrB_Info GrB_Matrix_eWiseMult_Semiring(GrB_Matrix C, const GrB_Matrix M, const G
   MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->mul, A, B, desc, false); }); }
 GrB_Info GrB_Matrix_apply(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_UnaryOp op, const GrB_Matrix A, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
-  return guarded(C, [&] { if (op->opcode >= U_USER) not_implemented("user-defined unary operator"); do_apply(C, M, accum, 0, op->opcode, op->xtype->code, nullptr, 0, A, desc); });
+  return guarded(C, [&] { if (is_user(op)) { do_apply_user(C, M, accum, UK_APPLY, op->name, op->defn, op->xtype->code, nullptr, 0, A, desc); return; }
+                          do_apply(C, M, accum, 0, op->opcode, op->xtype->code, nullptr, 0, A, desc); });
 }
 GrB_Info GxB_Matrix_select(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GxB_SelectOp op, const GrB_Matrix A, const GxB_Scalar thunk, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { do_select(C, M, accum, op, A, thunk, desc); });
@@ -362,9 +413,11 @@ GrB_Info GrB_Matrix_reduce_Monoid(GrB_Vector w, const GrB_Vector mask, const GrB
   GrB_Info GrB_Matrix_assign_##SUF(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, CT x, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, const GrB_Descriptor desc) { \
     MAT_GUARD(C); return guarded(C, [&] { do_assign_scalar(C, M, accum, &x, CODE, I, ni, J, nj, desc); }); } \
   GrB_Info GxB_Matrix_apply_BinaryOp1st_##SUF(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_BinaryOp op, CT x, const GrB_Matrix A, const GrB_Descriptor desc) { \
-    MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { check_binop(op, "apply"); do_apply(C, M, accum, 1, op->opcode, op->xtype->code, &x, CODE, A, desc); }); } \
+    MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { if (check_obj(op) && is_user(op)) { do_apply_user(C, M, accum, UK_BIND1ST, op->name, op->defn, op->xtype->code, &x, CODE, A, desc); return; } \
+                                                                            check_binop(op, "apply"); do_apply(C, M, accum, 1, op->opcode, op->xtype->code, &x, CODE, A, desc); }); } \
   GrB_Info GxB_Matrix_apply_BinaryOp2nd_##SUF(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, CT y, const GrB_Descriptor desc) { \
-    MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { check_binop(op, "apply"); do_apply(C, M, accum, 2, op->opcode, op->xtype->code, &y, CODE, A, desc); }); }
+    MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { if (check_obj(op) && is_user(op)) { do_apply_user(C, M, accum, UK_BIND2ND, op->name, op->defn, op->xtype->code, &y, CODE, A, desc); return; } \
+                                                                            check_binop(op, "apply"); do_apply(C, M, accum, 2, op->opcode, op->xtype->code, &y, CODE, A, desc); }); }
 GRB_TYPED_MATOPS(BOOL, bool, T_BOOL) GRB_TYPED_MATOPS(INT8, int8_t, T_INT8) GRB_TYPED_MATOPS(UINT8, uint8_t, T_UINT8)
 GRB_TYPED_MATOPS(INT16, int16_t, T_INT16) GRB_TYPED_MATOPS(UINT16, uint16_t, T_UINT16) GRB_TYPED_MATOPS(INT32, int32_t, T_INT32)
 GRB_TYPED_MATOPS(UINT32, uint32_t, T_UINT32) GRB_TYPED_MATOPS(INT64, int64_t, T_INT64) GRB_TYPED_MATOPS(UINT64, uint64_t, T_UINT64)

@@ -5,6 +5,7 @@
 #include "grb_api.hpp"
 #include "grb_device.hpp"
 #include "grb_semiring.hpp"
+#include "grb_userop.hpp"
 #include <vector>
 
 namespace grb {
@@ -12,8 +13,10 @@ namespace grb {
 inline void not_implemented(const std::string& what) { fail(GrB_INVALID_VALUE, "not implemented in the MI355X backend: " + what); }
 
 // built-in, same-type binary operator (x, y, z all one real type) or a comparison whose inputs share a type
+// (a user-defined operator runs in apply / eWiseAdd / eWiseMult only — grb_userop.cpp; those entry points look for it before they come here)
 inline void check_binop(GrB_BinaryOp op, const char* what) {
   if (!check_obj(op)) fail(GrB_UNINITIALIZED_OBJECT, std::string(what) + " operator is not initialised");
+  if (is_user(op)) userop_refuse(op->name, what);
   if (op->opcode >= B_FIRSTI) not_implemented(std::string("positional / user-defined operator ") + op->name);
   if (op->xtype != op->ytype) not_implemented(std::string("mixed-type operator ") + op->name);
 }

@@ -5,6 +5,7 @@
 #include "grb_internal.hpp"
 #include "grb_api.hpp"
 #include "grb_lazy.hpp"
+#include "grb_userop.hpp"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -233,12 +234,12 @@ static void print_value(FILE* f, int code, const void* p) {
 static FILE* outf(FILE* f) { return f ? f : stdout; }
 GrB_Info GxB_BinaryOp_fprint(GrB_BinaryOp op, const char* name, int pr, FILE* f) {
   if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; if (pr <= 0) return GrB_SUCCESS;
-  fprintf(outf(f), "\n    GraphBLAS BinaryOp: %s (built-in) z=%s(x,y)  x:%s y:%s z:%s\n", name ? name : "", op->name,
+  fprintf(outf(f), is_user(op) ? "\n    GraphBLAS BinaryOp: %s (user-defined) z=%s(x,y)  x:%s y:%s z:%s\n" : "\n    GraphBLAS BinaryOp: %s (built-in) z=%s(x,y)  x:%s y:%s z:%s\n", name ? name : "", op->name,
           op->xtype->name, op->ytype->name, op->ztype->name); return GrB_SUCCESS;
 }
 GrB_Info GxB_UnaryOp_fprint(GrB_UnaryOp op, const char* name, int pr, FILE* f) {
   if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; if (pr <= 0) return GrB_SUCCESS;
-  fprintf(outf(f), "\n    GraphBLAS UnaryOp: %s (built-in) z=%s(x)  x:%s z:%s\n", name ? name : "", op->name,
+  fprintf(outf(f), is_user(op) ? "\n    GraphBLAS UnaryOp: %s (user-defined) z=%s(x)  x:%s z:%s\n" : "\n    GraphBLAS UnaryOp: %s (built-in) z=%s(x)  x:%s z:%s\n", name ? name : "", op->name,
           op->xtype->name, op->ztype->name); return GrB_SUCCESS;
 }
 GrB_Info GxB_Monoid_fprint(GrB_Monoid m, const char* name, int pr, FILE* f) {
@@ -316,6 +317,7 @@ GrB_Info GrB_Descriptor_free(GrB_Descriptor* d) {
 // ---- algebra objects made of built-ins --------------------------------------------------------------
 GrB_Info GrB_Semiring_new(GrB_Semiring* s, GrB_Monoid add, GrB_BinaryOp mul) {
   if (!s) return GrB_NULL_POINTER; if (!check_obj(add) || !check_obj(mul)) return GrB_UNINITIALIZED_OBJECT;
+  if (is_user(mul)) { g_last_error = std::string("GrB_Semiring_new: user-defined operator ") + mul->name + " cannot be a semiring's multiplier (it runs in apply and eWise only)"; return GrB_DOMAIN_MISMATCH; }
   if (mul->ztype != add->op->ztype) return GrB_DOMAIN_MISMATCH;
   auto* r = new GrB_Semiring_opaque{GRB_MAGIC, add, mul, "", false};
   snprintf(r->name, sizeof r->name, "user_%s_%s", add->op->name, mul->name); *s = r; return GrB_SUCCESS;
@@ -325,6 +327,7 @@ GrB_Info GrB_Monoid_free(GrB_Monoid* m) { if (m && *m && check_obj(*m) && !(*m)-
 
 static GrB_Info monoid_new(GrB_Monoid* m, GrB_BinaryOp op, int code, const void* identity) {
   if (!m) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
+  if (is_user(op)) { g_last_error = std::string("GrB_Monoid_new: user-defined operator ") + op->name + " cannot be a monoid's operator (it runs in apply and eWise only)"; return GrB_DOMAIN_MISMATCH; }
   if (op->xtype != op->ztype || op->ytype != op->ztype) return GrB_DOMAIN_MISMATCH;
   auto* r = new GrB_Monoid_opaque{GRB_MAGIC, op, {0}, false, {0}, "", false};
   cast_scalar(op->ztype->code, r->identity, code, identity);

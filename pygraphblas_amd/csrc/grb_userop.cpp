@@ -1,0 +1,227 @@
+// grb_userop.cpp — user-defined unary and binary operators, handed over as C source and compiled for the device.
+//
+//   GxB_UnaryOp_new  (&op, fn, ztype, xtype,        name, defn)      defn: "void NAME (T *z, const T *x) { ... }"
+//   GxB_BinaryOp_new (&op, fn, ztype, xtype, ytype, name, defn)      defn: "void NAME (T *z, const T *x, const T *y) { ... }"
+// are SuiteSparse 7's forms: `defn` is the C definition of the function `name` (helper functions may precede it in the same string), T the C type of the
+// GraphBLAS type, `fn` a host function pointer that a device cannot call — it is kept and never used.  All of an operator's types are ONE of the 11 real
+// built-in types (what the reference's binary_op(arg_type) / unary_op(arg_type) decorators offer, pygraphblas/binaryop.py:137, unaryop.py:101).
+//
+// The object carries a fresh opcode beyond the built-in ones (>= U_USER / B_USER, so every switch over built-in opcodes sees a value it does not
+// know and the drivers refuse it before they get there: check_binop, grb_opcommon.hpp), its name and a copy of `defn`.  Nothing here needs a device.
+//
+// Running one (GrB_apply, GxB_apply_BinaryOp1st / 2nd, eWiseAdd, eWiseMult — the drivers in grb_matrix_ops.cpp / grb_vector_ops.cpp) goes through
+// userop_run: the definition is embedded in the text of ONE streaming kernel per (operator, kind, type) — every function of the definition made a device
+// function by `#pragma clang force_cuda_host_device`, the kind (apply | bind1st | bind2nd | eadd | emult) a constant of the text — compiled with hipRTC
+// through the chain compiler's build_kernel and its code-object cache on disk (grb_jit.hpp: source + architecture + hipRTC version + options; a second
+// process compiles nothing), at first use and outside the table's lock.  The kernel is entry-parallel: a lane owns four consecutive positions of the value
+// arrays, loaded and stored as one 16-byte pack (4-byte types; two for 8-byte ones), presence bytes as one 4-byte word.  Entries are computed by the
+// user's code only; where eWiseAdd finds an entry in one operand alone, the value is copied and the operator is not called.
+// A definition that does not compile, or a machine without hipRTC: the operation fails with an error code and the operator's name and the compiler's
+// log in the object's error string — there is no interpreter and no host route behind it.
+#include "grb_api.hpp"
+#include "grb_device.hpp"
+#include "grb_jit.hpp"
+#include "grb_userop.hpp"
+#include <atomic>
+#include <condition_variable>
+#include <map>
+#include <mutex>
+#include <sstream>
+
+namespace grb {
+namespace {
+
+std::atomic<int> g_next_unop{U_NOPS}, g_next_binop{B_NOPS};
+std::atomic<uint64_t> g_stat_compiled{0}, g_stat_from_disk{0}, g_stat_launched{0};
+
+const char* c_type(int code) {
+  switch (code) {
+    case T_BOOL: return "bool"; case T_INT8: return "signed char"; case T_UINT8: return "unsigned char"; case T_INT16: return "short";
+    case T_UINT16: return "unsigned short"; case T_INT32: return "int"; case T_UINT32: return "unsigned int"; case T_INT64: return "long long";
+    case T_UINT64: return "unsigned long long"; case T_FP32: return "float"; case T_FP64: return "double"; default: return nullptr;
+  }
+}
+const char* kind_name(int kind) {
+  switch (kind) { case UK_APPLY: return "apply"; case UK_BIND1ST: return "bind1st"; case UK_BIND2ND: return "bind2nd"; case UK_EADD: return "eadd"; default: return "emult"; }
+}
+
+// what the definition may assume, as <stdint.h>, <stdbool.h> and <math.h> would give it (hipRTC has no system headers; its built-in ones declare the math functions)
+const char* PRELUDE =
+  "typedef signed char grb_i8; typedef unsigned char grb_u8; typedef short grb_i16; typedef unsigned short grb_u16;\n"
+  "typedef int grb_i32; typedef unsigned int grb_u32; typedef long long grb_i64; typedef unsigned long long grb_u64;\n"
+  "#define int8_t grb_i8\n#define uint8_t grb_u8\n#define int16_t grb_i16\n#define uint16_t grb_u16\n#define int32_t grb_i32\n#define uint32_t grb_u32\n"
+  "#define int64_t grb_i64\n#define uint64_t grb_u64\n"
+  "#ifndef INFINITY\n#define INFINITY (__builtin_huge_val())\n#endif\n#ifndef NAN\n#define NAN (__builtin_nan(\"\"))\n#endif\n";
+
+// the kernel around the definition.  One text per (definition, name, kind, type): all of them are part of the cache key because they are part of the text.
+std::string generate(int kind, const char* name, const char* defn, int tcode) {
+  const int ts = type_size(tcode);
+  const bool unary = kind == UK_APPLY;
+  std::ostringstream o;
+  o << PRELUDE << "#pragma clang force_cuda_host_device begin\n" << defn << "\n#pragma clang force_cuda_host_device end\n"
+    << "typedef " << c_type(tcode) << " T;\n"
+    << "struct __attribute__((aligned(" << (4 * ts > 16 ? 16 : 4 * ts) << "))) P4 { T v[4]; }; struct __attribute__((aligned(4))) B4 { unsigned char v[4]; };\n";
+  if (unary) o << "__device__ __forceinline__ T grb_f(T a, T b) { T z; " << name << "(&z, &a); return z; }\n";
+  else o << "__device__ __forceinline__ T grb_f(T a, T b) { T z; " << name << "(&z, &a, &b); return z; }\n";
+  // x / y: operand values; px / py: presence bytes (0 = all present); both: eadd over aligned values; s: the bound scalar; z / q: result values / presence
+  o << "extern \"C\" __global__ void __launch_bounds__(256) grb_userop(const T* x, const unsigned char* px, const T* y, const unsigned char* py, const unsigned char* both,\n"
+       "    T s, T* z, unsigned char* q, unsigned long long n, int packed) {\n"
+       "  const unsigned long long stride = (unsigned long long)gridDim.x * 1024ull;\n"
+       "  for (unsigned long long base = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) * 4ull; base < n; base += stride) {\n"
+       "    const int nv = n - base >= 4ull ? 4 : (int)(n - base);\n"
+       "    T a[4], b[4], r[4]; bool ap[4], bp[4], bo[4], rp[4];\n"
+       "    if (nv == 4 && packed) {\n"
+       "      const P4 va = *(const P4*)(x + base); P4 vb = va; if (y) vb = *(const P4*)(y + base);\n"
+       "      B4 wa = {{1, 1, 1, 1}}, wb = {{1, 1, 1, 1}}, wo = {{1, 1, 1, 1}};\n"
+       "      if (px) wa = *(const B4*)(px + base); if (py) wb = *(const B4*)(py + base); if (both) wo = *(const B4*)(both + base);\n"
+       "#pragma unroll\n"
+       "      for (int h = 0; h < 4; h++) { a[h] = va.v[h]; b[h] = vb.v[h]; ap[h] = wa.v[h] != 0; bp[h] = wb.v[h] != 0; bo[h] = wo.v[h] != 0; }\n"
+       "    } else {\n"
+       "#pragma unroll\n"
+       "      for (int h = 0; h < 4; h++) { const unsigned long long i = h < nv ? base + h : base;\n"
+       "        a[h] = x[i]; b[h] = y ? y[i] : a[h]; ap[h] = px ? px[i] != 0 : true; bp[h] = py ? py[i] != 0 : true; bo[h] = both ? both[i] != 0 : true; }\n"
+       "    }\n"
+       "#pragma unroll\n"
+       "    for (int h = 0; h < 4; h++) {\n";
+  switch (kind) {
+    case UK_APPLY:   o << "      rp[h] = ap[h]; r[h] = ap[h] ? grb_f(a[h], a[h]) : (T)0;\n"; break;
+    case UK_BIND1ST: o << "      rp[h] = ap[h]; r[h] = ap[h] ? grb_f(s, a[h]) : (T)0;\n"; break;
+    case UK_BIND2ND: o << "      rp[h] = ap[h]; r[h] = ap[h] ? grb_f(a[h], s) : (T)0;\n"; break;
+    case UK_EMULT:   o << "      rp[h] = ap[h] && bp[h]; r[h] = rp[h] ? grb_f(a[h], b[h]) : (T)0;\n"; break;
+    default:         o << "      const bool two = ap[h] && bp[h] && bo[h]; rp[h] = ap[h] || bp[h];\n"      // one operand alone has the entry: its value is copied, the operator is not called
+                          "      r[h] = two ? grb_f(a[h], b[h]) : (ap[h] ? a[h] : (bp[h] ? b[h] : (T)0));\n"; break;
+  }
+  o << "    }\n"
+       "    if (nv == 4 && packed) {\n"
+       "      P4 t; B4 u;\n"
+       "#pragma unroll\n"
+       "      for (int h = 0; h < 4; h++) { t.v[h] = r[h]; u.v[h] = rp[h] ? 1 : 0; }\n"
+       "      *(P4*)(z + base) = t; if (q) *(B4*)(q + base) = u;\n"
+       "    } else { for (int h = 0; h < nv; h++) { z[base + h] = r[h]; if (q) q[base + h] = rp[h] ? 1 : 0; } }\n"
+       "  }\n"
+       "}\n";
+  return o.str();
+}
+
+struct Entry { bool compiling = false, failed = false; hipFunction_t fn = nullptr; hipModule_t mod = nullptr; std::string log; };
+std::map<std::string, Entry> g_cache;      // keyed by the generated text
+std::mutex g_mu;
+std::condition_variable g_cv;
+
+hipFunction_t kernel_for(int kind, const char* name, const char* defn, int tcode) {
+  if (!jit_available()) fail(GrB_PANIC, std::string("user-defined operator ") + name + ": libhiprtc was not found, and a user-defined operator has no other way to run");
+  const std::string src = generate(kind, name, defn, tcode);
+  std::unique_lock<std::mutex> lk(g_mu);
+  Entry& en = g_cache[src];
+  g_cv.wait(lk, [&] { return !en.compiling; });      // (another thread is compiling this very text: its result serves both)
+  if (!en.fn && !en.failed) {
+    en.compiling = true;
+    lk.unlock();                                     // the compilation (or the read of its cached code object) holds no lock
+    hipModule_t mod = nullptr; hipFunction_t f = nullptr; bool from_disk = false; std::string log;
+    const bool ok = jit_build_kernel(src, "grb_userop", "userop", &mod, &f, &from_disk, &log);
+    lk.lock();
+    en.compiling = false;
+    if (ok) { en.mod = mod; en.fn = f; if (from_disk) g_stat_from_disk++; else g_stat_compiled++; }
+    else { en.failed = true; en.log = log.empty() ? std::string("(no compiler log)") : log; }
+    g_cv.notify_all();
+  }
+  if (en.failed) fail(GrB_INVALID_VALUE, std::string("user-defined operator ") + name + ": its definition does not compile for the device:\n" + en.log);
+  return en.fn;
+}
+
+}  // namespace
+
+void userop_refuse(const char* opname, const char* where) {
+  fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + " cannot be used as " + where +
+                            ": user-defined operators run in apply, apply with a bound scalar, eWiseAdd and eWiseMult only");
+}
+
+void userop_run(int kind, const char* name, const char* defn, int tcode, uint64_t n, const void* x, const uint8_t* px, const void* y, const uint8_t* py,
+                const uint8_t* both, const void* scalar, void* z, uint8_t* q) {
+  if (!c_type(tcode) || !defn) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + name + ": not one of the real built-in types");
+  hipFunction_t fn = kernel_for(kind, name, defn, tcode);
+  g_last_plan = std::string("userop<name=") + name + ",kind=" + kind_name(kind) + ",type=" + type_by_code(tcode)->name + "> grb_userop ";
+  if (!n) return;
+  const size_t ts = (size_t)type_size(tcode), pa = 4 * ts > 16 ? 16 : 4 * ts;
+  auto al = [](const void* p, size_t a) { return !p || ((uintptr_t)p % a) == 0; };
+  int packed = al(x, pa) && al(y, pa) && al(z, pa) && al(px, 4) && al(py, 4) && al(both, 4) && al(q, 4) ? 1 : 0;
+  uint8_t s[16] = {0}; if (scalar) memcpy(s, scalar, ts);
+  unsigned long long nn = n;
+  void* args[] = {(void*)&x, (void*)&px, (void*)&y, (void*)&py, (void*)&both, (void*)s, (void*)&z, (void*)&q, (void*)&nn, (void*)&packed};
+  uint64_t blocks = (n + 1023) / 1024, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap;
+  GRB_HIP(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream(), args, nullptr));
+  g_stat_launched++;
+}
+
+}  // namespace grb
+
+using namespace grb;
+
+static bool one_real_type(GrB_Type a, GrB_Type b, GrB_Type c) {
+  return check_obj(a) && check_obj(b) && check_obj(c) && a == b && b == c && a->code >= T_BOOL && a->code <= T_FP64;
+}
+static char* copy_text(const char* t) { const size_t n = strlen(t); char* c = (char*)malloc(n + 1); if (c) memcpy(c, t, n + 1); return c; }
+// the name is spliced into the kernel's text as the function to call: it has to be a C identifier
+static bool is_identifier(const char* s) {
+  if (!*s || (*s >= '0' && *s <= '9')) return false;
+  for (; *s; s++) if (!((*s >= 'a' && *s <= 'z') || (*s >= 'A' && *s <= 'Z') || (*s >= '0' && *s <= '9') || *s == '_')) return false;
+  return true;
+}
+
+extern "C" {
+
+GrB_Info GxB_UnaryOp_new(GrB_UnaryOp* op, void* fn, GrB_Type ztype, GrB_Type xtype, const char* name, const char* defn) {
+  if (!op || !name || !defn || !ztype || !xtype) return GrB_NULL_POINTER;
+  if (!check_obj(ztype) || !check_obj(xtype)) return GrB_UNINITIALIZED_OBJECT;
+  if (!one_real_type(ztype, xtype, xtype)) { g_last_error = std::string("GxB_UnaryOp_new ") + name + ": the operator's types must be one real built-in type"; return GrB_DOMAIN_MISMATCH; }
+  if (!is_identifier(name) || strlen(name) >= 40) { g_last_error = "GxB_UnaryOp_new: the name must be the C identifier of the defined function (at most 39 characters)"; return GrB_INVALID_VALUE; }
+  char* text = copy_text(defn); if (!text) return GrB_OUT_OF_MEMORY;
+  auto* r = new (std::nothrow) GrB_UnaryOp_opaque{GRB_MAGIC, g_next_unop++, xtype, ztype, "", fn, text};
+  if (!r) { free(text); return GrB_OUT_OF_MEMORY; }
+  snprintf(r->name, sizeof r->name, "%s", name); *op = r; return GrB_SUCCESS;
+}
+GrB_Info GxB_BinaryOp_new(GrB_BinaryOp* op, void* fn, GrB_Type ztype, GrB_Type xtype, GrB_Type ytype, const char* name, const char* defn) {
+  if (!op || !name || !defn || !ztype || !xtype || !ytype) return GrB_NULL_POINTER;
+  if (!check_obj(ztype) || !check_obj(xtype) || !check_obj(ytype)) return GrB_UNINITIALIZED_OBJECT;
+  if (!one_real_type(ztype, xtype, ytype)) { g_last_error = std::string("GxB_BinaryOp_new ") + name + ": the operator's types must be one real built-in type"; return GrB_DOMAIN_MISMATCH; }
+  if (!is_identifier(name) || strlen(name) >= 40) { g_last_error = "GxB_BinaryOp_new: the name must be the C identifier of the defined function (at most 39 characters)"; return GrB_INVALID_VALUE; }
+  char* text = copy_text(defn); if (!text) return GrB_OUT_OF_MEMORY;
+  auto* r = new (std::nothrow) GrB_BinaryOp_opaque{GRB_MAGIC, g_next_binop++, xtype, ytype, ztype, "", fn, text};
+  if (!r) { free(text); return GrB_OUT_OF_MEMORY; }
+  snprintf(r->name, sizeof r->name, "%s", name); *op = r; return GrB_SUCCESS;
+}
+// built-in handles stay untouched; a user operator is released and the caller's variable set to NULL (a second free of that variable is a no-op)
+GrB_Info GrB_UnaryOp_free(GrB_UnaryOp* op) {
+  if (op && *op && check_obj(*op) && is_user(*op)) { (*op)->magic = GRB_FREED; free((*op)->defn); delete *op; *op = nullptr; }
+  return GrB_SUCCESS;
+}
+GrB_Info GrB_BinaryOp_free(GrB_BinaryOp* op) {
+  if (op && *op && check_obj(*op) && is_user(*op)) { (*op)->magic = GRB_FREED; free((*op)->defn); delete *op; *op = nullptr; }
+  return GrB_SUCCESS;
+}
+GrB_Info GrBX_userop_stats(uint64_t* compiled, uint64_t* loaded_from_disk, uint64_t* launched) {
+  if (compiled) *compiled = g_stat_compiled.load(); if (loaded_from_disk) *loaded_from_disk = g_stat_from_disk.load(); if (launched) *launched = g_stat_launched.load();
+  return GrB_SUCCESS;
+}
+// the text that is compiled for an operator of `type` named `name` with the definition `defn` in an operation of `kind` (0 apply, 1 bind1st, 2 bind2nd, 3 eadd, 4 emult)
+GrB_Info GrBX_userop_source(const char* name, const char* defn, GrB_Type type, int kind, char* buf, size_t len) {
+  if (!name || !defn || !type || !buf || !len) return GrB_NULL_POINTER;
+  if (!check_obj(type)) return GrB_UNINITIALIZED_OBJECT;
+  if (type->code > T_FP64 || kind < UK_APPLY || kind > UK_EMULT) return GrB_DOMAIN_MISMATCH;
+  const std::string src = generate(kind, name, defn, type->code);
+  if (src.size() + 1 > len) return GrB_INSUFFICIENT_SPACE;
+  memcpy(buf, src.c_str(), src.size() + 1); return GrB_SUCCESS;
+}
+// which images of a container are valid right now (bit 0: the host mirror, bit 1: the HBM image) — looks, changes nothing, completes no deferred work
+GrB_Info GrBX_Matrix_residency(const GrB_Matrix A, int* where) {
+  if (!A || !where) return GrB_NULL_POINTER; if (!check_obj(A)) return GrB_UNINITIALIZED_OBJECT;
+  *where = (A->host_valid ? 1 : 0) | ((A->dev_valid || A->bm.valid) ? 2 : 0); return GrB_SUCCESS;
+}
+GrB_Info GrBX_Vector_residency(const GrB_Vector v, int* where) {
+  if (!v || !where) return GrB_NULL_POINTER; if (!check_obj(v)) return GrB_UNINITIALIZED_OBJECT;
+  *where = (v->host_valid ? 1 : 0) | (v->dev_valid ? 2 : 0); return GrB_SUCCESS;
+}
+// the message of this thread's most recent failure: what the calls without an object to hang it on leave (GxB_*Op_new, GrB_Monoid_new, GrB_Semiring_new)
+GrB_Info GrBX_last_error(char* buf, int len) { if (buf && len > 0) snprintf(buf, len, "%s", g_last_error.c_str()); return GrB_SUCCESS; }
+
+}  // extern "C"

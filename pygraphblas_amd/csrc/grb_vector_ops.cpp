@@ -167,10 +167,61 @@ static void vec_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const 
   w->dnvals_known = !allow && !reg; w->dnvals = w->dnvals_known ? n : 0;       // every index, no mask: the vector is full now
 }
 
+// a user-defined operator (grb_userop.cpp) runs on bitmap vectors in HBM only
+static void user_needs_layout(const char* opname, bool hyper, bool cplx) {
+  if (hyper) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": hypersparse containers (a size beyond the device layout) are out of its scope");
+  if (cplx) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": complex containers are out of its scope");
+}
+
+// eWiseAdd / eWiseMult with a user-defined operator: never queued — deferred work is completed first, then the operator's compiled kernel runs over the two bitmaps
+static void vec_ewise_user(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v, GrB_Descriptor desc, bool is_union) {
+  user_needs_layout(op->name, is_hyper(w) || is_hyper(u) || is_hyper(v) || (mask && is_hyper(mask)),
+                    w->type->code >= T_FC32 || u->type->code >= T_FC32 || v->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc); const uint64_t n = w->n;
+  if (u->n != n || v->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "eWise: vector sizes differ");
+  lazy_flush();
+  if (!mask && dv.mask_comp) { if (dv.replace) GrB_Vector_clear(w); return; }
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
+  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  vec_to_device(u); vec_to_device(v);
+  const int xc = op->xtype->code;
+  DevBuf uc, vc, tval(n * type_size(xc) + 16), tpres(n + 16);
+  const void* uv = cast_values(xc, u->type->code, u->dval.p, n, uc);
+  const void* vv = cast_values(xc, v->type->code, v->dval.p, n, vc);
+  userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), nullptr, nullptr, tval.p, tpres.as<uint8_t>());
+  const bool uf = u->dnvals_known && u->dnvals == n, vf = v->dnvals_known && v->dnvals == n;
+  const uint64_t tn = (is_union ? (uf || vf) : (uf && vf)) ? n : ~0ull;
+  vector_write_back(w, xc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/false, tn);
+}
+
+// apply with a user-defined operator: kind UK_APPLY (unary) or UK_BIND1ST / UK_BIND2ND (binary with a bound scalar)
+static void vec_apply_user(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, int kind, const char* name, const char* defn, int xcode, const void* scalar, int scode,
+                           GrB_Vector u, GrB_Descriptor desc) {
+  need_device();
+  if (!check_obj(u) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "apply: uninitialised operand");
+  user_needs_layout(name, is_hyper(w) || is_hyper(u) || (mask && is_hyper(mask)), w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32) || scode >= T_FC32);
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc); const uint64_t n = w->n;
+  if (u->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "apply: vector sizes differ");
+  lazy_flush();
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
+  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  uint8_t s[16] = {0}; if (scalar) cast_scalar(xcode, s, scode, scalar);
+  vec_to_device(u);
+  DevBuf uc, tval(n * type_size(xcode) + 16), tpres(n + 16);
+  const void* uv = cast_values(xcode, u->type->code, u->dval.p, n, uc);
+  userop_run(kind, name, defn, xcode, n, uv, u->dpres.as<uint8_t>(), nullptr, nullptr, nullptr, s, tval.p, tpres.as<uint8_t>());
+  vector_write_back(w, xcode, tval, tpres, allow, accum, dv.replace, false, u->dnvals_known ? u->dnvals : ~0ull);
+}
+
 static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v,
                          GrB_Descriptor desc, bool is_union) {
   need_device();
   if (!check_obj(u) || !check_obj(v) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "eWise: uninitialised operand");
+  if (check_obj(op) && is_user(op)) { vec_ewise_user(w, mask, accum, op, u, v, desc, is_union); return; }
   check_binop(op, "eWise");
   if (is_hyper(w)) { hyper_vec_ewise(w, mask, accum, op, u, v, desc, is_union); return; }      // a size beyond the device layout
   const DescView dv(desc); const uint64_t n = w->n;
@@ -283,7 +334,7 @@ GrB_Info GrBX_Vector_iseq(bool* equal, const GrB_Vector u, const GrB_Vector v) {
 
 GrB_Info GrB_Vector_apply(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_UnaryOp op, const GrB_Vector u, const GrB_Descriptor desc) {
   VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
-  return guarded(w, [&] { if (op->opcode >= U_USER) not_implemented("user-defined unary operator");
+  return guarded(w, [&] { if (is_user(op)) { vec_apply_user(w, mask, accum, UK_APPLY, op->name, op->defn, op->xtype->code, nullptr, 0, u, desc); return; }
     if (op->opcode >= U_POSITIONI) { vec_position_op(w, mask, accum, op->opcode - U_POSITIONI, op->ztype->code, u, desc); return; }
     vec_apply_op(w, mask, accum, 0, op->opcode, op->xtype->code, op->ztype->code, nullptr, 0, u, desc); });
 }
@@ -325,9 +376,11 @@ GrB_Info GxB_Vector_select(GrB_Vector w, const GrB_Vector mask, const GrB_Binary
   GrB_Info GrB_Vector_assign_##SUF(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, CT x, const GrB_Index* I, GrB_Index ni, const GrB_Descriptor desc) { \
     VEC_GUARD(w); return guarded(w, [&] { vec_assign(w, mask, accum, &x, CODE, I, ni, desc); }); } \
   GrB_Info GxB_Vector_apply_BinaryOp1st_##SUF(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, CT x, const GrB_Vector u, const GrB_Descriptor desc) { \
-    VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; return guarded(w, [&] { check_binop(op, "apply"); vec_apply_op(w, mask, accum, 1, op->opcode, op->xtype->code, op->ztype->code, &x, CODE, u, desc); }); } \
+    VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; return guarded(w, [&] { if (check_obj(op) && is_user(op)) { vec_apply_user(w, mask, accum, UK_BIND1ST, op->name, op->defn, op->xtype->code, &x, CODE, u, desc); return; } \
+                                                                            check_binop(op, "apply"); vec_apply_op(w, mask, accum, 1, op->opcode, op->xtype->code, op->ztype->code, &x, CODE, u, desc); }); } \
   GrB_Info GxB_Vector_apply_BinaryOp2nd_##SUF(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, CT y, const GrB_Descriptor desc) { \
-    VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; return guarded(w, [&] { check_binop(op, "apply"); vec_apply_op(w, mask, accum, 2, op->opcode, op->xtype->code, op->ztype->code, &y, CODE, u, desc); }); }
+    VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; return guarded(w, [&] { if (check_obj(op) && is_user(op)) { vec_apply_user(w, mask, accum, UK_BIND2ND, op->name, op->defn, op->xtype->code, &y, CODE, u, desc); return; } \
+                                                                            check_binop(op, "apply"); vec_apply_op(w, mask, accum, 2, op->opcode, op->xtype->code, op->ztype->code, &y, CODE, u, desc); }); }
 GRB_TYPED_VECOPS(BOOL, bool, T_BOOL) GRB_TYPED_VECOPS(INT8, int8_t, T_INT8) GRB_TYPED_VECOPS(UINT8, uint8_t, T_UINT8)
 GRB_TYPED_VECOPS(INT16, int16_t, T_INT16) GRB_TYPED_VECOPS(UINT16, uint16_t, T_UINT16) GRB_TYPED_VECOPS(INT32, int32_t, T_INT32)
 GRB_TYPED_VECOPS(UINT32, uint32_t, T_UINT32) GRB_TYPED_VECOPS(INT64, int64_t, T_INT64) GRB_TYPED_VECOPS(UINT64, uint64_t, T_UINT64)

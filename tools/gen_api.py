@@ -361,6 +361,23 @@ GrB_Info GrB_Semiring_new(GrB_Semiring *semiring, GrB_Monoid add, GrB_BinaryOp m
 GrB_Info GrB_Semiring_free(GrB_Semiring *semiring);
 GrB_Info GrB_Monoid_free(GrB_Monoid *monoid);
 
+/* ---- user-defined unary / binary operators, handed over as C source and compiled for the device at first use (grb_userop.cpp) ----
+ * `defn` is the C definition of the function `name`, in SuiteSparse 7's form: "void NAME (T *z, const T *x) { ... }" or
+ * "void NAME (T *z, const T *x, const T *y) { ... }", T the C type of the GraphBLAS type; helper functions may precede it in the same string.
+ * `fn` (a host function pointer) is never called and may be NULL.  All of the operator's types must be ONE of the 11 real built-in types
+ * (GrB_DOMAIN_MISMATCH otherwise).  Such an operator runs in GrB_*_apply, GxB_*_apply_BinaryOp1st / 2nd, GrB_*_eWiseAdd_BinaryOp and
+ * GrB_*_eWiseMult_BinaryOp on containers with an HBM layout; every other use returns GrB_DOMAIN_MISMATCH.  The function-pointer forms
+ * GrB_UnaryOp_new / GrB_BinaryOp_new, GrB_Type_new and GxB_SelectOp_new do not exist. */
+GrB_Info GxB_UnaryOp_new(GrB_UnaryOp *unaryop, void *function, GrB_Type ztype, GrB_Type xtype, const char *name, const char *defn);
+GrB_Info GxB_BinaryOp_new(GrB_BinaryOp *binaryop, void *function, GrB_Type ztype, GrB_Type xtype, GrB_Type ytype, const char *name, const char *defn);
+GrB_Info GrB_UnaryOp_free(GrB_UnaryOp *unaryop);     /* releases a user-defined operator and sets the variable to NULL; built-in handles are left alone */
+GrB_Info GrB_BinaryOp_free(GrB_BinaryOp *binaryop);
+GrB_Info GrBX_userop_stats(uint64_t *compiled, uint64_t *loaded_from_disk, uint64_t *launched); /* user-operator kernels compiled with hipRTC, loaded from the code-object cache on disk instead, and launches through them */
+GrB_Info GrBX_userop_source(const char *name, const char *defn, GrB_Type type, int kind, char *buf, size_t len); /* the kernel text compiled for such an operator in an operation of `kind` (0 apply, 1 bind1st, 2 bind2nd, 3 eadd, 4 emult) */
+GrB_Info GrBX_Matrix_residency(const GrB_Matrix A, int *where);   /* which images of the container are valid: bit 0 the host mirror, bit 1 the HBM image (a look: nothing is moved, no deferred work completed) */
+GrB_Info GrBX_Vector_residency(const GrB_Vector v, int *where);
+GrB_Info GrBX_last_error(char *buf, int len);        /* the message of the calling thread's most recent failure (for calls that have no container to ask: GxB_*Op_new, GrB_Monoid_new_*, GrB_Semiring_new) */
+
 /* ---- matrices ---- */
 GrB_Info GrB_Matrix_new(GrB_Matrix *A, GrB_Type type, GrB_Index nrows, GrB_Index ncols);
 GrB_Info GrB_Matrix_dup(GrB_Matrix *C, const GrB_Matrix A);
