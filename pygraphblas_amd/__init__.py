@@ -19,18 +19,18 @@ from .base import (GraphBLASException, NoValue, UninitializedObject, InvalidObje
                    IndexOutOfBound, Panic)
 from . import types, descriptor  # noqa: E402
 from .types import (BOOL, INT8, UINT8, INT16, UINT16, INT32, UINT32, INT64, UINT64, FP32, FP64, Accum, BinaryOp, Monoid,  # noqa: E402
-                    Semiring, UnaryOp, promote)
+                    Semiring, UnaryOp, SelectOp, promote)
 from .matrix import Matrix  # noqa: E402
 from .vector import Vector  # noqa: E402
 from . import userop  # noqa: E402
-from .userop import unary_op, binary_op  # noqa: E402
+from .userop import unary_op, binary_op, select_op  # noqa: E402
 
 GxB_INDEX_MAX = _capi.constants["GxB_INDEX_MAX"]
 device_info = _capi.device_info
 last_kernel_plan = _capi.last_kernel_plan
 
-__all__ = ["lib", "Matrix", "Vector", "types", "descriptor", "Accum", "BinaryOp", "Monoid", "Semiring", "UnaryOp", "promote",
-           "userop", "unary_op", "binary_op",
+__all__ = ["lib", "Matrix", "Vector", "types", "descriptor", "Accum", "BinaryOp", "Monoid", "Semiring", "UnaryOp", "SelectOp", "promote",
+           "userop", "unary_op", "binary_op", "select_op",
            "BOOL", "INT8", "UINT8", "INT16", "UINT16", "INT32", "UINT32", "INT64", "UINT64", "FP32", "FP64",
            "GraphBLASException", "NoValue", "UninitializedObject", "InvalidObject", "NullPointer", "InvalidValue",
            "InvalidIndex", "DomainMismatch", "DimensionMismatch", "OutputNotEmpty", "OutOfMemory", "InsufficientSpace",

@@ -47,7 +47,8 @@ struct GrB_BinaryOp_opaque { uint64_t magic; int opcode; GrB_Type_opaque* xtype;
 struct GrB_Monoid_opaque { uint64_t magic; GrB_BinaryOp_opaque* op; uint8_t identity[16]; bool has_terminal; uint8_t terminal[16]; char name[48]; bool builtin; };
 struct GrB_Semiring_opaque { uint64_t magic; GrB_Monoid_opaque* add; GrB_BinaryOp_opaque* mul; char name[56]; bool builtin; };
 struct GrB_Descriptor_opaque { uint64_t magic; int outp, mask, inp0, inp1, axb, nthreads, sort; double chunk; bool builtin; char name[16]; };
-struct GxB_SelectOp_opaque { uint64_t magic; int opcode; char name[24]; void* fn; GrB_Type_opaque* xtype; GrB_Type_opaque* ttype; };
+// a user-defined select operator (GxB_SelectOp_new, grb_userop.cpp; opcode >= SEL_USER) has its value and thunk types and owns a copy of its C definition; built-ins: nullptr
+struct GxB_SelectOp_opaque { uint64_t magic; int opcode; char name[40]; void* fn; GrB_Type_opaque* xtype; GrB_Type_opaque* ttype; char* defn; };
 
 typedef GrB_Type_opaque* GrB_Type;
 typedef GrB_UnaryOp_opaque* GrB_UnaryOp;

@@ -12,6 +12,7 @@
 #include "grb_opcommon.hpp"
 #include "grb_matops.hpp"
 #include "grb_extract.hpp"
+#include "grb_lazy.hpp"
 
 using namespace grb;
 
@@ -265,10 +266,33 @@ void do_apply_user(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, int kind, con
   matrix_write_back(C, T, xcode, M, dv, accum, false);
 }
 
+// select with a user-defined operator: the predicate's compiled kernel writes the keep bytes over op(A)'s entries (their row indices expanded, the values cast
+// into the operator's type FOR THE PREDICATE ONLY: T keeps A's own values and type), then the compaction and write-back of every select.  Never queued.
+void do_select_user(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GxB_SelectOp op, GrB_Matrix A, GxB_Scalar thunk, GrB_Descriptor desc) {
+  const bool has_thunk = thunk && check_obj(thunk) && thunk->has;
+  user_needs_layout(op->name, is_hyper(C) || is_hyper(M) || is_hyper(A),
+                    C->type->code >= T_FC32 || A->type->code >= T_FC32 || (M && M->type->code >= T_FC32) || (has_thunk && thunk->type->code >= T_FC32));
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc);
+  const uint64_t r = dv.tran0 ? A->ncols : A->nrows, c = dv.tran0 ? A->nrows : A->ncols;
+  if (C->nrows != r || C->ncols != c || (M && (M->nrows != r || M->ncols != c))) fail(GrB_DIMENSION_MISMATCH, "select: dimensions do not conform");
+  lazy_flush();
+  if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
+  const DevCSR& S = operand(A, dv.tran0);           // (a transposed input: i and j are those of the transposed matrix)
+  const int acode = A->type->code, xc = op->xtype->code, kc = op->ttype->code;
+  DevBuf rowidx(S.nnz * 4 + 16), keep(S.nnz + 16), xcast; DevCSR T;
+  csr_row_indices(S, rowidx.as<uint32_t>());
+  const void* xv = cast_values(xc, acode, S.val.p, S.nnz, xcast);
+  uint8_t th[16] = {0}; if (has_thunk) cast_scalar(kc, th, thunk->type->code, thunk->x);      // (no thunk, or an empty one: the zero of the thunk type)
+  userselect_run(op->name, op->defn, xc, kc, false, S.nnz, rowidx.as<uint32_t>(), S.col.as<uint32_t>(), xv, nullptr, th, keep.as<uint8_t>());
+  csr_compact(S, S.val.p, A->type->size, keep.as<uint8_t>(), T);
+  matrix_write_back(C, T, acode, M, dv, accum, false);
+}
+
 void do_select(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GxB_SelectOp op, GrB_Matrix A, GxB_Scalar thunk, GrB_Descriptor desc) {
   need_device(); check_mat(A, "select"); if (M) check_mat(M, "select");
   if (!check_obj(op)) fail(GrB_UNINITIALIZED_OBJECT, "select: operator");
-  if (op->opcode == SEL_USER) not_implemented("user-defined select operator");
+  if (is_user(op)) { do_select_user(C, M, accum, op, A, thunk, desc); return; }
   const DescView dv(desc);
   const uint64_t r = dv.tran0 ? A->ncols : A->nrows, c = dv.tran0 ? A->nrows : A->ncols;
   if (C->nrows != r || C->ncols != c || (M && (M->nrows != r || M->ncols != c))) fail(GrB_DIMENSION_MISMATCH, "select: dimensions do not conform");

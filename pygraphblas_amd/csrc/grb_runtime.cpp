@@ -257,7 +257,9 @@ GrB_Info GxB_Semiring_fprint(GrB_Semiring s, const char* name, int pr, FILE* f) 
 }
 GrB_Info GxB_SelectOp_fprint(GxB_SelectOp op, const char* name, int pr, FILE* f) {
   if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; if (pr <= 0) return GrB_SUCCESS;
-  fprintf(outf(f), "\n    GraphBLAS SelectOp: %s: %s\n", name ? name : "", op->name); return GrB_SUCCESS;
+  if (is_user(op)) fprintf(outf(f), "\n    GraphBLAS SelectOp: %s (user-defined) keep=%s(i,j,x,thunk)  x:%s thunk:%s\n", name ? name : "", op->name, op->xtype->name, op->ttype->name);
+  else fprintf(outf(f), "\n    GraphBLAS SelectOp: %s: %s\n", name ? name : "", op->name);
+  return GrB_SUCCESS;
 }
 
 // ---- descriptors ----------------------------------------------------------------------------------

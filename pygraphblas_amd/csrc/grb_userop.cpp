@@ -18,6 +18,12 @@
 // user's code only; where eWiseAdd finds an entry in one operand alone, the value is copied and the operator is not called.
 // A definition that does not compile, or a machine without hipRTC: the operation fails with an error code and the operator's name and the compiler's
 // log in the object's error string — there is no interpreter and no host route behind it.
+//
+//   GxB_SelectOp_new (&op, fn, xtype, ttype, name, defn)             defn: "bool NAME (GrB_Index i, GrB_Index j, const X *x, const K *thunk) { ... }"
+// is the same for select: a predicate over an entry's row, column, value (X: the C type of xtype) and the thunk (K: of ttype; NULL: xtype).  GxB_Matrix_select /
+// GxB_Vector_select run it through userselect_run: one text per (definition, name, xtype, ttype, matrix | vector) with the kernel grb_userselect, which writes
+// one keep byte per stored entry (matrix: per CSR position; vector: per bitmap position, i the position and j 0); the drivers compact / write back as for the
+// built-in select operators.
 #include "grb_api.hpp"
 #include "grb_device.hpp"
 #include "grb_jit.hpp"
@@ -31,7 +37,7 @@
 namespace grb {
 namespace {
 
-std::atomic<int> g_next_unop{U_NOPS}, g_next_binop{B_NOPS};
+std::atomic<int> g_next_unop{U_NOPS}, g_next_binop{B_NOPS}, g_next_selop{SEL_USER};
 std::atomic<uint64_t> g_stat_compiled{0}, g_stat_from_disk{0}, g_stat_launched{0};
 
 const char* c_type(int code) {
@@ -103,14 +109,57 @@ std::string generate(int kind, const char* name, const char* defn, int tcode) {
   return o.str();
 }
 
+// the select kernel around a predicate.  One text per (definition, name, xtype, ttype, matrix | vector).  The geometry is grb_userop's: 256 threads, a lane owns
+// four consecutive entries.  Packed path (every array aligned, a whole group): row indices, column indices and 4-byte values one 16-byte pack each (8-byte
+// values two, narrower ones one narrower pack), presence one 4-byte word, the four keep bytes one 4-byte word; the last partial group and unaligned views
+// go entry by entry.  Indices are widened unsigned to GrB_Index; the predicate is not evaluated for an absent position (&& short-circuits).
+std::string generate_select(const char* name, const char* defn, int xcode, int tcode, bool on_vector) {
+  const int ts = type_size(xcode);
+  std::ostringstream o;
+  o << PRELUDE << "typedef unsigned long long GrB_Index;\n"
+    << "#pragma clang force_cuda_host_device begin\n" << defn << "\n#pragma clang force_cuda_host_device end\n"
+    << "typedef " << c_type(xcode) << " X; typedef " << c_type(tcode) << " K;\n"
+    << "#define GRB_ON_VECTOR " << (on_vector ? 1 : 0) << "\n"
+    << "struct __attribute__((aligned(" << (4 * ts > 16 ? 16 : 4 * ts) << "))) P4 { X v[4]; }; struct __attribute__((aligned(16))) U4 { unsigned v[4]; };\n"
+       "struct __attribute__((aligned(4))) B4 { unsigned char v[4]; };\n"
+    // rowidx / col: the entries' row and column indices (vector: unused, i is the position and j is 0); x: values; pres: presence bytes (0 = all present);
+    // thunk: already in K; keep: one byte per entry
+    << "extern \"C\" __global__ void __launch_bounds__(256) grb_userselect(const unsigned* rowidx, const unsigned* col, const X* x, const unsigned char* pres, K thunk,\n"
+       "    unsigned char* keep, unsigned long long n, int packed) {\n"
+       "  const unsigned long long stride = (unsigned long long)gridDim.x * 1024ull;\n"
+       "  const bool positions = GRB_ON_VECTOR || !rowidx;\n"
+       "  for (unsigned long long base = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) * 4ull; base < n; base += stride) {\n"
+       "    const int nv = n - base >= 4ull ? 4 : (int)(n - base);\n"
+       "    X a[4]; GrB_Index ri[4], cj[4]; bool ap[4]; unsigned char r[4];\n"
+       "    if (nv == 4 && packed) {\n"
+       "      const P4 va = *(const P4*)(x + base);\n"
+       "      B4 wa = {{1, 1, 1, 1}}; if (pres) wa = *(const B4*)(pres + base);\n"
+       "      U4 vr = {{0, 0, 0, 0}}, vc = {{0, 0, 0, 0}};\n"
+       "      if (!positions) { vr = *(const U4*)(rowidx + base); vc = *(const U4*)(col + base); }\n"
+       "#pragma unroll\n"
+       "      for (int h = 0; h < 4; h++) { a[h] = va.v[h]; ap[h] = wa.v[h] != 0; ri[h] = positions ? base + h : (GrB_Index)vr.v[h]; cj[h] = positions ? 0ull : (GrB_Index)vc.v[h]; }\n"
+       "    } else {\n"
+       "#pragma unroll\n"
+       "      for (int h = 0; h < 4; h++) { const unsigned long long p = h < nv ? base + h : base;\n"
+       "        a[h] = x[p]; ap[h] = pres ? pres[p] != 0 : true; ri[h] = positions ? p : (GrB_Index)rowidx[p]; cj[h] = positions ? 0ull : (GrB_Index)col[p]; }\n"
+       "    }\n"
+       "#pragma unroll\n"
+       "    for (int h = 0; h < 4; h++) r[h] = (ap[h] && " << name << "(ri[h], cj[h], &a[h], &thunk)) ? 1 : 0;\n"
+       "    if (nv == 4 && packed) { B4 u; u.v[0] = r[0]; u.v[1] = r[1]; u.v[2] = r[2]; u.v[3] = r[3]; *(B4*)(keep + base) = u; }\n"
+       "    else { for (int h = 0; h < nv; h++) keep[base + h] = r[h]; }\n"
+       "  }\n"
+       "}\n";
+  return o.str();
+}
+
 struct Entry { bool compiling = false, failed = false; hipFunction_t fn = nullptr; hipModule_t mod = nullptr; std::string log; };
 std::map<std::string, Entry> g_cache;      // keyed by the generated text
 std::mutex g_mu;
 std::condition_variable g_cv;
 
-hipFunction_t kernel_for(int kind, const char* name, const char* defn, int tcode) {
+// the compiled kernel `entry` of the text `src` (code objects on disk: `prefix`-<hash>.co), for the operator `name`
+hipFunction_t kernel_of(const std::string& src, const char* name, const char* entry, const char* prefix) {
   if (!jit_available()) fail(GrB_PANIC, std::string("user-defined operator ") + name + ": libhiprtc was not found, and a user-defined operator has no other way to run");
-  const std::string src = generate(kind, name, defn, tcode);
   std::unique_lock<std::mutex> lk(g_mu);
   Entry& en = g_cache[src];
   g_cv.wait(lk, [&] { return !en.compiling; });      // (another thread is compiling this very text: its result serves both)
@@ -118,7 +167,7 @@ hipFunction_t kernel_for(int kind, const char* name, const char* defn, int tcode
     en.compiling = true;
     lk.unlock();                                     // the compilation (or the read of its cached code object) holds no lock
     hipModule_t mod = nullptr; hipFunction_t f = nullptr; bool from_disk = false; std::string log;
-    const bool ok = jit_build_kernel(src, "grb_userop", "userop", &mod, &f, &from_disk, &log);
+    const bool ok = jit_build_kernel(src, entry, prefix, &mod, &f, &from_disk, &log);
     lk.lock();
     en.compiling = false;
     if (ok) { en.mod = mod; en.fn = f; if (from_disk) g_stat_from_disk++; else g_stat_compiled++; }
@@ -128,6 +177,7 @@ hipFunction_t kernel_for(int kind, const char* name, const char* defn, int tcode
   if (en.failed) fail(GrB_INVALID_VALUE, std::string("user-defined operator ") + name + ": its definition does not compile for the device:\n" + en.log);
   return en.fn;
 }
+hipFunction_t kernel_for(int kind, const char* name, const char* defn, int tcode) { return kernel_of(generate(kind, name, defn, tcode), name, "grb_userop", "userop"); }
 
 }  // namespace
 
@@ -148,6 +198,25 @@ void userop_run(int kind, const char* name, const char* defn, int tcode, uint64_
   uint8_t s[16] = {0}; if (scalar) memcpy(s, scalar, ts);
   unsigned long long nn = n;
   void* args[] = {(void*)&x, (void*)&px, (void*)&y, (void*)&py, (void*)&both, (void*)s, (void*)&z, (void*)&q, (void*)&nn, (void*)&packed};
+  uint64_t blocks = (n + 1023) / 1024, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap;
+  GRB_HIP(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream(), args, nullptr));
+  g_stat_launched++;
+}
+
+void userselect_run(const char* name, const char* defn, int xcode, int tcode, bool on_vector, uint64_t n, const uint32_t* rowidx, const uint32_t* col, const void* x,
+                    const uint8_t* pres, const void* thunk, uint8_t* keep) {
+  if (!c_type(xcode) || !c_type(tcode) || !defn) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + name + ": not one of the real built-in types");
+  hipFunction_t fn = kernel_of(generate_select(name, defn, xcode, tcode, on_vector), name, "grb_userselect", "userselect");
+  g_last_plan = std::string("userselect<name=") + name + ",xtype=" + type_by_code(xcode)->name + ",ttype=" + type_by_code(tcode)->name + ",on=" + (on_vector ? "vector" : "matrix") + "> grb_userselect ";
+  if (!n) return;
+  if (on_vector) { rowidx = nullptr; col = nullptr; }
+  else if (!rowidx || !col) fail(GrB_PANIC, std::string("user-defined operator ") + name + ": select on a matrix without its index arrays");
+  const size_t ts = (size_t)type_size(xcode), pa = 4 * ts > 16 ? 16 : 4 * ts;
+  auto al = [](const void* p, size_t a) { return !p || ((uintptr_t)p % a) == 0; };
+  int packed = al(rowidx, 16) && al(col, 16) && al(x, pa) && al(pres, 4) && al(keep, 4) ? 1 : 0;
+  uint8_t s[16] = {0}; if (thunk) memcpy(s, thunk, (size_t)type_size(tcode));
+  unsigned long long nn = n;
+  void* args[] = {(void*)&rowidx, (void*)&col, (void*)&x, (void*)&pres, (void*)s, (void*)&keep, (void*)&nn, (void*)&packed};
   uint64_t blocks = (n + 1023) / 1024, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap;
   GRB_HIP(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream(), args, nullptr));
   g_stat_launched++;
@@ -198,6 +267,33 @@ GrB_Info GrB_UnaryOp_free(GrB_UnaryOp* op) {
 GrB_Info GrB_BinaryOp_free(GrB_BinaryOp* op) {
   if (op && *op && check_obj(*op) && is_user(*op)) { (*op)->magic = GRB_FREED; free((*op)->defn); delete *op; *op = nullptr; }
   return GrB_SUCCESS;
+}
+// a predicate "bool NAME (GrB_Index i, GrB_Index j, const X *x, const K *thunk)": X the C type of xtype, K of ttype (NULL: the same as xtype), both real built-in types
+GrB_Info GxB_SelectOp_new(GxB_SelectOp* op, void* fn, GrB_Type xtype, GrB_Type ttype, const char* name, const char* defn) {
+  if (!op || !name || !defn || !xtype) return GrB_NULL_POINTER;
+  if (!check_obj(xtype) || (ttype && !check_obj(ttype))) return GrB_UNINITIALIZED_OBJECT;
+  if (!ttype) ttype = xtype;
+  if (!one_real_type(xtype, xtype, xtype) || !one_real_type(ttype, ttype, ttype)) {
+    g_last_error = std::string("GxB_SelectOp_new ") + name + ": the operator's value and thunk types must be real built-in types"; return GrB_DOMAIN_MISMATCH; }
+  if (!is_identifier(name) || strlen(name) >= 40) { g_last_error = "GxB_SelectOp_new: the name must be the C identifier of the defined function (at most 39 characters)"; return GrB_INVALID_VALUE; }
+  char* text = copy_text(defn); if (!text) return GrB_OUT_OF_MEMORY;
+  auto* r = new (std::nothrow) GxB_SelectOp_opaque{GRB_MAGIC, g_next_selop++, "", fn, xtype, ttype, text};
+  if (!r) { free(text); return GrB_OUT_OF_MEMORY; }
+  snprintf(r->name, sizeof r->name, "%s", name); *op = r; return GrB_SUCCESS;
+}
+GrB_Info GxB_SelectOp_free(GxB_SelectOp* op) {
+  if (op && *op && check_obj(*op) && is_user(*op)) { (*op)->magic = GRB_FREED; free((*op)->defn); delete *op; *op = nullptr; }
+  return GrB_SUCCESS;
+}
+// the text that is compiled for a select operator (`ttype` NULL: the same as `xtype`) used on a matrix (on_vector 0) or on a vector (1)
+GrB_Info GrBX_selectop_source(const char* name, const char* defn, GrB_Type xtype, GrB_Type ttype, int on_vector, char* buf, size_t len) {
+  if (!name || !defn || !xtype || !buf || !len) return GrB_NULL_POINTER;
+  if (!check_obj(xtype) || (ttype && !check_obj(ttype))) return GrB_UNINITIALIZED_OBJECT;
+  if (!ttype) ttype = xtype;
+  if (xtype->code > T_FP64 || ttype->code > T_FP64) return GrB_DOMAIN_MISMATCH;
+  const std::string src = generate_select(name, defn, xtype->code, ttype->code, on_vector != 0);
+  if (src.size() + 1 > len) return GrB_INSUFFICIENT_SPACE;
+  memcpy(buf, src.c_str(), src.size() + 1); return GrB_SUCCESS;
 }
 GrB_Info GrBX_userop_stats(uint64_t* compiled, uint64_t* loaded_from_disk, uint64_t* launched) {
   if (compiled) *compiled = g_stat_compiled.load(); if (loaded_from_disk) *loaded_from_disk = g_stat_from_disk.load(); if (launched) *launched = g_stat_launched.load();

@@ -1,4 +1,4 @@
-// grb_userop.hpp — user-defined unary / binary operators handed over as C source (GxB_UnaryOp_new / GxB_BinaryOp_new) and compiled for the device (grb_userop.cpp).
+// grb_userop.hpp — user-defined unary / binary / select operators handed over as C source (GxB_UnaryOp_new / GxB_BinaryOp_new / GxB_SelectOp_new) and compiled for the device (grb_userop.cpp).
 #pragma once
 #include "grb_internal.hpp"
 
@@ -8,6 +8,7 @@ enum UserKind { UK_APPLY = 0, UK_BIND1ST, UK_BIND2ND, UK_EADD, UK_EMULT };
 
 inline bool is_user(const GrB_BinaryOp_opaque* op) { return op->opcode >= B_USER; }
 inline bool is_user(const GrB_UnaryOp_opaque* op) { return op->opcode >= U_USER; }
+inline bool is_user(const GxB_SelectOp_opaque* op) { return op->opcode >= SEL_USER; }
 
 // GrB_DOMAIN_MISMATCH: the operator `opname` cannot be used as `where` (an accumulator, a monoid, a multiplier, ...)
 [[noreturn]] void userop_refuse(const char* opname, const char* where);
@@ -21,5 +22,15 @@ inline bool is_user(const GrB_UnaryOp_opaque* op) { return op->opcode >= U_USER;
 // Throws GrbError when hipRTC is missing or the definition does not compile (the message carries the operator's name and the compiler's log).
 void userop_run(int kind, const char* name, const char* defn, int tcode, uint64_t n, const void* x, const uint8_t* px, const void* y, const uint8_t* py,
                 const uint8_t* both, const void* scalar, void* z, uint8_t* q);
+
+// keep[p] = present(p) && NAME(i, j, &x[p], &thunk) over n entries with the select operator's compiled kernel (`name`, `defn`, value type xcode, thunk type
+// tcode); sets the kernel plan.
+//   rowidx / col entries' row and column indices of a matrix (on_vector: ignored — i is the position p, j is 0)
+//   x            the entries' values, already in xcode
+//   pres         presence bytes of a bitmap, nullptr = every position holds an entry
+//   thunk        the thunk, already in tcode
+// Throws like userop_run.
+void userselect_run(const char* name, const char* defn, int xcode, int tcode, bool on_vector, uint64_t n, const uint32_t* rowidx, const uint32_t* col, const void* x,
+                    const uint8_t* pres, const void* thunk, uint8_t* keep);
 
 }  // namespace grb

@@ -217,6 +217,29 @@ static void vec_apply_user(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, in
   vector_write_back(w, xcode, tval, tpres, allow, accum, dv.replace, false, u->dnvals_known ? u->dnvals : ~0ull);
 }
 
+// select with a user-defined operator over the bitmap: i is the position, j is 0; the values are cast into the operator's type for the predicate only.  Never queued.
+static void vec_select_user(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GxB_SelectOp op, GrB_Vector u, GxB_Scalar thunk, GrB_Descriptor desc) {
+  if (mask && !check_obj(mask)) fail(GrB_UNINITIALIZED_OBJECT, "select: uninitialised mask");
+  const bool has_thunk = thunk && check_obj(thunk) && thunk->has;
+  user_needs_layout(op->name, is_hyper(w) || is_hyper(u) || (mask && is_hyper(mask)),
+                    w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32) || (has_thunk && thunk->type->code >= T_FC32));
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc); const uint64_t n = w->n;
+  if (u->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "select: vector sizes differ");
+  lazy_flush();
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
+  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  vec_to_device(u);
+  const int uc = u->type->code, xc = op->xtype->code, kc = op->ttype->code; const size_t ts = u->type->size;
+  DevBuf tval(n * ts + 16), tpres(n + 16), xcast;
+  if (n) GRB_HIP(hipMemcpyAsync(tval.p, u->dval.p, n * ts, hipMemcpyDeviceToDevice, stream()));
+  const void* xv = cast_values(xc, uc, u->dval.p, n, xcast);
+  uint8_t th[16] = {0}; if (has_thunk) cast_scalar(kc, th, thunk->type->code, thunk->x);
+  userselect_run(op->name, op->defn, xc, kc, true, n, nullptr, nullptr, xv, u->dpres.as<uint8_t>(), th, tpres.as<uint8_t>());
+  vector_write_back(w, uc, tval, tpres, allow, accum, dv.replace, false);
+}
+
 static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v,
                          GrB_Descriptor desc, bool is_union) {
   need_device();
@@ -343,9 +366,9 @@ GrB_Info GxB_Vector_select(GrB_Vector w, const GrB_Vector mask, const GrB_Binary
   VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; if (!check_obj(op) || !check_obj(u)) return GrB_UNINITIALIZED_OBJECT;
   return guarded(w, [&] {
     need_device();
+    if (is_user(op)) { vec_select_user(w, mask, accum, op, u, thunk, desc); return; }
     const DescView dv(desc); const uint64_t n = w->n;
     if (u->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "select: vector sizes differ");
-    if (op->opcode == SEL_USER) not_implemented("user-defined select operator");
     DevBuf allow_buf; bool nothing = false;
     const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
     if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }

@@ -703,21 +703,23 @@ class Matrix:
     assign = assign_matrix
 
     def select(self, op, thunk=None, out=None, mask=None, accum=None, desc=None):
-        """`GxB_Matrix_select` with a built-in select operator name ("TRIL", ">0", ...) (reference: matrix.py:2042-2140)."""
-        opname = {"tril": "TRIL", "triu": "TRIU", "diag": "DIAG", "offdiag": "OFFDIAG", "nonzero": "NONZERO",
+        """`GxB_Matrix_select` with a built-in select operator name ("TRIL", ">0", ...) or a `@select_op` operator (reference: matrix.py:2042-2140)."""
+        user = isinstance(op, types.SelectOp)
+        opname = None if user else {"tril": "TRIL", "triu": "TRIU", "diag": "DIAG", "offdiag": "OFFDIAG", "nonzero": "NONZERO",
                   "!=0": "NONZERO", "==0": "EQ_ZERO", ">0": "GT_ZERO", ">=0": "GE_ZERO", "<0": "LT_ZERO", "<=0": "LE_ZERO",
                   "!=": "NE_THUNK", "==": "EQ_THUNK", ">": "GT_THUNK", ">=": "GE_THUNK", "<": "LT_THUNK", "<=": "LE_THUNK"}.get(op, op)
+        oph = C.c_void_p(op.get_op() if user else _capi.handle("GxB_" + opname))
         if out is None:
             out = Matrix.sparse(self.type, self.nrows, self.ncols)
         th = None
         if thunk is not None:
             th = C.c_void_p()
-            ttyp = types.INT64 if opname in ("TRIL", "TRIU", "DIAG", "OFFDIAG") else self.type
+            ttyp = op.thunk_type if user else (types.INT64 if opname in ("TRIL", "TRIU", "DIAG", "OFFDIAG") else self.type)
             check(lib.GxB_Scalar_new(C.byref(th), C.c_void_p(ttyp._h)))
             check(getattr(lib, "GxB_Scalar_setElement_" + ttyp.__name__)(th, ttyp._c(thunk)))
         mh, ah, dh = get_args(mask, accum, desc)
         try:
-            check(lib.GxB_Matrix_select(out._h, mh, ah, C.c_void_p(_capi.handle("GxB_" + opname)), self._h, th, dh), out)
+            check(lib.GxB_Matrix_select(out._h, mh, ah, oph, self._h, th, dh), out)
         finally:
             if th is not None:
                 lib.GxB_Scalar_free(C.byref(th))

@@ -61,6 +61,13 @@ class BinaryOp(_Op):
         return A.emult(B, self, *args, **kwargs)
 
 
+class SelectOp(_Op):
+    """A select operator object (the built-in ones are named by strings in `Matrix.select`; `@select_op` makes user-defined ones)."""
+
+    def __init__(self, cname, name, typ):
+        super().__init__("SelectOp", cname, name, typ)
+
+
 class Accum:
     """`with Accum(INT64.min): ...` — default accumulator (reference: pygraphblas/binaryop.py:80-101)."""
 

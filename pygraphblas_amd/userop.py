@@ -1,4 +1,4 @@
-"""User-defined unary and binary operators: `@unary_op(T)` / `@binary_op(T)`.
+"""User-defined unary, binary and select operators: `@unary_op(T)` / `@binary_op(T)` / `@select_op(T, thunk_type=None)`.
 
 Same names and call shape as the reference's decorators (pygraphblas/binaryop.py:137, unaryop.py:101).  The reference compiles the
 Python function with numba into a host function pointer; a HIP kernel cannot call one.  Here the function's AST is translated into
@@ -9,6 +9,14 @@ device at first use (grb_userop.cpp).  The result is used like a built-in operat
     @binary_op(FP32)
     def PLUS(x, y):
         return x + log1p(exp(y - x))
+
+`@select_op(T, thunk_type=None)` (reference: pygraphblas/selectop.py:103) makes a predicate over an entry's row, column, value and the thunk, for
+`A.select(op, thunk)` on `Matrix` and `Vector` (`GxB_SelectOp_new`): i and j are integers, x has the kind of T, v that of `thunk_type` (T when not given),
+and the returned value's truth decides whether the entry stays.
+
+    @select_op(FP64)
+    def band_above(i, j, x, v):
+        return abs(i - j) <= 2 and x > v
 
 The supported subset of Python (anything else raises `TypeError` at decoration time, naming the construct and its line):
 
@@ -36,7 +44,7 @@ from . import types
 from ._capi import lib
 from .base import check, _error_codes, GraphBLASException
 
-__all__ = ["unary_op", "binary_op", "UserUnaryOp", "UserBinaryOp", "translate"]
+__all__ = ["unary_op", "binary_op", "select_op", "UserUnaryOp", "UserBinaryOp", "UserSelectOp", "translate", "translate_select"]
 
 _CTYPE = {"BOOL": "bool", "INT8": "int8_t", "UINT8": "uint8_t", "INT16": "int16_t", "UINT16": "uint16_t", "INT32": "int32_t",
           "UINT32": "uint32_t", "INT64": "int64_t", "UINT64": "uint64_t", "FP32": "float", "FP64": "double"}
@@ -92,6 +100,7 @@ class _Translator:
         self.specs = {}            # (helper name, argument types) -> (C name, return type, text)
         self.order = []            # C texts of specialised helper functions, in dependency order
         self.active = []           # helpers being specialised (recursion check)
+        self.select = None         # a select operator: the C types (X, K) of its value and thunk
 
     def err(self, node, what):
         line = self.line0 + getattr(node, "lineno", 1) - 1
@@ -167,7 +176,9 @@ class _Translator:
                     self.err(st, "'return' without a value")
                 text, t = self.expr(st.value, ctx)
                 ctx["state"]["ret"] = _join(ctx["state"]["ret"], t)
-                if ctx["is_op"]:
+                if ctx["is_op"] and self.select:
+                    out.append(f"{pad}return ({text}) != 0;")
+                elif ctx["is_op"]:
                     out.append(f"{pad}{{ *z = ({self.ctype})({text}); return; }}")
                 else:
                     out.append(f"{pad}return {_cast(text, t, ctx['state']['ret'])};")
@@ -377,6 +388,12 @@ class _Translator:
         if ctype is None:
             out.append(f"static {_C[ret]} {cname}({', '.join(f'{_C[env[p]]} v_{p}' for p in params) or 'void'}) {{")
             skip = set(params)
+        elif self.select:
+            out.append(f"bool {cname}(GrB_Index i, GrB_Index j, const {self.select[0]} *x, const {self.select[1]} *thunk) {{")
+            skip = set()
+            for p, q in zip(params, ("i", "j", "*x", "*thunk")):
+                out.append(f"  {_C[env[p]]} v_{p} = ({_C[env[p]]})({q});")
+                skip.add(p)
         else:
             ptrs = ["x", "y"][:len(params)]
             out.append(f"void {cname}({ctype} *z, " + ", ".join(f"const {ctype} *{p}" for p in ptrs) + ") {")
@@ -392,30 +409,58 @@ class _Translator:
         return "\n".join(out)
 
 
-def translate(func, typ, nargs):
-    """The C definition (`defn` of GxB_UnaryOp_new / GxB_BinaryOp_new) of the Python function `func` as an operator on `typ`."""
+def _parse(func):
+    """(the function's `def` node, its first line, the names it can see, the int / float / bool constants among them)"""
     if not inspect.isfunction(func):
         raise TypeError("a user-defined operator is made from a plain Python function")
     try:
         lines, line0 = inspect.getsourcelines(func)
     except (OSError, TypeError) as e:
         raise TypeError(f"{getattr(func, '__name__', func)}: the function's source is not available ({e})")
-    tree = ast.parse(textwrap.dedent("".join(lines)))
-    if not tree.body or not isinstance(tree.body[0], ast.FunctionDef):
+    try:
+        tree = ast.parse(textwrap.dedent("".join(lines)))
+    except SyntaxError:                                                    # (a lambda inside a longer expression: its lines alone do not parse)
+        tree = None
+    if tree is None or not tree.body or not isinstance(tree.body[0], ast.FunctionDef):
         raise TypeError(f"{func.__name__}: a user-defined operator is made from a 'def' (not a lambda)")
-    fdef = tree.body[0]
     cv = inspect.getclosurevars(func)
     scope = dict(cv.builtins)
     scope.update(cv.globals)
     scope.update(cv.nonlocals)
     consts = {k: v for k, v in scope.items() if isinstance(v, (bool, int, float))}
-    base = "d" if typ.__name__ in ("FP32", "FP64") else "i"
+    return tree.body[0], line0, scope, consts
+
+
+def _base(typ):
+    return "d" if typ.__name__ in ("FP32", "FP64") else "i"
+
+
+def translate(func, typ, nargs):
+    """The C definition (`defn` of GxB_UnaryOp_new / GxB_BinaryOp_new) of the Python function `func` as an operator on `typ`."""
+    fdef, line0, scope, consts = _parse(func)
+    base = _base(typ)
     tr = _Translator(func, base, line0, consts)
     tr.scope, tr.top, tr.ctype = scope, fdef, _CTYPE[typ.__name__]
     if len(fdef.args.args) != nargs:
         tr.err(fdef, f"a function of {len(fdef.args.args)} parameter(s) as {'a unary' if nargs == 1 else 'a binary'} operator")
     env, _ret, body, params = tr.function(fdef, [base] * nargs, {})
     text = tr.emit(func.__name__, fdef, env, "i", body, params, _CTYPE[typ.__name__])
+    helpers = [h for name, h in _HELPERS if name in tr.used]
+    return "\n".join(helpers + tr.order + [text]) + "\n"
+
+
+def translate_select(func, typ, thunk_type=None):
+    """The C definition (`defn` of GxB_SelectOp_new) of the Python predicate `func(i, j, x, v)`: i and j integers, x a value of `typ`, v one of `thunk_type`
+    (`typ` when None); the truth of what it returns is the `bool` result."""
+    fdef, line0, scope, consts = _parse(func)
+    thunk_type = thunk_type or typ
+    tr = _Translator(func, _base(typ), line0, consts)
+    tr.scope, tr.top, tr.ctype = scope, fdef, "bool"
+    tr.select = (_CTYPE[typ.__name__], _CTYPE[thunk_type.__name__])
+    if len(fdef.args.args) != 4:
+        tr.err(fdef, f"a function of {len(fdef.args.args)} parameter(s) as a select operator (it takes four: i, j, x, thunk)")
+    env, _ret, body, params = tr.function(fdef, ["i", "i", _base(typ), _base(thunk_type)], {})
+    text = tr.emit(func.__name__, fdef, env, "i", body, params, "bool")
     helpers = [h for name, h in _HELPERS if name in tr.used]
     return "\n".join(helpers + tr.order + [text]) + "\n"
 
@@ -468,6 +513,21 @@ class UserBinaryOp(_UserOp, types.BinaryOp):
         self._setup("BinaryOp", func, typ, h, defn)
 
 
+class UserSelectOp(_UserOp, types.SelectOp):
+    """A select operator compiled from a Python predicate (`@select_op(T, thunk_type)`): `A.select(op, thunk)`."""
+    _free = staticmethod(lambda ref: lib.GxB_SelectOp_free(ref))
+
+    def __init__(self, func, typ, thunk_type=None, defn=None):
+        defn = defn if defn is not None else translate_select(func, typ, thunk_type)
+        h = C.c_void_p()
+        info = lib.GxB_SelectOp_new(C.byref(h), None, C.c_void_p(typ._h), C.c_void_p(thunk_type._h) if thunk_type is not None else None,
+                                    func.__name__.encode(), defn.encode())
+        if info:
+            _raise(info, "GxB_SelectOp_new")
+        self._setup("SelectOp", func, typ, h, defn)
+        self.thunk_type = thunk_type or typ
+
+
 def unary_op(arg_type):
     """Decorator: a Python function of one argument -> a `GrB_UnaryOp` on `arg_type` (reference: pygraphblas/unaryop.py:101)."""
     def inner(func):
@@ -480,4 +540,12 @@ def binary_op(arg_type, nopython=True):
     `nopython` is accepted for the reference's call shape and has no meaning here)."""
     def inner(func):
         return UserBinaryOp(func, arg_type)
+    return inner
+
+
+def select_op(arg_type, thunk_type=None):
+    """Decorator: a Python predicate `f(i, j, x, v)` -> a `GxB_SelectOp` on values of `arg_type` with a thunk of `thunk_type`
+    (`arg_type` when None) (reference: pygraphblas/selectop.py:103)."""
+    def inner(func):
+        return UserSelectOp(func, arg_type, thunk_type)
     return inner

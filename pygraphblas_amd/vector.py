@@ -318,19 +318,22 @@ class Vector:
         return out
 
     def select(self, op, thunk=None, out=None, mask=None, accum=None, desc=None):
-        """`GxB_Vector_select` with a built-in select operator name ("NONZERO", ">", ...) (reference: pygraphblas/vector.py:1354-1404)."""
-        opname = {"nonzero": "NONZERO", "!=0": "NONZERO", "==0": "EQ_ZERO", ">0": "GT_ZERO", ">=0": "GE_ZERO", "<0": "LT_ZERO", "<=0": "LE_ZERO",
+        """`GxB_Vector_select` with a built-in select operator name ("NONZERO", ">", ...) or a `@select_op` operator (reference: pygraphblas/vector.py:1354-1404)."""
+        user = isinstance(op, types.SelectOp)
+        opname = None if user else {"nonzero": "NONZERO", "!=0": "NONZERO", "==0": "EQ_ZERO", ">0": "GT_ZERO", ">=0": "GE_ZERO", "<0": "LT_ZERO", "<=0": "LE_ZERO",
                   "!=": "NE_THUNK", "==": "EQ_THUNK", ">": "GT_THUNK", ">=": "GE_THUNK", "<": "LT_THUNK", "<=": "LE_THUNK"}.get(op, op)
+        oph = C.c_void_p(op.get_op() if user else _capi.handle("GxB_" + opname))
         if out is None:
             out = Vector.sparse(self.type, self.size)
         th = None
         if thunk is not None:
             th = C.c_void_p()
-            check(lib.GxB_Scalar_new(C.byref(th), C.c_void_p(self.type._h)))
-            check(getattr(lib, "GxB_Scalar_setElement_" + self.type.__name__)(th, self.type._c(thunk)))
+            ttyp = op.thunk_type if user else self.type
+            check(lib.GxB_Scalar_new(C.byref(th), C.c_void_p(ttyp._h)))
+            check(getattr(lib, "GxB_Scalar_setElement_" + ttyp.__name__)(th, ttyp._c(thunk)))
         mh, ah, dh = get_args(mask, accum, desc)
         try:
-            check(lib.GxB_Vector_select(out._h, mh, ah, C.c_void_p(_capi.handle("GxB_" + opname)), self._h, th, dh), out)
+            check(lib.GxB_Vector_select(out._h, mh, ah, oph, self._h, th, dh), out)
         finally:
             if th is not None:
                 lib.GxB_Scalar_free(C.byref(th))

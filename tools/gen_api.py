@@ -367,13 +367,19 @@ GrB_Info GrB_Monoid_free(GrB_Monoid *monoid);
  * `fn` (a host function pointer) is never called and may be NULL.  All of the operator's types must be ONE of the 11 real built-in types
  * (GrB_DOMAIN_MISMATCH otherwise).  Such an operator runs in GrB_*_apply, GxB_*_apply_BinaryOp1st / 2nd, GrB_*_eWiseAdd_BinaryOp and
  * GrB_*_eWiseMult_BinaryOp on containers with an HBM layout; every other use returns GrB_DOMAIN_MISMATCH.  The function-pointer forms
- * GrB_UnaryOp_new / GrB_BinaryOp_new, GrB_Type_new and GxB_SelectOp_new do not exist (DESIGN.md section 8). */
+ * GrB_UnaryOp_new / GrB_BinaryOp_new and GrB_Type_new do not exist (DESIGN.md section 8).
+ * A user-defined select operator is the same for GxB_Matrix_select / GxB_Vector_select: `defn` defines the predicate
+ * "bool NAME (GrB_Index i, GrB_Index j, const X *x, const K *thunk) { ... }", X the C type of `xtype`, K of `ttype` (NULL: the same as `xtype`), both one of
+ * the 11 real built-in types; an entry is kept where it returns true (a vector's entry: i its position, j 0). */
 GrB_Info GxB_UnaryOp_new(GrB_UnaryOp *unaryop, void *function, GrB_Type ztype, GrB_Type xtype, const char *name, const char *defn);
 GrB_Info GxB_BinaryOp_new(GrB_BinaryOp *binaryop, void *function, GrB_Type ztype, GrB_Type xtype, GrB_Type ytype, const char *name, const char *defn);
 GrB_Info GrB_UnaryOp_free(GrB_UnaryOp *unaryop);     /* releases a user-defined operator and sets the variable to NULL; built-in handles are left alone */
 GrB_Info GrB_BinaryOp_free(GrB_BinaryOp *binaryop);
+GrB_Info GxB_SelectOp_new(GxB_SelectOp *selectop, void *function, GrB_Type xtype, GrB_Type ttype, const char *name, const char *defn);
+GrB_Info GxB_SelectOp_free(GxB_SelectOp *selectop);  /* releases a user-defined select operator and sets the variable to NULL; the built-in GxB_TRIL ... are left alone */
 GrB_Info GrBX_userop_stats(uint64_t *compiled, uint64_t *loaded_from_disk, uint64_t *launched); /* user-operator kernels compiled with hipRTC, loaded from the code-object cache on disk instead, and launches through them */
 GrB_Info GrBX_userop_source(const char *name, const char *defn, GrB_Type type, int kind, char *buf, size_t len); /* the kernel text compiled for such an operator in an operation of `kind` (0 apply, 1 bind1st, 2 bind2nd, 3 eadd, 4 emult) */
+GrB_Info GrBX_selectop_source(const char *name, const char *defn, GrB_Type xtype, GrB_Type ttype, int on_vector, char *buf, size_t len); /* the kernel text compiled for a select operator used on a matrix (on_vector 0) or a vector (1) */
 GrB_Info GrBX_Matrix_residency(const GrB_Matrix A, int *where);   /* which images of the container are valid: bit 0 the host mirror, bit 1 the HBM image (a look: nothing is moved, no deferred work completed) */
 GrB_Info GrBX_Vector_residency(const GrB_Vector v, int *where);
 GrB_Info GrBX_last_error(char *buf, int len);        /* the message of the calling thread's most recent failure (for calls that have no container to ask: GxB_*Op_new, GrB_Monoid_new_*, GrB_Semiring_new) */
