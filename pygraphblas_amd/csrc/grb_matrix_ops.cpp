@@ -35,6 +35,29 @@ struct CsrView { const DevCSR* m; DevBuf vals; const void* v; };
 // device CSR of op(A) with values cast to `code` (or untouched when `need_vals` is false)
 const DevCSR& operand(GrB_Matrix A, bool transpose) { mat_to_device(A); return transpose ? mat_csc(A) : A->csr; }
 
+// the dimensions of op(A)
+struct Dims { uint64_t r, c; };
+Dims op_dims(GrB_Matrix A, bool transpose) { return transpose ? Dims{A->ncols, A->nrows} : Dims{A->nrows, A->ncols}; }
+// C and the mask are d.r x d.c, or GrB_DIMENSION_MISMATCH with the caller's own message
+void conform(GrB_Matrix C, GrB_Matrix M, Dims d, const char* msg) {
+  if (C->nrows != d.r || C->ncols != d.c || (M && (M->nrows != d.r || M->ncols != d.c))) fail(GrB_DIMENSION_MISMATCH, msg);
+}
+// no mask + complement: nothing may be written (C is cleared under replace), and the caller returns
+bool nothing_to_write(GrB_Matrix C, GrB_Matrix M, const DescView& dv) {
+  if (M || !dv.mask_comp) return false;
+  if (dv.replace) GrB_Matrix_clear(C);
+  return true;
+}
+// T has S's pattern (row pointers and columns copied) and a fresh value array of `val_bytes` (+ 16: the kernels of user-defined operators store whole packs)
+DevCSR pattern_copy(const DevCSR& S, size_t val_bytes) {
+  DevCSR T; T.nrows = S.nrows; T.ncols = S.ncols; T.nnz = S.nnz;
+  T.rowptr.alloc(((size_t)S.nrows + 1) * 4); T.col.alloc(S.nnz * 4 + 4); T.val.alloc(val_bytes + 16);
+  GRB_HIP(hipMemcpyAsync(T.rowptr.p, S.rowptr.p, ((size_t)S.nrows + 1) * 4, hipMemcpyDeviceToDevice, stream()));
+  if (S.nnz) GRB_HIP(hipMemcpyAsync(T.col.p, S.col.p, S.nnz * 4, hipMemcpyDeviceToDevice, stream()));
+  T.valid = true;
+  return T;
+}
+
 void adopt(GrB_Matrix C, DevCSR& T, int tcode) {
   // C becomes exactly T (cast values if the types differ)
   if (tcode != C->type->code && T.nnz) { DevBuf c(T.nnz * C->type->size); vec_cast_values(C->type->code, c.p, tcode, T.val.p, T.nnz); T.val = std::move(c); }
@@ -50,10 +73,7 @@ void adopt(GrB_Matrix C, DevCSR& T, int tcode) {
 // C<M,replace> = accum(C, T).  `t_masked`: T already has no entry the mask forbids.  (Declared in grb_extract.hpp: the extract entry points of grb_host_ops.cpp end in it too.)
 void grb::matrix_write_back(GrB_Matrix C, DevCSR& T, int tcode, GrB_Matrix M, const DescView& dv, GrB_BinaryOp accum, bool t_masked) {
   if (accum) check_binop(accum, "accum");
-  if (!M && dv.mask_comp) {      // no mask + complement: nothing may be written
-    if (dv.replace) GrB_Matrix_clear(C);
-    return;
-  }
+  if (nothing_to_write(C, M, dv)) return;
   const bool c_empty = mat_nvals(C) == 0;
   if (!accum && (!M || (t_masked && (dv.replace || c_empty)))) { adopt(C, T, tcode); return; }
   if (!accum && M && (dv.replace || c_empty)) {
@@ -89,12 +109,12 @@ void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semirin
   if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mxm(C, M, accum, semiring, A, B, desc); return; }   // dimensions beyond the device layouts
   check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm");
   const DescView dv(desc);
-  const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
-  const uint64_t br = dv.tran1 ? B->ncols : B->nrows, bc = dv.tran1 ? B->nrows : B->ncols;
-  if (ac != br || C->nrows != ar || C->ncols != bc || (M && (M->nrows != ar || M->ncols != bc))) fail(GrB_DIMENSION_MISMATCH, "mxm: dimensions do not conform");
+  const Dims a = op_dims(A, dv.tran0), b = op_dims(B, dv.tran1);
+  if (a.c != b.r) fail(GrB_DIMENSION_MISMATCH, "mxm: dimensions do not conform");
+  conform(C, M, {a.r, b.c}, "mxm: dimensions do not conform");
   SemiringDesc sd = make_semiring_desc(semiring, false);
   g_last_plan.clear();
-  if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
+  if (nothing_to_write(C, M, dv)) return;
   // a batch of a few very long rows times a large matrix (the BC sweeps' frontier products): the rows of the batch's BITMAP through GrB_vxm, the result a bitmap
   if (!dv.tran0 && mat_batch_shape(A->nrows, A->ncols, A->type->code) && mat_batch_shape(C->nrows, C->ncols, C->type->code) && (!M || mat_batch_shape(M->nrows, M->ncols, M->type->code)) &&
       !is_hyper(B) && A != B && M != B) {
@@ -142,63 +162,39 @@ void do_transpose(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Matrix A, 
   const DescView dv(desc);
   // desc.INP0 = TRAN transposes the input first: the result is then A itself
   const bool tr = !dv.tran0;
-  const uint64_t r = tr ? A->ncols : A->nrows, c = tr ? A->nrows : A->ncols;
-  if (C->nrows != r || C->ncols != c || (M && (M->nrows != r || M->ncols != c))) fail(GrB_DIMENSION_MISMATCH, "transpose: dimensions do not conform");
+  conform(C, M, op_dims(A, tr), "transpose: dimensions do not conform");
   const DevCSR& S = operand(A, tr);
-  DevCSR T; const size_t ts = A->type->size;
-  T.nrows = S.nrows; T.ncols = S.ncols; T.nnz = S.nnz;
-  T.rowptr.alloc(((size_t)S.nrows + 1) * 4); T.col.alloc(S.nnz * 4 + 4); T.val.alloc(S.nnz * ts + 8);
-  GRB_HIP(hipMemcpyAsync(T.rowptr.p, S.rowptr.p, ((size_t)S.nrows + 1) * 4, hipMemcpyDeviceToDevice, stream()));
-  if (S.nnz) { GRB_HIP(hipMemcpyAsync(T.col.p, S.col.p, S.nnz * 4, hipMemcpyDeviceToDevice, stream()));
-               GRB_HIP(hipMemcpyAsync(T.val.p, S.val.p, S.nnz * ts, hipMemcpyDeviceToDevice, stream())); }
-  T.valid = true;
+  const size_t ts = A->type->size;
+  DevCSR T = pattern_copy(S, S.nnz * ts);
+  if (S.nnz) GRB_HIP(hipMemcpyAsync(T.val.p, S.val.p, S.nnz * ts, hipMemcpyDeviceToDevice, stream()));
   matrix_write_back(C, T, A->type->code, M, dv, accum, false);
 }
 
-// a user-defined operator (grb_userop.cpp) has no HBM-less route: hypersparse and complex containers are refused, naming the operator
-void user_needs_layout(const char* opname, bool hyper, bool cplx) {
-  if (hyper) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": hypersparse containers (a dimension beyond the device layout) are out of its scope");
-  if (cplx) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": complex containers are out of its scope");
-}
-
-// eWiseAdd / eWiseMult with a user-defined operator: the merge of the two patterns moves both operands' values to the output's positions
-// (csr_ewise_aligned), the operator's compiled kernel streams over them, the write-back is the one of every other operation
-void do_ewise_user(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, bool is_union) {
-  user_needs_layout(op->name, is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B),
-                    C->type->code >= T_FC32 || A->type->code >= T_FC32 || B->type->code >= T_FC32 || (M && M->type->code >= T_FC32));
-  if (accum) check_binop(accum, "accum");
-  const DescView dv(desc);
-  const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
-  const uint64_t br = dv.tran1 ? B->ncols : B->nrows, bc = dv.tran1 ? B->nrows : B->ncols;
-  if (ar != br || ac != bc || C->nrows != ar || C->ncols != ac || (M && (M->nrows != ar || M->ncols != ac))) fail(GrB_DIMENSION_MISMATCH, "eWise: dimensions do not conform");
-  if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
-  const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);
-  const int xc = op->xtype->code;
-  DevBuf acast, bcast, xv, yv, both;
-  const void* av = cast_values(xc, A->type->code, Ad.val.p, Ad.nnz, acast);
-  const void* bv = cast_values(xc, B->type->code, Bd.val.p, Bd.nnz, bcast);
-  DevCSR T;
-  csr_ewise_aligned(xc, Ad, av, Bd, bv, is_union, T, xv, yv, both);
-  userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, T.nnz, xv.p, nullptr, yv.p, nullptr, is_union ? both.as<uint8_t>() : nullptr, nullptr, T.val.p, nullptr);
-  matrix_write_back(C, T, xc, M, dv, accum, false);
-}
-
+// eWiseAdd / eWiseMult.  A user-defined operator (grb_userop.cpp) has no HBM-less route — hypersparse and complex containers are refused, naming it — and no
+// batch routes: the merge of the two patterns moves both operands' values to the output's positions (csr_ewise_aligned) and its compiled kernel streams over
+// them, where a built-in operator's csr_ewise merges and computes in one pass.
 void do_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, bool is_union) {
   need_device(); check_mat(A, "eWise"); check_mat(B, "eWise"); if (M) check_mat(M, "eWise");
-  if (check_obj(op) && is_user(op)) { do_ewise_user(C, M, accum, op, A, B, desc, is_union); return; }
-  check_binop(op, "eWise");
-  if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mat_ewise(C, M, accum, op, A, B, desc, is_union); return; }
+  const bool user = check_obj(op) && is_user(op);
+  if (user) {
+    user_needs_layout(op->name, "dimension", is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B),
+                      C->type->code >= T_FC32 || A->type->code >= T_FC32 || B->type->code >= T_FC32 || (M && M->type->code >= T_FC32));
+    if (accum) check_binop(accum, "accum");
+  } else {
+    check_binop(op, "eWise");
+    if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mat_ewise(C, M, accum, op, A, B, desc, is_union); return; }
+  }
   const DescView dv(desc);
-  const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
-  const uint64_t br = dv.tran1 ? B->ncols : B->nrows, bc = dv.tran1 ? B->nrows : B->ncols;
-  if (ar != br || ac != bc || C->nrows != ar || C->ncols != ac || (M && (M->nrows != ar || M->ncols != ac))) fail(GrB_DIMENSION_MISMATCH, "eWise: dimensions do not conform");
-  if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
-  if (!dv.tran0 && !dv.tran1 && batch_wanted(C, mat_nvals(A) + mat_nvals(B)) && A->type->code < T_FC32 && B->type->code < T_FC32 && (!M || M->type->code < T_FC32)) {
+  const Dims a = op_dims(A, dv.tran0), b = op_dims(B, dv.tran1);
+  if (a.r != b.r || a.c != b.c) fail(GrB_DIMENSION_MISMATCH, "eWise: dimensions do not conform");
+  conform(C, M, a, "eWise: dimensions do not conform");
+  if (nothing_to_write(C, M, dv)) return;
+  if (!user && !dv.tran0 && !dv.tran1 && batch_wanted(C, mat_nvals(A) + mat_nvals(B)) && A->type->code < T_FC32 && B->type->code < T_FC32 && (!M || M->type->code < T_FC32)) {
     if (accum) check_binop(accum, "accum");
     ewise_batch(C, M, dv, accum, op, A, B, is_union); return;      // a batch of a few very long rows (BC sweeps): its bitmap as ONE vector through the vector kernel
   }
   const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);
-  if (few_long_rows(C->nrows, C->ncols, Ad.nnz + Bd.nnz)) {          // a batch of a few very long rows (BC sweeps): row by row through the vector kernels
+  if (!user && few_long_rows(C->nrows, C->ncols, Ad.nnz + Bd.nnz)) {          // a batch of a few very long rows (BC sweeps): row by row through the vector kernels
     DevCSR T; ewise_few_rows(C, M, dv, accum, op, Ad, A->type, Bd, B->type, is_union, T);
     adopt(C, T, C->type->code); return;
   }
@@ -207,102 +203,78 @@ void do_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, G
   const void* av = cast_values(xc, A->type->code, Ad.val.p, Ad.nnz, acast);
   const void* bv = cast_values(xc, B->type->code, Bd.val.p, Bd.nnz, bcast);
   DevCSR T;
-  csr_ewise(xc, Ad, av, Bd, bv, op->opcode, is_union, T);
+  if (user) {
+    DevBuf xv, yv, both;
+    csr_ewise_aligned(xc, Ad, av, Bd, bv, is_union, T, xv, yv, both);
+    userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, T.nnz, xv.p, nullptr, yv.p, nullptr, is_union ? both.as<uint8_t>() : nullptr, nullptr, T.val.p, nullptr);
+  } else {
+    csr_ewise(xc, Ad, av, Bd, bv, op->opcode, is_union, T);
+  }
   matrix_write_back(C, T, xc, M, dv, accum, false);
 }
 
-// mode 0 unary, 1 bind-first, 2 bind-second
-void do_apply(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, int mode, int opcode, int xcode, const void* scalar, int scode, GrB_Matrix A, GrB_Descriptor desc) {
+// apply, and apply with a bound scalar (the ElemOp's mode).  A user-defined operator is refused on containers without an HBM layout and has its accumulator
+// looked at first; the positional operators and the bitmap batch route exist for built-in operators only.
+void do_apply(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const ElemOp& op, const void* scalar, int scode, GrB_Matrix A, GrB_Descriptor desc) {
   need_device(); check_mat(A, "apply"); if (M) check_mat(M, "apply");
+  if (op.user()) {
+    user_needs_layout(op.name, "dimension", is_hyper(C) || is_hyper(M) || is_hyper(A),
+                      C->type->code >= T_FC32 || A->type->code >= T_FC32 || (M && M->type->code >= T_FC32) || scode >= T_FC32);
+    if (accum) check_binop(accum, "accum");
+  }
   const DescView dv(desc);
-  const uint64_t r = dv.tran0 ? A->ncols : A->nrows, c = dv.tran0 ? A->nrows : A->ncols;
-  if (C->nrows != r || C->ncols != c || (M && (M->nrows != r || M->ncols != c))) fail(GrB_DIMENSION_MISMATCH, "apply: dimensions do not conform");
-  if (mode == 0 && opcode >= U_POSITIONI && opcode <= U_POSITIONJ1) {      // positional: T has op(A)'s pattern, the values are the entries' row / column indices in the operator's type
-    if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
+  conform(C, M, op_dims(A, dv.tran0), "apply: dimensions do not conform");
+  const bool positional = !op.user() && op.mode == 0 && op.opcode >= U_POSITIONI && op.opcode <= U_POSITIONJ1;
+  if ((op.user() || positional) && nothing_to_write(C, M, dv)) return;      // (every other built-in operator: the write-back finds it, after the accumulator)
+  if (positional) {      // T has op(A)'s pattern, the values are the entries' row / column indices in the operator's type
     const DevCSR& S = operand(A, dv.tran0);
-    DevCSR T; T.nrows = S.nrows; T.ncols = S.ncols; T.nnz = S.nnz;
-    T.rowptr.alloc(((size_t)S.nrows + 1) * 4); T.col.alloc(S.nnz * 4 + 4); T.val.alloc(S.nnz * type_size(xcode) + 8);
-    GRB_HIP(hipMemcpyAsync(T.rowptr.p, S.rowptr.p, ((size_t)S.nrows + 1) * 4, hipMemcpyDeviceToDevice, stream()));
-    if (S.nnz) GRB_HIP(hipMemcpyAsync(T.col.p, S.col.p, S.nnz * 4, hipMemcpyDeviceToDevice, stream()));
-    csr_position_values(xcode, S, opcode - U_POSITIONI, T.val.p);
-    T.valid = true;
-    matrix_write_back(C, T, xcode, M, dv, accum, false);
+    DevCSR T = pattern_copy(S, S.nnz * type_size(op.xcode));
+    csr_position_values(op.xcode, S, op.opcode - U_POSITIONI, T.val.p);
+    matrix_write_back(C, T, op.xcode, M, dv, accum, false);
     return;
   }
-  if (!M && !accum && !dv.mask_comp && !dv.tran0 && A->bm.valid && !A->host_valid && batch_wanted(C, mat_nvals(A)) && A->type->code < T_FC32) {      // a batch that lives as a bitmap stays one
-    uint8_t s16[16] = {0}; if (scalar) cast_scalar(xcode, s16, scode, scalar);
-    apply_batch(C, mode, opcode, xcode, s16, A); return;
+  uint8_t s[16] = {0}; if (scalar) cast_scalar(op.xcode, s, scode, scalar);
+  if (!op.user() && !M && !accum && !dv.mask_comp && !dv.tran0 && A->bm.valid && !A->host_valid && batch_wanted(C, mat_nvals(A)) && A->type->code < T_FC32) {      // a batch that lives as a bitmap stays one
+    apply_batch(C, op.mode, op.opcode, op.xcode, s, A); return;
   }
   const DevCSR& S = operand(A, dv.tran0);
-  DevCSR T; T.nrows = S.nrows; T.ncols = S.ncols; T.nnz = S.nnz;
-  T.rowptr.alloc(((size_t)S.nrows + 1) * 4); T.col.alloc(S.nnz * 4 + 4); T.val.alloc(S.nnz * type_size(xcode) + 8);
-  GRB_HIP(hipMemcpyAsync(T.rowptr.p, S.rowptr.p, ((size_t)S.nrows + 1) * 4, hipMemcpyDeviceToDevice, stream()));
-  if (S.nnz) GRB_HIP(hipMemcpyAsync(T.col.p, S.col.p, S.nnz * 4, hipMemcpyDeviceToDevice, stream()));
-  DevBuf ac; const void* av = cast_values(xcode, A->type->code, S.val.p, S.nnz, ac);
-  uint8_t s[16] = {0}; if (scalar) cast_scalar(xcode, s, scode, scalar);
-  vec_apply(xcode, S.nnz, av, nullptr, mode, opcode, s, T.val.p, nullptr);
-  T.valid = true;
-  matrix_write_back(C, T, xcode, M, dv, accum, false);
+  DevCSR T = pattern_copy(S, S.nnz * type_size(op.xcode));
+  DevBuf ac; const void* av = cast_values(op.xcode, A->type->code, S.val.p, S.nnz, ac);
+  elem_eval(op, S.nnz, av, nullptr, s, T.val.p, nullptr);
+  matrix_write_back(C, T, op.xcode, M, dv, accum, false);
 }
 
-// apply with a user-defined operator: kind UK_APPLY (unary) or UK_BIND1ST / UK_BIND2ND (binary with a bound scalar)
-void do_apply_user(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, int kind, const char* name, const char* defn, int xcode, const void* scalar, int scode, GrB_Matrix A, GrB_Descriptor desc) {
-  need_device(); check_mat(A, "apply"); if (M) check_mat(M, "apply");
-  user_needs_layout(name, is_hyper(C) || is_hyper(M) || is_hyper(A), C->type->code >= T_FC32 || A->type->code >= T_FC32 || (M && M->type->code >= T_FC32) || scode >= T_FC32);
-  if (accum) check_binop(accum, "accum");
-  const DescView dv(desc);
-  const uint64_t r = dv.tran0 ? A->ncols : A->nrows, c = dv.tran0 ? A->nrows : A->ncols;
-  if (C->nrows != r || C->ncols != c || (M && (M->nrows != r || M->ncols != c))) fail(GrB_DIMENSION_MISMATCH, "apply: dimensions do not conform");
-  if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
-  const DevCSR& S = operand(A, dv.tran0);
-  DevCSR T; T.nrows = S.nrows; T.ncols = S.ncols; T.nnz = S.nnz;
-  T.rowptr.alloc(((size_t)S.nrows + 1) * 4); T.col.alloc(S.nnz * 4 + 4); T.val.alloc(S.nnz * type_size(xcode) + 16);
-  GRB_HIP(hipMemcpyAsync(T.rowptr.p, S.rowptr.p, ((size_t)S.nrows + 1) * 4, hipMemcpyDeviceToDevice, stream()));
-  if (S.nnz) GRB_HIP(hipMemcpyAsync(T.col.p, S.col.p, S.nnz * 4, hipMemcpyDeviceToDevice, stream()));
-  DevBuf ac; const void* av = cast_values(xcode, A->type->code, S.val.p, S.nnz, ac);
-  uint8_t s[16] = {0}; if (scalar) cast_scalar(xcode, s, scode, scalar);
-  userop_run(kind, name, defn, xcode, S.nnz, av, nullptr, nullptr, nullptr, nullptr, s, T.val.p, nullptr);
-  T.valid = true;
-  matrix_write_back(C, T, xcode, M, dv, accum, false);
-}
-
-// select with a user-defined operator: the predicate's compiled kernel writes the keep bytes over op(A)'s entries (their row indices expanded, the values cast
-// into the operator's type FOR THE PREDICATE ONLY: T keeps A's own values and type), then the compaction and write-back of every select.  Never queued.
-void do_select_user(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GxB_SelectOp op, GrB_Matrix A, GxB_Scalar thunk, GrB_Descriptor desc) {
-  const bool has_thunk = thunk && check_obj(thunk) && thunk->has;
-  user_needs_layout(op->name, is_hyper(C) || is_hyper(M) || is_hyper(A),
-                    C->type->code >= T_FC32 || A->type->code >= T_FC32 || (M && M->type->code >= T_FC32) || (has_thunk && thunk->type->code >= T_FC32));
-  if (accum) check_binop(accum, "accum");
-  const DescView dv(desc);
-  const uint64_t r = dv.tran0 ? A->ncols : A->nrows, c = dv.tran0 ? A->nrows : A->ncols;
-  if (C->nrows != r || C->ncols != c || (M && (M->nrows != r || M->ncols != c))) fail(GrB_DIMENSION_MISMATCH, "select: dimensions do not conform");
-  lazy_flush();
-  if (!M && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }
-  const DevCSR& S = operand(A, dv.tran0);           // (a transposed input: i and j are those of the transposed matrix)
-  const int acode = A->type->code, xc = op->xtype->code, kc = op->ttype->code;
-  DevBuf rowidx(S.nnz * 4 + 16), keep(S.nnz + 16), xcast; DevCSR T;
-  csr_row_indices(S, rowidx.as<uint32_t>());
-  const void* xv = cast_values(xc, acode, S.val.p, S.nnz, xcast);
-  uint8_t th[16] = {0}; if (has_thunk) cast_scalar(kc, th, thunk->type->code, thunk->x);      // (no thunk, or an empty one: the zero of the thunk type)
-  userselect_run(op->name, op->defn, xc, kc, false, S.nnz, rowidx.as<uint32_t>(), S.col.as<uint32_t>(), xv, nullptr, th, keep.as<uint8_t>());
-  csr_compact(S, S.val.p, A->type->size, keep.as<uint8_t>(), T);
-  matrix_write_back(C, T, acode, M, dv, accum, false);
-}
-
+// select: the keep bytes over op(A)'s entries, then the compaction (T keeps A's own values and type) and the write-back.  A built-in operator makes the keep bytes
+// from the positions or the values; a user-defined one with its compiled kernel, over the entries' row indices expanded and the values cast into the operator's
+// type FOR THE PREDICATE ONLY — it is refused on containers without an HBM layout, has its accumulator looked at first and is never queued.
 void do_select(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GxB_SelectOp op, GrB_Matrix A, GxB_Scalar thunk, GrB_Descriptor desc) {
   need_device(); check_mat(A, "select"); if (M) check_mat(M, "select");
   if (!check_obj(op)) fail(GrB_UNINITIALIZED_OBJECT, "select: operator");
-  if (is_user(op)) { do_select_user(C, M, accum, op, A, thunk, desc); return; }
+  const bool user = is_user(op), has_thunk = thunk && check_obj(thunk) && thunk->has;
+  if (user) {
+    user_needs_layout(op->name, "dimension", is_hyper(C) || is_hyper(M) || is_hyper(A),
+                      C->type->code >= T_FC32 || A->type->code >= T_FC32 || (M && M->type->code >= T_FC32) || (has_thunk && thunk->type->code >= T_FC32));
+    if (accum) check_binop(accum, "accum");
+  }
   const DescView dv(desc);
-  const uint64_t r = dv.tran0 ? A->ncols : A->nrows, c = dv.tran0 ? A->nrows : A->ncols;
-  if (C->nrows != r || C->ncols != c || (M && (M->nrows != r || M->ncols != c))) fail(GrB_DIMENSION_MISMATCH, "select: dimensions do not conform");
-  const DevCSR& S = operand(A, dv.tran0);
+  conform(C, M, op_dims(A, dv.tran0), "select: dimensions do not conform");
+  if (user) { lazy_flush(); if (nothing_to_write(C, M, dv)) return; }
+  const DevCSR& S = operand(A, dv.tran0);           // (a transposed input: i and j are those of the transposed matrix)
   const int acode = A->type->code;
-  int64_t k = 0; uint8_t th[16] = {0};
-  if (thunk && check_obj(thunk) && thunk->has) { cast_scalar(T_INT64, &k, thunk->type->code, thunk->x); cast_scalar(acode, th, thunk->type->code, thunk->x); }
-  DevBuf keep(S.nnz + 1); DevCSR T;
-  if (op->opcode <= SEL_OFFDIAG) select_positional_flags(S, op->opcode, k, keep.as<uint8_t>());
-  else select_value_flags(acode, S.nnz, S.val.p, nullptr, op->opcode, th, keep.as<uint8_t>());
+  DevBuf keep(S.nnz + 16); DevCSR T;
+  int64_t k = 0; uint8_t th[16] = {0};      // the thunk as a diagonal, and in the type it is compared in (no thunk, or an empty one: zero)
+  if (user) {
+    const int xc = op->xtype->code, kc = op->ttype->code;
+    DevBuf rowidx(S.nnz * 4 + 16), xcast;
+    csr_row_indices(S, rowidx.as<uint32_t>());
+    const void* xv = cast_values(xc, acode, S.val.p, S.nnz, xcast);
+    if (has_thunk) cast_scalar(kc, th, thunk->type->code, thunk->x);
+    userselect_run(op->name, op->defn, xc, kc, false, S.nnz, rowidx.as<uint32_t>(), S.col.as<uint32_t>(), xv, nullptr, th, keep.as<uint8_t>());
+  } else {
+    if (has_thunk) { cast_scalar(T_INT64, &k, thunk->type->code, thunk->x); cast_scalar(acode, th, thunk->type->code, thunk->x); }
+    if (op->opcode <= SEL_OFFDIAG) select_positional_flags(S, op->opcode, k, keep.as<uint8_t>());
+    else select_value_flags(acode, S.nnz, S.val.p, nullptr, op->opcode, th, keep.as<uint8_t>());
+  }
   csr_compact(S, S.val.p, A->type->size, keep.as<uint8_t>(), T);
   matrix_write_back(C, T, acode, M, dv, accum, false);
 }
@@ -312,11 +284,9 @@ void do_reduce_vector(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Mon
   if (!check_obj(monoid)) fail(GrB_UNINITIALIZED_OBJECT, "reduce: monoid"); check_binop(monoid->op, "monoid");
   if (mask && !check_obj(mask)) fail(GrB_UNINITIALIZED_OBJECT, "reduce: mask");
   const DescView dv(desc);
-  const uint64_t r = dv.tran0 ? A->ncols : A->nrows;
-  if (w->n != r || (mask && mask->n != r)) fail(GrB_DIMENSION_MISMATCH, "reduce: dimensions do not conform");
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, r, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  const uint64_t r = op_dims(A, dv.tran0).r;
+  DevBuf allow_buf; const uint8_t* allow;
+  if (vector_prelude(w, mask, dv, r, {}, "reduce: dimensions do not conform", false, allow_buf, allow)) return;
   const int mc = monoid->op->ztype->code;
   DevBuf ac, tval(r * type_size(mc) + 8), tpres(r + 1);
   // the columns of a large matrix whose transpose is not at hand (desc T0 on a by-row matrix): no transpose is built for this, every
@@ -357,7 +327,7 @@ void do_assign_scalar(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const void
   if (C->nrows > GRB_DIM_DEVICE_MAX || C->ncols > GRB_DIM_DEVICE_MAX || C->type->code >= T_FC32) { host_assign_scalar(C, M, accum, x, xcode, I, ni, J, nj, desc); return; }
   need_device(); if (M) check_mat(M, "assign");
   const DescView dv(desc);
-  if (M && (M->nrows != C->nrows || M->ncols != C->ncols)) fail(GrB_DIMENSION_MISMATCH, "assign: mask dimensions");
+  conform(C, M, {C->nrows, C->ncols}, "assign: mask dimensions");
   if (I == GrB_ALL && J == GrB_ALL && !M && !accum && !dv.mask_comp && C->nrows * C->ncols <= 0xFFFFFFF0ull && C->nrows * C->ncols > 0) {
     // every position of C: the full one-valued matrix, written by one kernel (`Matrix.dense`, `M[:, :] = x`)
     uint8_t s0[16]; cast_scalar(C->type->code, s0, xcode, x);
@@ -422,8 +392,7 @@ GrB_Info GrB_Matrix_eWiseMult_Semiring(GrB_Matrix C, const GrB_Matrix M, const G
   MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->mul, A, B, desc, false); }); }
 GrB_Info GrB_Matrix_apply(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_UnaryOp op, const GrB_Matrix A, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
-  return guarded(C, [&] { if (is_user(op)) { do_apply_user(C, M, accum, UK_APPLY, op->name, op->defn, op->xtype->code, nullptr, 0, A, desc); return; }
-                          do_apply(C, M, accum, 0, op->opcode, op->xtype->code, nullptr, 0, A, desc); });
+  return guarded(C, [&] { do_apply(C, M, accum, elem_op(op), nullptr, 0, A, desc); });
 }
 GrB_Info GxB_Matrix_select(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GxB_SelectOp op, const GrB_Matrix A, const GxB_Scalar thunk, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { do_select(C, M, accum, op, A, thunk, desc); });
@@ -437,11 +406,9 @@ GrB_Info GrB_Matrix_reduce_Monoid(GrB_Vector w, const GrB_Vector mask, const GrB
   GrB_Info GrB_Matrix_assign_##SUF(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, CT x, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, const GrB_Descriptor desc) { \
     MAT_GUARD(C); return guarded(C, [&] { do_assign_scalar(C, M, accum, &x, CODE, I, ni, J, nj, desc); }); } \
   GrB_Info GxB_Matrix_apply_BinaryOp1st_##SUF(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_BinaryOp op, CT x, const GrB_Matrix A, const GrB_Descriptor desc) { \
-    MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { if (check_obj(op) && is_user(op)) { do_apply_user(C, M, accum, UK_BIND1ST, op->name, op->defn, op->xtype->code, &x, CODE, A, desc); return; } \
-                                                                            check_binop(op, "apply"); do_apply(C, M, accum, 1, op->opcode, op->xtype->code, &x, CODE, A, desc); }); } \
+    MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { do_apply(C, M, accum, elem_op(op, 1), &x, CODE, A, desc); }); } \
   GrB_Info GxB_Matrix_apply_BinaryOp2nd_##SUF(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, CT y, const GrB_Descriptor desc) { \
-    MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { if (check_obj(op) && is_user(op)) { do_apply_user(C, M, accum, UK_BIND2ND, op->name, op->defn, op->xtype->code, &y, CODE, A, desc); return; } \
-                                                                            check_binop(op, "apply"); do_apply(C, M, accum, 2, op->opcode, op->xtype->code, &y, CODE, A, desc); }); }
+    MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; return guarded(C, [&] { do_apply(C, M, accum, elem_op(op, 2), &y, CODE, A, desc); }); }
 GRB_TYPED_MATOPS(BOOL, bool, T_BOOL) GRB_TYPED_MATOPS(INT8, int8_t, T_INT8) GRB_TYPED_MATOPS(UINT8, uint8_t, T_UINT8)
 GRB_TYPED_MATOPS(INT16, int16_t, T_INT16) GRB_TYPED_MATOPS(UINT16, uint16_t, T_UINT16) GRB_TYPED_MATOPS(INT32, int32_t, T_INT32)
 GRB_TYPED_MATOPS(UINT32, uint32_t, T_UINT32) GRB_TYPED_MATOPS(INT64, int64_t, T_INT64) GRB_TYPED_MATOPS(UINT64, uint64_t, T_UINT64)

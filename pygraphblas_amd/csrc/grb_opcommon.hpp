@@ -1,11 +1,13 @@
 // grb_opcommon.hpp — pieces every GraphBLAS operation driver shares: operator validation, operand
-// typecasts into the operator's domain, mask -> allow bytes, and the final
-// C<M,replace> = accum(C, T) write-back for vectors.
+// typecasts into the operator's domain, the operator of an element-wise step (ElemOp), mask -> allow bytes and the
+// vector operations' prelude, and the final C<M,replace> = accum(C, T) write-back for vectors.
 #pragma once
 #include "grb_api.hpp"
 #include "grb_device.hpp"
 #include "grb_semiring.hpp"
 #include "grb_userop.hpp"
+#include "grb_lazy.hpp"
+#include <initializer_list>
 #include <vector>
 
 namespace grb {
@@ -19,6 +21,24 @@ inline void check_binop(GrB_BinaryOp op, const char* what) {
   if (is_user(op)) userop_refuse(op->name, what);
   if (op->opcode >= B_FIRSTI) not_implemented(std::string("positional / user-defined operator ") + op->name);
   if (op->xtype != op->ytype) not_implemented(std::string("mixed-type operator ") + op->name);
+}
+
+// The operator of an element-wise step — GrB_apply, GxB_apply_BinaryOp1st / 2nd — built-in or user-defined alike: what the drivers need of a GrB_UnaryOp, or
+// of a GrB_BinaryOp with one operand bound.  mode: 0 unary, 1 z = f(s, x), 2 z = f(x, s) — the numbers of UK_APPLY / UK_BIND1ST / UK_BIND2ND.
+struct ElemOp {
+  int mode, opcode, xcode, zcode; const char* name; const char* defn;
+  bool user() const { return opcode >= (mode == 0 ? (int)U_USER : (int)B_USER); }
+};
+inline ElemOp elem_op(GrB_UnaryOp op) { return {0, op->opcode, op->xtype->code, op->ztype->code, op->name, op->defn}; }      // (the entry points have checked the handle)
+inline ElemOp elem_op(GrB_BinaryOp op, int mode) {
+  if (!(check_obj(op) && is_user(op))) check_binop(op, "apply");
+  return {mode, op->opcode, op->xtype->code, op->ztype->code, op->name, op->defn};
+}
+// z(i) = f(x(i)) | f(s, x(i)) | f(x(i), s) over n positions: x and the bound scalar s already in the operator's type, px / q the presence bytes of a bitmap
+// (nullptr: every position holds an entry / no presence bytes wanted).  A built-in operator's ahead-of-time kernel, or a user-defined one's compiled kernel.
+inline void elem_eval(const ElemOp& op, uint64_t n, const void* x, const uint8_t* px, const void* s, void* z, uint8_t* q) {
+  if (op.user()) userop_run(op.mode, op.name, op.defn, op.xcode, n, x, px, nullptr, nullptr, nullptr, s, z, q);
+  else vec_apply(op.xcode, n, x, px, op.mode, op.opcode, s, z, q);
 }
 
 // ONE rule for NaN under a floating-point MIN / MAX monoid, on every path: the operator is fmin / fmax (a NaN operand is omitted, as in
@@ -107,6 +127,21 @@ inline const uint8_t* vector_allow(GrB_Vector mask, const DescView& dv, uint64_t
   tmp.alloc(n ? n : 1);
   build_allow(n, mask->type->code, mask->dval.p, mask->dpres.as<uint8_t>(), dv.mask_struct, dv.mask_comp, tmp.as<uint8_t>());
   return tmp.as<uint8_t>();
+}
+
+// The prelude of a vector operation: w, the operands and the mask all have the size n (GrB_DIMENSION_MISMATCH with the caller's own `msg` otherwise);
+// deferred work is completed when `flush` (a user-defined operator is never queued: it runs after everything before it); the mask becomes `allow`.
+// True: nothing may be written (no mask + complement) — w has been cleared under replace, and the caller returns.
+inline bool vector_prelude(GrB_Vector w, GrB_Vector mask, const DescView& dv, uint64_t n, std::initializer_list<GrB_Vector> operands, const char* msg, bool flush,
+                           DevBuf& tmp, const uint8_t*& allow) {
+  bool conform = w->n == n && (!mask || mask->n == n);
+  for (GrB_Vector u : operands) conform = conform && u->n == n;
+  if (!conform) fail(GrB_DIMENSION_MISMATCH, msg);
+  if (flush) lazy_flush();
+  bool nothing = false;
+  allow = vector_allow(mask, dv, n, tmp, &nothing);
+  if (nothing && dv.replace) GrB_Vector_clear(w);
+  return nothing;
 }
 
 // Write T (bitmap tval/tpres of type tcode; buffers are consumed) into w under mask/accum/replace.

@@ -9,8 +9,11 @@
 // The object carries a fresh opcode beyond the built-in ones (>= U_USER / B_USER, so every switch over built-in opcodes sees a value it does not
 // know and the drivers refuse it before they get there: check_binop, grb_opcommon.hpp), its name and a copy of `defn`.  Nothing here needs a device.
 //
-// Running one (GrB_apply, GxB_apply_BinaryOp1st / 2nd, eWiseAdd, eWiseMult — the drivers in grb_matrix_ops.cpp / grb_vector_ops.cpp) goes through
-// userop_run: the definition is embedded in the text of ONE streaming kernel per (operator, kind, type) — every function of the definition made a device
+// Running one (GrB_apply, GxB_apply_BinaryOp1st / 2nd, eWiseAdd, eWiseMult) goes through the drivers of the built-in operators in grb_matrix_ops.cpp /
+// grb_vector_ops.cpp: do_apply / vec_apply_op take an ElemOp (grb_opcommon.hpp), whose elem_eval calls userop_run where a built-in operator's kernel would
+// run; do_ewise / vec_ewise_op call it in their general tail.  A block `if (user)` at the top of each driver refuses containers without an HBM layout
+// (user_needs_layout, here) and looks at the accumulator BEFORE the dimensions; such a call is never queued and completes deferred work first.  In
+// userop_run the definition is embedded in the text of ONE streaming kernel per (operator, kind, type) — every function of the definition made a device
 // function by `#pragma clang force_cuda_host_device`, the kind (apply | bind1st | bind2nd | eadd | emult) a constant of the text — compiled with hipRTC
 // through the chain compiler's build_kernel and its code-object cache on disk (grb_jit.hpp: source + architecture + hipRTC version + options; a second
 // process compiles nothing), at first use and outside the table's lock.  The kernel is entry-parallel: a lane owns four consecutive positions of the value
@@ -21,7 +24,7 @@
 //
 //   GxB_SelectOp_new (&op, fn, xtype, ttype, name, defn)             defn: "bool NAME (GrB_Index i, GrB_Index j, const X *x, const K *thunk) { ... }"
 // is the same for select: a predicate over an entry's row, column, value (X: the C type of xtype) and the thunk (K: of ttype; NULL: xtype).  GxB_Matrix_select /
-// GxB_Vector_select run it through userselect_run: one text per (definition, name, xtype, ttype, matrix | vector) with the kernel grb_userselect, which writes
+// GxB_Vector_select (do_select, vec_select: the built-in select operators' drivers, whose keep bytes it makes) run it through userselect_run: one text per (definition, name, xtype, ttype, matrix | vector) with the kernel grb_userselect, which writes
 // one keep byte per stored entry (matrix: per CSR position; vector: per bitmap position, i the position and j 0); the drivers compact / write back as for the
 // built-in select operators.
 #include "grb_api.hpp"
@@ -177,7 +180,16 @@ hipFunction_t kernel_of(const std::string& src, const char* name, const char* en
   if (en.failed) fail(GrB_INVALID_VALUE, std::string("user-defined operator ") + name + ": its definition does not compile for the device:\n" + en.log);
   return en.fn;
 }
-hipFunction_t kernel_for(int kind, const char* name, const char* defn, int tcode) { return kernel_of(generate(kind, name, defn, tcode), name, "grb_userop", "userop"); }
+
+// the alignment a packed access needs: four values of the type, 16 bytes at the most (8-byte values go as two packs)
+size_t pack_bytes(int tcode) { const size_t b = 4 * (size_t)type_size(tcode); return b > 16 ? 16 : b; }
+bool aligned(const void* p, size_t a) { return !p || ((uintptr_t)p % a) == 0; }
+// both kernels' launch: 256 threads, a lane owns four consecutive entries, at most 16 workgroups per compute unit (the kernels stride)
+void launch(hipFunction_t fn, uint64_t n, void** args) {
+  uint64_t blocks = (n + 1023) / 1024, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap;
+  GRB_HIP(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream(), args, nullptr));
+  g_stat_launched++;
+}
 
 }  // namespace
 
@@ -186,21 +198,23 @@ void userop_refuse(const char* opname, const char* where) {
                             ": user-defined operators run in apply, apply with a bound scalar, eWiseAdd and eWiseMult only");
 }
 
+void user_needs_layout(const char* opname, const char* extent, bool hyper, bool cplx) {
+  if (hyper) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": hypersparse containers (a " + extent + " beyond the device layout) are out of its scope");
+  if (cplx) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": complex containers are out of its scope");
+}
+
 void userop_run(int kind, const char* name, const char* defn, int tcode, uint64_t n, const void* x, const uint8_t* px, const void* y, const uint8_t* py,
                 const uint8_t* both, const void* scalar, void* z, uint8_t* q) {
   if (!c_type(tcode) || !defn) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + name + ": not one of the real built-in types");
-  hipFunction_t fn = kernel_for(kind, name, defn, tcode);
+  hipFunction_t fn = kernel_of(generate(kind, name, defn, tcode), name, "grb_userop", "userop");
   g_last_plan = std::string("userop<name=") + name + ",kind=" + kind_name(kind) + ",type=" + type_by_code(tcode)->name + "> grb_userop ";
   if (!n) return;
-  const size_t ts = (size_t)type_size(tcode), pa = 4 * ts > 16 ? 16 : 4 * ts;
-  auto al = [](const void* p, size_t a) { return !p || ((uintptr_t)p % a) == 0; };
-  int packed = al(x, pa) && al(y, pa) && al(z, pa) && al(px, 4) && al(py, 4) && al(both, 4) && al(q, 4) ? 1 : 0;
-  uint8_t s[16] = {0}; if (scalar) memcpy(s, scalar, ts);
+  const size_t pa = pack_bytes(tcode);
+  int packed = aligned(x, pa) && aligned(y, pa) && aligned(z, pa) && aligned(px, 4) && aligned(py, 4) && aligned(both, 4) && aligned(q, 4) ? 1 : 0;
+  uint8_t s[16] = {0}; if (scalar) memcpy(s, scalar, (size_t)type_size(tcode));
   unsigned long long nn = n;
   void* args[] = {(void*)&x, (void*)&px, (void*)&y, (void*)&py, (void*)&both, (void*)s, (void*)&z, (void*)&q, (void*)&nn, (void*)&packed};
-  uint64_t blocks = (n + 1023) / 1024, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap;
-  GRB_HIP(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream(), args, nullptr));
-  g_stat_launched++;
+  launch(fn, n, args);
 }
 
 void userselect_run(const char* name, const char* defn, int xcode, int tcode, bool on_vector, uint64_t n, const uint32_t* rowidx, const uint32_t* col, const void* x,
@@ -211,24 +225,18 @@ void userselect_run(const char* name, const char* defn, int xcode, int tcode, bo
   if (!n) return;
   if (on_vector) { rowidx = nullptr; col = nullptr; }
   else if (!rowidx || !col) fail(GrB_PANIC, std::string("user-defined operator ") + name + ": select on a matrix without its index arrays");
-  const size_t ts = (size_t)type_size(xcode), pa = 4 * ts > 16 ? 16 : 4 * ts;
-  auto al = [](const void* p, size_t a) { return !p || ((uintptr_t)p % a) == 0; };
-  int packed = al(rowidx, 16) && al(col, 16) && al(x, pa) && al(pres, 4) && al(keep, 4) ? 1 : 0;
+  int packed = aligned(rowidx, 16) && aligned(col, 16) && aligned(x, pack_bytes(xcode)) && aligned(pres, 4) && aligned(keep, 4) ? 1 : 0;
   uint8_t s[16] = {0}; if (thunk) memcpy(s, thunk, (size_t)type_size(tcode));
   unsigned long long nn = n;
   void* args[] = {(void*)&rowidx, (void*)&col, (void*)&x, (void*)&pres, (void*)s, (void*)&keep, (void*)&nn, (void*)&packed};
-  uint64_t blocks = (n + 1023) / 1024, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap;
-  GRB_HIP(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream(), args, nullptr));
-  g_stat_launched++;
+  launch(fn, n, args);
 }
 
 }  // namespace grb
 
 using namespace grb;
 
-static bool one_real_type(GrB_Type a, GrB_Type b, GrB_Type c) {
-  return check_obj(a) && check_obj(b) && check_obj(c) && a == b && b == c && a->code >= T_BOOL && a->code <= T_FP64;
-}
+static bool real_type(GrB_Type t) { return t->code >= T_BOOL && t->code <= T_FP64; }
 static char* copy_text(const char* t) { const size_t n = strlen(t); char* c = (char*)malloc(n + 1); if (c) memcpy(c, t, n + 1); return c; }
 // the name is spliced into the kernel's text as the function to call: it has to be a C identifier
 static bool is_identifier(const char* s) {
@@ -237,63 +245,57 @@ static bool is_identifier(const char* s) {
   return true;
 }
 
-extern "C" {
-
-GrB_Info GxB_UnaryOp_new(GrB_UnaryOp* op, void* fn, GrB_Type ztype, GrB_Type xtype, const char* name, const char* defn) {
-  if (!op || !name || !defn || !ztype || !xtype) return GrB_NULL_POINTER;
-  if (!check_obj(ztype) || !check_obj(xtype)) return GrB_UNINITIALIZED_OBJECT;
-  if (!one_real_type(ztype, xtype, xtype)) { g_last_error = std::string("GxB_UnaryOp_new ") + name + ": the operator's types must be one real built-in type"; return GrB_DOMAIN_MISMATCH; }
-  if (!is_identifier(name) || strlen(name) >= 40) { g_last_error = "GxB_UnaryOp_new: the name must be the C identifier of the defined function (at most 39 characters)"; return GrB_INVALID_VALUE; }
+// What GxB_UnaryOp_new / GxB_BinaryOp_new / GxB_SelectOp_new (`who`) share: the arguments are there and initialised, the operator's `types` are real built-in
+// types (`one_type`: and all the same one), the name is a C identifier, the definition is copied; `make(text)` allocates the object around the copy.
+template <class Op, class Make>
+static GrB_Info new_userop(Op** op, const char* who, const char* name, const char* defn, std::initializer_list<GrB_Type> types, bool one_type, Make make) {
+  if (!op || !name || !defn) return GrB_NULL_POINTER;
+  for (GrB_Type t : types) if (!t) return GrB_NULL_POINTER;
+  for (GrB_Type t : types) if (!check_obj(t)) return GrB_UNINITIALIZED_OBJECT;
+  bool ok = true; for (GrB_Type t : types) ok = ok && real_type(t) && (!one_type || t == *types.begin());
+  if (!ok) { g_last_error = std::string(who) + " " + name + (one_type ? ": the operator's types must be one real built-in type" : ": the operator's value and thunk types must be real built-in types"); return GrB_DOMAIN_MISMATCH; }
+  if (!is_identifier(name) || strlen(name) >= 40) { g_last_error = std::string(who) + ": the name must be the C identifier of the defined function (at most 39 characters)"; return GrB_INVALID_VALUE; }
   char* text = copy_text(defn); if (!text) return GrB_OUT_OF_MEMORY;
-  auto* r = new (std::nothrow) GrB_UnaryOp_opaque{GRB_MAGIC, g_next_unop++, xtype, ztype, "", fn, text};
-  if (!r) { free(text); return GrB_OUT_OF_MEMORY; }
-  snprintf(r->name, sizeof r->name, "%s", name); *op = r; return GrB_SUCCESS;
-}
-GrB_Info GxB_BinaryOp_new(GrB_BinaryOp* op, void* fn, GrB_Type ztype, GrB_Type xtype, GrB_Type ytype, const char* name, const char* defn) {
-  if (!op || !name || !defn || !ztype || !xtype || !ytype) return GrB_NULL_POINTER;
-  if (!check_obj(ztype) || !check_obj(xtype) || !check_obj(ytype)) return GrB_UNINITIALIZED_OBJECT;
-  if (!one_real_type(ztype, xtype, ytype)) { g_last_error = std::string("GxB_BinaryOp_new ") + name + ": the operator's types must be one real built-in type"; return GrB_DOMAIN_MISMATCH; }
-  if (!is_identifier(name) || strlen(name) >= 40) { g_last_error = "GxB_BinaryOp_new: the name must be the C identifier of the defined function (at most 39 characters)"; return GrB_INVALID_VALUE; }
-  char* text = copy_text(defn); if (!text) return GrB_OUT_OF_MEMORY;
-  auto* r = new (std::nothrow) GrB_BinaryOp_opaque{GRB_MAGIC, g_next_binop++, xtype, ytype, ztype, "", fn, text};
+  Op* r = make(text);
   if (!r) { free(text); return GrB_OUT_OF_MEMORY; }
   snprintf(r->name, sizeof r->name, "%s", name); *op = r; return GrB_SUCCESS;
 }
 // built-in handles stay untouched; a user operator is released and the caller's variable set to NULL (a second free of that variable is a no-op)
-GrB_Info GrB_UnaryOp_free(GrB_UnaryOp* op) {
+template <class Op> static GrB_Info free_userop(Op** op) {
   if (op && *op && check_obj(*op) && is_user(*op)) { (*op)->magic = GRB_FREED; free((*op)->defn); delete *op; *op = nullptr; }
   return GrB_SUCCESS;
 }
-GrB_Info GrB_BinaryOp_free(GrB_BinaryOp* op) {
-  if (op && *op && check_obj(*op) && is_user(*op)) { (*op)->magic = GRB_FREED; free((*op)->defn); delete *op; *op = nullptr; }
-  return GrB_SUCCESS;
+static GrB_Info copy_out(const std::string& src, char* buf, size_t len) {
+  if (src.size() + 1 > len) return GrB_INSUFFICIENT_SPACE;
+  memcpy(buf, src.c_str(), src.size() + 1); return GrB_SUCCESS;
+}
+
+extern "C" {
+
+GrB_Info GxB_UnaryOp_new(GrB_UnaryOp* op, void* fn, GrB_Type ztype, GrB_Type xtype, const char* name, const char* defn) {
+  return new_userop(op, "GxB_UnaryOp_new", name, defn, {ztype, xtype}, true,
+                    [&](char* text) { return new (std::nothrow) GrB_UnaryOp_opaque{GRB_MAGIC, g_next_unop++, xtype, ztype, "", fn, text}; });
+}
+GrB_Info GxB_BinaryOp_new(GrB_BinaryOp* op, void* fn, GrB_Type ztype, GrB_Type xtype, GrB_Type ytype, const char* name, const char* defn) {
+  return new_userop(op, "GxB_BinaryOp_new", name, defn, {ztype, xtype, ytype}, true,
+                    [&](char* text) { return new (std::nothrow) GrB_BinaryOp_opaque{GRB_MAGIC, g_next_binop++, xtype, ytype, ztype, "", fn, text}; });
 }
 // a predicate "bool NAME (GrB_Index i, GrB_Index j, const X *x, const K *thunk)": X the C type of xtype, K of ttype (NULL: the same as xtype), both real built-in types
 GrB_Info GxB_SelectOp_new(GxB_SelectOp* op, void* fn, GrB_Type xtype, GrB_Type ttype, const char* name, const char* defn) {
-  if (!op || !name || !defn || !xtype) return GrB_NULL_POINTER;
-  if (!check_obj(xtype) || (ttype && !check_obj(ttype))) return GrB_UNINITIALIZED_OBJECT;
   if (!ttype) ttype = xtype;
-  if (!one_real_type(xtype, xtype, xtype) || !one_real_type(ttype, ttype, ttype)) {
-    g_last_error = std::string("GxB_SelectOp_new ") + name + ": the operator's value and thunk types must be real built-in types"; return GrB_DOMAIN_MISMATCH; }
-  if (!is_identifier(name) || strlen(name) >= 40) { g_last_error = "GxB_SelectOp_new: the name must be the C identifier of the defined function (at most 39 characters)"; return GrB_INVALID_VALUE; }
-  char* text = copy_text(defn); if (!text) return GrB_OUT_OF_MEMORY;
-  auto* r = new (std::nothrow) GxB_SelectOp_opaque{GRB_MAGIC, g_next_selop++, "", fn, xtype, ttype, text};
-  if (!r) { free(text); return GrB_OUT_OF_MEMORY; }
-  snprintf(r->name, sizeof r->name, "%s", name); *op = r; return GrB_SUCCESS;
+  return new_userop(op, "GxB_SelectOp_new", name, defn, {xtype, ttype}, false,
+                    [&](char* text) { return new (std::nothrow) GxB_SelectOp_opaque{GRB_MAGIC, g_next_selop++, "", fn, xtype, ttype, text}; });
 }
-GrB_Info GxB_SelectOp_free(GxB_SelectOp* op) {
-  if (op && *op && check_obj(*op) && is_user(*op)) { (*op)->magic = GRB_FREED; free((*op)->defn); delete *op; *op = nullptr; }
-  return GrB_SUCCESS;
-}
+GrB_Info GrB_UnaryOp_free(GrB_UnaryOp* op) { return free_userop(op); }
+GrB_Info GrB_BinaryOp_free(GrB_BinaryOp* op) { return free_userop(op); }
+GrB_Info GxB_SelectOp_free(GxB_SelectOp* op) { return free_userop(op); }
 // the text that is compiled for a select operator (`ttype` NULL: the same as `xtype`) used on a matrix (on_vector 0) or on a vector (1)
 GrB_Info GrBX_selectop_source(const char* name, const char* defn, GrB_Type xtype, GrB_Type ttype, int on_vector, char* buf, size_t len) {
   if (!name || !defn || !xtype || !buf || !len) return GrB_NULL_POINTER;
   if (!check_obj(xtype) || (ttype && !check_obj(ttype))) return GrB_UNINITIALIZED_OBJECT;
   if (!ttype) ttype = xtype;
   if (xtype->code > T_FP64 || ttype->code > T_FP64) return GrB_DOMAIN_MISMATCH;
-  const std::string src = generate_select(name, defn, xtype->code, ttype->code, on_vector != 0);
-  if (src.size() + 1 > len) return GrB_INSUFFICIENT_SPACE;
-  memcpy(buf, src.c_str(), src.size() + 1); return GrB_SUCCESS;
+  return copy_out(generate_select(name, defn, xtype->code, ttype->code, on_vector != 0), buf, len);
 }
 GrB_Info GrBX_userop_stats(uint64_t* compiled, uint64_t* loaded_from_disk, uint64_t* launched) {
   if (compiled) *compiled = g_stat_compiled.load(); if (loaded_from_disk) *loaded_from_disk = g_stat_from_disk.load(); if (launched) *launched = g_stat_launched.load();
@@ -304,9 +306,7 @@ GrB_Info GrBX_userop_source(const char* name, const char* defn, GrB_Type type, i
   if (!name || !defn || !type || !buf || !len) return GrB_NULL_POINTER;
   if (!check_obj(type)) return GrB_UNINITIALIZED_OBJECT;
   if (type->code > T_FP64 || kind < UK_APPLY || kind > UK_EMULT) return GrB_DOMAIN_MISMATCH;
-  const std::string src = generate(kind, name, defn, type->code);
-  if (src.size() + 1 > len) return GrB_INSUFFICIENT_SPACE;
-  memcpy(buf, src.c_str(), src.size() + 1); return GrB_SUCCESS;
+  return copy_out(generate(kind, name, defn, type->code), buf, len);
 }
 // which images of a container are valid right now (bit 0: the host mirror, bit 1: the HBM image) — looks, changes nothing, completes no deferred work
 GrB_Info GrBX_Matrix_residency(const GrB_Matrix A, int* where) {

@@ -12,6 +12,9 @@ inline bool is_user(const GxB_SelectOp_opaque* op) { return op->opcode >= SEL_US
 
 // GrB_DOMAIN_MISMATCH: the operator `opname` cannot be used as `where` (an accumulator, a monoid, a multiplier, ...)
 [[noreturn]] void userop_refuse(const char* opname, const char* where);
+// A user-defined operator runs on containers with an HBM layout only: GrB_DOMAIN_MISMATCH naming the operator for a hypersparse container (`extent`: what of
+// it is beyond the device layout — "dimension" of a matrix, "size" of a vector) or a complex one.
+void user_needs_layout(const char* opname, const char* extent, bool hyper, bool cplx);
 
 // Evaluate the operator (`name`, `defn`, all of its types `tcode`) over n positions with its compiled kernel; sets the kernel plan.
 //   x / y        operand values of type tcode (y: nullptr for UK_APPLY / UK_BIND*)

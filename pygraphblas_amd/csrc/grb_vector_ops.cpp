@@ -135,9 +135,8 @@ static void vec_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const 
       return;
     }
   }
-  DevBuf allow_buf, region; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) { GrB_Vector_clear(w); } return; }
+  DevBuf allow_buf, region; const uint8_t* allow;
+  if (vector_prelude(w, mask, dv, n, {}, "assign: mask size", false, allow_buf, allow)) return;
   if (I == GrB_ALL && !mask && !accum) {                     // `w(:) = s`: a note on the vector in non-blocking mode (grb_lazy.cpp)
     uint8_t sw[16] = {0}; cast_scalar(w->type->code, sw, xcode, x);
     if (lazy_fill(w, sw)) return;
@@ -167,93 +166,30 @@ static void vec_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const 
   w->dnvals_known = !allow && !reg; w->dnvals = w->dnvals_known ? n : 0;       // every index, no mask: the vector is full now
 }
 
-// a user-defined operator (grb_userop.cpp) runs on bitmap vectors in HBM only
-static void user_needs_layout(const char* opname, bool hyper, bool cplx) {
-  if (hyper) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": hypersparse containers (a size beyond the device layout) are out of its scope");
-  if (cplx) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + ": complex containers are out of its scope");
-}
-
-// eWiseAdd / eWiseMult with a user-defined operator: never queued — deferred work is completed first, then the operator's compiled kernel runs over the two bitmaps
-static void vec_ewise_user(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v, GrB_Descriptor desc, bool is_union) {
-  user_needs_layout(op->name, is_hyper(w) || is_hyper(u) || is_hyper(v) || (mask && is_hyper(mask)),
-                    w->type->code >= T_FC32 || u->type->code >= T_FC32 || v->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
-  if (accum) check_binop(accum, "accum");
-  const DescView dv(desc); const uint64_t n = w->n;
-  if (u->n != n || v->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "eWise: vector sizes differ");
-  lazy_flush();
-  if (!mask && dv.mask_comp) { if (dv.replace) GrB_Vector_clear(w); return; }
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
-  vec_to_device(u); vec_to_device(v);
-  const int xc = op->xtype->code;
-  DevBuf uc, vc, tval(n * type_size(xc) + 16), tpres(n + 16);
-  const void* uv = cast_values(xc, u->type->code, u->dval.p, n, uc);
-  const void* vv = cast_values(xc, v->type->code, v->dval.p, n, vc);
-  userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), nullptr, nullptr, tval.p, tpres.as<uint8_t>());
-  const bool uf = u->dnvals_known && u->dnvals == n, vf = v->dnvals_known && v->dnvals == n;
-  const uint64_t tn = (is_union ? (uf || vf) : (uf && vf)) ? n : ~0ull;
-  vector_write_back(w, xc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/false, tn);
-}
-
-// apply with a user-defined operator: kind UK_APPLY (unary) or UK_BIND1ST / UK_BIND2ND (binary with a bound scalar)
-static void vec_apply_user(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, int kind, const char* name, const char* defn, int xcode, const void* scalar, int scode,
-                           GrB_Vector u, GrB_Descriptor desc) {
-  need_device();
-  if (!check_obj(u) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "apply: uninitialised operand");
-  user_needs_layout(name, is_hyper(w) || is_hyper(u) || (mask && is_hyper(mask)), w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32) || scode >= T_FC32);
-  if (accum) check_binop(accum, "accum");
-  const DescView dv(desc); const uint64_t n = w->n;
-  if (u->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "apply: vector sizes differ");
-  lazy_flush();
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
-  uint8_t s[16] = {0}; if (scalar) cast_scalar(xcode, s, scode, scalar);
-  vec_to_device(u);
-  DevBuf uc, tval(n * type_size(xcode) + 16), tpres(n + 16);
-  const void* uv = cast_values(xcode, u->type->code, u->dval.p, n, uc);
-  userop_run(kind, name, defn, xcode, n, uv, u->dpres.as<uint8_t>(), nullptr, nullptr, nullptr, s, tval.p, tpres.as<uint8_t>());
-  vector_write_back(w, xcode, tval, tpres, allow, accum, dv.replace, false, u->dnvals_known ? u->dnvals : ~0ull);
-}
-
-// select with a user-defined operator over the bitmap: i is the position, j is 0; the values are cast into the operator's type for the predicate only.  Never queued.
-static void vec_select_user(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GxB_SelectOp op, GrB_Vector u, GxB_Scalar thunk, GrB_Descriptor desc) {
-  if (mask && !check_obj(mask)) fail(GrB_UNINITIALIZED_OBJECT, "select: uninitialised mask");
-  const bool has_thunk = thunk && check_obj(thunk) && thunk->has;
-  user_needs_layout(op->name, is_hyper(w) || is_hyper(u) || (mask && is_hyper(mask)),
-                    w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32) || (has_thunk && thunk->type->code >= T_FC32));
-  if (accum) check_binop(accum, "accum");
-  const DescView dv(desc); const uint64_t n = w->n;
-  if (u->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "select: vector sizes differ");
-  lazy_flush();
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
-  vec_to_device(u);
-  const int uc = u->type->code, xc = op->xtype->code, kc = op->ttype->code; const size_t ts = u->type->size;
-  DevBuf tval(n * ts + 16), tpres(n + 16), xcast;
-  if (n) GRB_HIP(hipMemcpyAsync(tval.p, u->dval.p, n * ts, hipMemcpyDeviceToDevice, stream()));
-  const void* xv = cast_values(xc, uc, u->dval.p, n, xcast);
-  uint8_t th[16] = {0}; if (has_thunk) cast_scalar(kc, th, thunk->type->code, thunk->x);
-  userselect_run(op->name, op->defn, xc, kc, true, n, nullptr, nullptr, xv, u->dpres.as<uint8_t>(), th, tpres.as<uint8_t>());
-  vector_write_back(w, uc, tval, tpres, allow, accum, dv.replace, false);
-}
-
+// eWiseAdd / eWiseMult.  A user-defined operator (grb_userop.cpp) runs on bitmap vectors in HBM only and is never queued: deferred work is completed first, then
+// its compiled kernel runs where a built-in operator's vec_ewise does.  The hypersparse route, the queue and the one-pass kernel serve built-in operators only.
 static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v,
                          GrB_Descriptor desc, bool is_union) {
   need_device();
   if (!check_obj(u) || !check_obj(v) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "eWise: uninitialised operand");
-  if (check_obj(op) && is_user(op)) { vec_ewise_user(w, mask, accum, op, u, v, desc, is_union); return; }
-  check_binop(op, "eWise");
-  if (is_hyper(w)) { hyper_vec_ewise(w, mask, accum, op, u, v, desc, is_union); return; }      // a size beyond the device layout
+  const bool user = check_obj(op) && is_user(op);
+  if (user) {
+    user_needs_layout(op->name, "size", is_hyper(w) || is_hyper(u) || is_hyper(v) || (mask && is_hyper(mask)),
+                      w->type->code >= T_FC32 || u->type->code >= T_FC32 || v->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
+    if (accum) check_binop(accum, "accum");
+  } else {
+    check_binop(op, "eWise");
+    if (is_hyper(w)) { hyper_vec_ewise(w, mask, accum, op, u, v, desc, is_union); return; }      // a size beyond the device layout
+  }
+  // (the prelude's steps one by one: the allow bytes cost a kernel, and the one-pass kernel below reads the mask in place)
   const DescView dv(desc); const uint64_t n = w->n;
   if (u->n != n || v->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "eWise: vector sizes differ");
+  if (user) lazy_flush();
   if (!mask && dv.mask_comp) { if (dv.replace) GrB_Vector_clear(w); return; }      // no mask, complemented: nothing may be written
-  if (!mask && !accum && lazy_ewise(w, op, u, v, is_union)) return;      // queued: runs fused with its neighbours when a result is looked at
   const int xc = op->xtype->code;
-  // one pass when everything works in w's own type (round 6): the mask read in place, T(i) in a register, the write-back in the same store
-  {
+  if (!user) {
+    if (!mask && !accum && lazy_ewise(w, op, u, v, is_union)) return;      // queued: runs fused with its neighbours when a result is looked at
+    // one pass when everything works in w's own type (round 6): the mask read in place, T(i) in a register, the write-back in the same store
     const char* fe = getenv("GRB_MI355X_EWISE_FUSED");
     const bool off = fe && atoi(fe) == 0;      // measurement / test hook (read per call, like GRB_MI355X_CHAIN_JIT)
     const int wc = w->type->code;
@@ -277,35 +213,38 @@ static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_
   }
   DevBuf allow_buf; bool nothing = false;
   const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
   vec_to_device(u); vec_to_device(v);
-  DevBuf uc, vc, tval(n * type_size(xc) + 1), tpres(n + 1);
+  DevBuf uc, vc, tval(n * type_size(xc) + 16), tpres(n + 16);
   const void* uv = cast_values(xc, u->type->code, u->dval.p, n, uc);
   const void* vv = cast_values(xc, v->type->code, v->dval.p, n, vc);
-  vec_ewise(xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), op->opcode, is_union, tval.p, tpres.as<uint8_t>());
+  if (user) userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), nullptr, nullptr, tval.p, tpres.as<uint8_t>());
+  else vec_ewise(xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), op->opcode, is_union, tval.p, tpres.as<uint8_t>());
   // a comparison yields 0/1 in the operand type: identical to BOOL after the typecast into w
   const bool uf = u->dnvals_known && u->dnvals == n, vf = v->dnvals_known && v->dnvals == n;
   const uint64_t tn = (is_union ? (uf || vf) : (uf && vf)) ? n : ~0ull;          // a full operand makes the union full, two make the intersection full
   vector_write_back(w, xc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/false, tn);
 }
 
-// mode 0: unary op; 1: z = f(s, x); 2: z = f(x, s)
-static void vec_apply_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, int mode, int opcode, int opxcode, int opzcode, const void* scalar, int scode,
-                         GrB_Vector u, GrB_Descriptor desc) {
+// apply, and apply with a bound scalar (the ElemOp's mode).  A user-defined operator is refused on containers without an HBM layout, has its accumulator looked at
+// first, and is never queued; a built-in one may join the queue of deferred element-wise work.
+static void vec_apply_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const ElemOp& op, const void* scalar, int scode, GrB_Vector u, GrB_Descriptor desc) {
   need_device();
   if (!check_obj(u) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "apply: uninitialised operand");
+  if (op.user()) {
+    user_needs_layout(op.name, "size", is_hyper(w) || is_hyper(u) || (mask && is_hyper(mask)),
+                      w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32) || scode >= T_FC32);
+    if (accum) check_binop(accum, "accum");
+  }
   const DescView dv(desc); const uint64_t n = w->n;
-  if (u->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "apply: vector sizes differ");
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
-  uint8_t s[16] = {0}; if (scalar) cast_scalar(opxcode, s, scode, scalar);
-  if (!mask && !accum && lazy_apply(w, mode, opcode, opxcode, opzcode, s, u)) return;
+  DevBuf allow_buf; const uint8_t* allow;
+  if (vector_prelude(w, mask, dv, n, {u}, "apply: vector sizes differ", op.user(), allow_buf, allow)) return;
+  uint8_t s[16] = {0}; if (scalar) cast_scalar(op.xcode, s, scode, scalar);
+  if (!op.user() && !mask && !accum && lazy_apply(w, op.mode, op.opcode, op.xcode, op.zcode, s, u)) return;
   vec_to_device(u);
-  DevBuf uc, tval(n * type_size(opxcode) + 1), tpres(n + 1);
-  const void* uv = cast_values(opxcode, u->type->code, u->dval.p, n, uc);
-  vec_apply(opxcode, n, uv, u->dpres.as<uint8_t>(), mode, opcode, s, tval.p, tpres.as<uint8_t>());
-  vector_write_back(w, opxcode, tval, tpres, allow, accum, dv.replace, false, u->dnvals_known ? u->dnvals : ~0ull);     // apply keeps the pattern
+  DevBuf uc, tval(n * type_size(op.xcode) + 16), tpres(n + 16);
+  const void* uv = cast_values(op.xcode, u->type->code, u->dval.p, n, uc);
+  elem_eval(op, n, uv, u->dpres.as<uint8_t>(), s, tval.p, tpres.as<uint8_t>());
+  vector_write_back(w, op.xcode, tval, tpres, allow, accum, dv.replace, false, u->dnvals_known ? u->dnvals : ~0ull);     // apply keeps the pattern
 }
 
 // positional unary operators on a vector (an n x 1 column): the pattern of u, the values are the index (which 0 / 1: + 1) or the column 0 (2 / 3: + 1)
@@ -313,15 +252,54 @@ static void vec_position_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, i
   need_device();
   if (!check_obj(u) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "apply: uninitialised operand");
   const DescView dv(desc); const uint64_t n = w->n;
-  if (u->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "apply: vector sizes differ");
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  DevBuf allow_buf; const uint8_t* allow;
+  if (vector_prelude(w, mask, dv, n, {u}, "apply: vector sizes differ", false, allow_buf, allow)) return;
   vec_to_device(u);
   DevBuf tval(n * type_size(zcode) + 1), tpres(n + 1);
   vec_position_values(zcode, n, which, tval.p);
   if (n) GRB_HIP(hipMemcpyAsync(tpres.p, u->dpres.p, n, hipMemcpyDeviceToDevice, stream()));
   vector_write_back(w, zcode, tval, tpres, allow, accum, dv.replace, false, u->dnvals_known ? u->dnvals : ~0ull);
+}
+
+// select: T is u with the presence bytes the operator keeps.  A built-in operator makes them from the positions (an n x 1 column: entry (i, 0)) or from the
+// values; a user-defined one with its compiled kernel (i the position, j 0; the values cast into the operator's type FOR THE PREDICATE ONLY), never queued.
+static void vec_select(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GxB_SelectOp op, GrB_Vector u, GxB_Scalar thunk, GrB_Descriptor desc) {
+  need_device();
+  if (mask && !check_obj(mask)) fail(GrB_UNINITIALIZED_OBJECT, "select: uninitialised mask");
+  const bool user = is_user(op), has_thunk = thunk && check_obj(thunk) && thunk->has;
+  if (user) {
+    user_needs_layout(op->name, "size", is_hyper(w) || is_hyper(u) || (mask && is_hyper(mask)),
+                      w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32) || (has_thunk && thunk->type->code >= T_FC32));
+    if (accum) check_binop(accum, "accum");
+  }
+  const DescView dv(desc); const uint64_t n = w->n;
+  DevBuf allow_buf; const uint8_t* allow;
+  if (vector_prelude(w, mask, dv, n, {u}, "select: vector sizes differ", user, allow_buf, allow)) return;
+  vec_to_device(u);
+  const int uc = u->type->code; const size_t ts = u->type->size;
+  DevBuf tval(n * ts + 16), tpres(n + 16);
+  if (n) GRB_HIP(hipMemcpyAsync(tval.p, u->dval.p, n * ts, hipMemcpyDeviceToDevice, stream()));
+  int64_t k = 0; uint8_t th[16] = {0};      // the thunk as a diagonal, and in the type it is compared in (no thunk, or an empty one: zero)
+  if (user) {
+    const int xc = op->xtype->code, kc = op->ttype->code; DevBuf xcast;
+    const void* xv = cast_values(xc, uc, u->dval.p, n, xcast);
+    if (has_thunk) cast_scalar(kc, th, thunk->type->code, thunk->x);
+    userselect_run(op->name, op->defn, xc, kc, true, n, nullptr, nullptr, xv, u->dpres.as<uint8_t>(), th, tpres.as<uint8_t>());
+  } else {
+    if (has_thunk) { cast_scalar(T_INT64, &k, thunk->type->code, thunk->x); cast_scalar(uc, th, thunk->type->code, thunk->x); }
+    if (op->opcode <= SEL_OFFDIAG) {
+      // positional on an n x 1 column: entry (i, 0);  tril: 0 <= i + k ... keep iff j - i <= k etc.
+      std::vector<uint8_t> up(n), keep(n);
+      GRB_HIP(hipMemcpyAsync(up.data(), u->dpres.p, n, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+      for (uint64_t i = 0; i < n; i++) { const int64_t d = 0 - (int64_t)i; bool kp = false;
+        switch (op->opcode) { case SEL_TRIL: kp = d <= k; break; case SEL_TRIU: kp = d >= k; break; case SEL_DIAG: kp = d == k; break; default: kp = d != k; }
+        keep[i] = up[i] && kp; }
+      GRB_HIP(hipMemcpyAsync(tpres.p, keep.data(), n, hipMemcpyHostToDevice, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+    } else {
+      select_value_flags(uc, n, u->dval.p, u->dpres.as<uint8_t>(), op->opcode, th, tpres.as<uint8_t>());
+    }
+  }
+  vector_write_back(w, uc, tval, tpres, allow, accum, dv.replace, false);
 }
 
 #define VEC_GUARD(w) if (!(w)) return GrB_NULL_POINTER; if (!check_obj(w)) return GrB_UNINITIALIZED_OBJECT
@@ -357,40 +335,14 @@ GrB_Info GrBX_Vector_iseq(bool* equal, const GrB_Vector u, const GrB_Vector v) {
 
 GrB_Info GrB_Vector_apply(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_UnaryOp op, const GrB_Vector u, const GrB_Descriptor desc) {
   VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
-  return guarded(w, [&] { if (is_user(op)) { vec_apply_user(w, mask, accum, UK_APPLY, op->name, op->defn, op->xtype->code, nullptr, 0, u, desc); return; }
-    if (op->opcode >= U_POSITIONI) { vec_position_op(w, mask, accum, op->opcode - U_POSITIONI, op->ztype->code, u, desc); return; }
-    vec_apply_op(w, mask, accum, 0, op->opcode, op->xtype->code, op->ztype->code, nullptr, 0, u, desc); });
+  return guarded(w, [&] { const ElemOp e = elem_op(op);
+    if (!e.user() && op->opcode >= U_POSITIONI) { vec_position_op(w, mask, accum, op->opcode - U_POSITIONI, op->ztype->code, u, desc); return; }
+    vec_apply_op(w, mask, accum, e, nullptr, 0, u, desc); });
 }
 
 GrB_Info GxB_Vector_select(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GxB_SelectOp op, const GrB_Vector u, const GxB_Scalar thunk, const GrB_Descriptor desc) {
   VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; if (!check_obj(op) || !check_obj(u)) return GrB_UNINITIALIZED_OBJECT;
-  return guarded(w, [&] {
-    need_device();
-    if (is_user(op)) { vec_select_user(w, mask, accum, op, u, thunk, desc); return; }
-    const DescView dv(desc); const uint64_t n = w->n;
-    if (u->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "select: vector sizes differ");
-    DevBuf allow_buf; bool nothing = false;
-    const uint8_t* allow = vector_allow(mask, dv, n, allow_buf, &nothing);
-    if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
-    vec_to_device(u);
-    const int uc = u->type->code; const size_t ts = u->type->size;
-    DevBuf tval(n * ts + 1), tpres(n + 1);
-    GRB_HIP(hipMemcpyAsync(tval.p, u->dval.p, n * ts, hipMemcpyDeviceToDevice, stream()));
-    int64_t k = 0; uint8_t th[16] = {0};
-    if (thunk && check_obj(thunk) && thunk->has) { cast_scalar(T_INT64, &k, thunk->type->code, thunk->x); cast_scalar(uc, th, thunk->type->code, thunk->x); }
-    if (op->opcode <= SEL_OFFDIAG) {
-      // positional on an n x 1 column: entry (i, 0);  tril: 0 <= i + k ... keep iff j - i <= k etc.
-      std::vector<uint8_t> up(n), keep(n);
-      GRB_HIP(hipMemcpyAsync(up.data(), u->dpres.p, n, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
-      for (uint64_t i = 0; i < n; i++) { const int64_t d = 0 - (int64_t)i; bool kp = false;
-        switch (op->opcode) { case SEL_TRIL: kp = d <= k; break; case SEL_TRIU: kp = d >= k; break; case SEL_DIAG: kp = d == k; break; default: kp = d != k; }
-        keep[i] = up[i] && kp; }
-      GRB_HIP(hipMemcpyAsync(tpres.p, keep.data(), n, hipMemcpyHostToDevice, stream())); GRB_HIP(hipStreamSynchronize(stream()));
-    } else {
-      select_value_flags(uc, n, u->dval.p, u->dpres.as<uint8_t>(), op->opcode, th, tpres.as<uint8_t>());
-    }
-    vector_write_back(w, uc, tval, tpres, allow, accum, dv.replace, false);
-  });
+  return guarded(w, [&] { vec_select(w, mask, accum, op, u, thunk, desc); });
 }
 
 #define GRB_TYPED_VECOPS(SUF, CT, CODE) \
@@ -399,11 +351,9 @@ GrB_Info GxB_Vector_select(GrB_Vector w, const GrB_Vector mask, const GrB_Binary
   GrB_Info GrB_Vector_assign_##SUF(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, CT x, const GrB_Index* I, GrB_Index ni, const GrB_Descriptor desc) { \
     VEC_GUARD(w); return guarded(w, [&] { vec_assign(w, mask, accum, &x, CODE, I, ni, desc); }); } \
   GrB_Info GxB_Vector_apply_BinaryOp1st_##SUF(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, CT x, const GrB_Vector u, const GrB_Descriptor desc) { \
-    VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; return guarded(w, [&] { if (check_obj(op) && is_user(op)) { vec_apply_user(w, mask, accum, UK_BIND1ST, op->name, op->defn, op->xtype->code, &x, CODE, u, desc); return; } \
-                                                                            check_binop(op, "apply"); vec_apply_op(w, mask, accum, 1, op->opcode, op->xtype->code, op->ztype->code, &x, CODE, u, desc); }); } \
+    VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; return guarded(w, [&] { vec_apply_op(w, mask, accum, elem_op(op, 1), &x, CODE, u, desc); }); } \
   GrB_Info GxB_Vector_apply_BinaryOp2nd_##SUF(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, CT y, const GrB_Descriptor desc) { \
-    VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; return guarded(w, [&] { if (check_obj(op) && is_user(op)) { vec_apply_user(w, mask, accum, UK_BIND2ND, op->name, op->defn, op->xtype->code, &y, CODE, u, desc); return; } \
-                                                                            check_binop(op, "apply"); vec_apply_op(w, mask, accum, 2, op->opcode, op->xtype->code, op->ztype->code, &y, CODE, u, desc); }); }
+    VEC_GUARD(w); if (!op || !u) return GrB_NULL_POINTER; return guarded(w, [&] { vec_apply_op(w, mask, accum, elem_op(op, 2), &y, CODE, u, desc); }); }
 GRB_TYPED_VECOPS(BOOL, bool, T_BOOL) GRB_TYPED_VECOPS(INT8, int8_t, T_INT8) GRB_TYPED_VECOPS(UINT8, uint8_t, T_UINT8)
 GRB_TYPED_VECOPS(INT16, int16_t, T_INT16) GRB_TYPED_VECOPS(UINT16, uint16_t, T_UINT16) GRB_TYPED_VECOPS(INT32, int32_t, T_INT32)
 GRB_TYPED_VECOPS(UINT32, uint32_t, T_UINT32) GRB_TYPED_VECOPS(INT64, int64_t, T_INT64) GRB_TYPED_VECOPS(UINT64, uint64_t, T_UINT64)
