@@ -14,46 +14,11 @@
 //   traffic  (12 + ts) bytes read and (4 + ts) written per entry of A, 8 bytes per row of C.
 // No atomics anywhere: every output position has exactly one writer.
 #include "grb_assign.hpp"
-#include "grb_device.hpp"
+#include "grb_index.hpp"
 #include "grb_matops.hpp"
 
 namespace grb {
-
-void segmented_sort_pairs_u32(const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t n, uint32_t nseg, const uint32_t* begins, const uint32_t* ends, int end_bit);   // grb_prims.hip
-
 namespace {
-
-constexpr uint32_t NONE = 0xFFFFFFFFu;
-
-template <int TS> struct WordOf { typedef typename std::conditional<TS == 8, uint64_t, typename std::conditional<TS == 4, uint32_t, typename std::conditional<TS == 2, uint16_t, uint8_t>::type>::type>::type type; };
-
-// index argument on the device, both ways
-struct DIdx { int kind; uint32_t lo, step; uint64_t n; const uint32_t* list; const uint32_t* inv; };
-__device__ __forceinline__ uint32_t idx_at(const DIdx& x, uint64_t k) {
-  switch (x.kind) {
-    case EX_ALL: return (uint32_t)k;
-    case EX_RANGE: return x.lo + (uint32_t)k * x.step;
-    case EX_BACK: return x.lo - (uint32_t)k * x.step;
-    default: return x.list[k];
-  }
-}
-// the k with I[k] == i, or NONE
-__device__ __forceinline__ uint32_t idx_inv(const DIdx& x, uint32_t i) {
-  switch (x.kind) {
-    case EX_ALL: return i;
-    case EX_RANGE: case EX_BACK: {
-      const bool side = x.kind == EX_BACK ? i <= x.lo : i >= x.lo;
-      const uint32_t d = x.kind == EX_BACK ? x.lo - i : i - x.lo, q = d / x.step;
-      return (side && q * x.step == d && q < x.n) ? q : NONE;
-    }
-    default: return x.inv[i];
-  }
-}
-DIdx didx(const ExIdx& x, const DevBuf* inv = nullptr) { return DIdx{x.kind, x.lo, x.step ? x.step : 1u, x.n, x.list, inv ? inv->as<uint32_t>() : nullptr}; }
-
-inline int grid_of(uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (int)b; }
-inline void check_ts(size_t ts) { if (ts != 1 && ts != 2 && ts != 4 && ts != 8) fail(GrB_DOMAIN_MISMATCH, "assign: values of this size have no device route"); }
-#define GRB_AS_TS(ts, CALL) switch (ts) { case 1: { constexpr int TS = 1; CALL; } break; case 2: { constexpr int TS = 2; CALL; } break; case 4: { constexpr int TS = 4; CALL; } break; default: { constexpr int TS = 8; CALL; } break; }
 
 // ---- the inverse table of a list, and the repeat test ------------------------------------------------------------------
 __global__ void k_assign_inv_scatter(const uint32_t* __restrict__ list, uint64_t n, uint32_t* __restrict__ inv) {
@@ -76,13 +41,6 @@ __global__ void k_assign_move(uint64_t nnz, const uint32_t* __restrict__ rowidx,
     const uint64_t dst = (uint64_t)trp[idx_at(I, a)] + (p - arp[a]);
     ocol[dst] = idx_at(J, acol[p]); ((W*)oval)[dst] = ((const W*)aval)[p];
   }
-}
-__global__ void k_assign_iota(uint32_t* p, uint64_t n) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) p[i] = (uint32_t)i;
-}
-template <int TS> __global__ void k_assign_gather(const uint32_t* __restrict__ perm, uint64_t n, const uint8_t* __restrict__ val, uint8_t* __restrict__ oval) {
-  typedef typename WordOf<TS>::type W;
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) ((W*)oval)[i] = ((const W*)val)[perm[i]];
 }
 
 // ---- the region of C ----------------------------------------------------------------------------------------------------
@@ -146,15 +104,15 @@ bool assign_inverse(const ExIdx& x, uint64_t dim, DevBuf& inv) {
   GRB_HIP(hipMemsetAsync(inv.p, 0xFF, dim * 4, stream()));
   GRB_HIP(hipMemsetAsync(inv.as<uint32_t>() + dim, 0, 4, stream()));
   if (!x.n) return true;
-  hipLaunchKernelGGL(k_assign_inv_scatter, dim3(grid_of(x.n)), dim3(256), 0, stream(), x.list, x.n, inv.as<uint32_t>());
-  hipLaunchKernelGGL(k_assign_inv_check, dim3(grid_of(x.n)), dim3(256), 0, stream(), x.list, x.n, inv.as<uint32_t>(), inv.as<uint32_t>() + dim);
+  hipLaunchKernelGGL(k_assign_inv_scatter, dim3(grid_1d(x.n)), dim3(256), 0, stream(), x.list, x.n, inv.as<uint32_t>());
+  hipLaunchKernelGGL(k_assign_inv_check, dim3(grid_1d(x.n)), dim3(256), 0, stream(), x.list, x.n, inv.as<uint32_t>(), inv.as<uint32_t>() + dim);
   uint32_t repeat = 0;
   GRB_HIP(hipMemcpyAsync(&repeat, inv.as<uint32_t>() + dim, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
   return repeat == 0;
 }
 
 void assign_relocate(const DevCSR& A, size_t ts, const ExIdx& I, const ExIdx& J, uint32_t crows, uint32_t ccols, DevCSR& T, AssignPlan& plan) {
-  check_ts(ts);
+  check_value_size(ts, "assign");
   if (A.nrows != I.n || A.ncols != J.n) fail(GrB_PANIC, "assign: operand shape does not match the index arguments");      // (the entry points checked it: the kernels' bounds depend on it)
   const uint64_t nnz = A.nnz;
   T.clear(); T.nrows = crows; T.ncols = ccols; T.nnz = nnz;
@@ -164,22 +122,18 @@ void assign_relocate(const DevCSR& A, size_t ts, const ExIdx& I, const ExIdx& J,
   const DIdx di = didx(I), dj = didx(J);
   DevBuf len(((size_t)crows + 1) * 4), rowidx(nnz * 4 + 4);
   GRB_HIP(hipMemsetAsync(len.p, 0, ((size_t)crows + 1) * 4, stream()));
-  hipLaunchKernelGGL(k_assign_rowlen, dim3(grid_of(I.n)), dim3(256), 0, stream(), di, I.n, A.rowptr.as<uint32_t>(), len.as<uint32_t>());
+  hipLaunchKernelGGL(k_assign_rowlen, dim3(grid_1d(I.n)), dim3(256), 0, stream(), di, I.n, A.rowptr.as<uint32_t>(), len.as<uint32_t>());
   exclusive_scan_u32(len.as<uint32_t>(), T.rowptr.as<uint32_t>(), (uint64_t)crows + 1);
   csr_row_indices(A, rowidx.as<uint32_t>());
   const bool rowsort = !J.increasing && J.n > 1;
   DevBuf ucol, uval;                                                         // unsorted columns / values when the rows are sorted afterwards
   if (rowsort) { ucol.alloc(nnz * 4); uval.alloc(nnz * ts); }
   uint32_t* oc = rowsort ? ucol.as<uint32_t>() : T.col.as<uint32_t>(); uint8_t* ov = rowsort ? uval.as<uint8_t>() : T.val.as<uint8_t>();
-  GRB_AS_TS(ts, hipLaunchKernelGGL((k_assign_move<TS>), dim3(grid_of(nnz)), dim3(256), 0, stream(), nnz, rowidx.as<uint32_t>(), A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), A.val.as<uint8_t>(), di, dj,
-                                   T.rowptr.as<uint32_t>(), oc, ov));
-  if (rowsort) {
-    DevBuf iota(nnz * 4), perm(nnz * 4);
-    hipLaunchKernelGGL(k_assign_iota, dim3(grid_of(nnz)), dim3(256), 0, stream(), iota.as<uint32_t>(), nnz);
-    int bits = 1; while (bits < 32 && (1ull << bits) < (uint64_t)ccols) bits++;
-    segmented_sort_pairs_u32(ucol.as<uint32_t>(), T.col.as<uint32_t>(), iota.as<uint32_t>(), perm.as<uint32_t>(), nnz, crows, T.rowptr.as<uint32_t>(), T.rowptr.as<uint32_t>() + 1, bits);
-    GRB_AS_TS(ts, hipLaunchKernelGGL((k_assign_gather<TS>), dim3(grid_of(nnz)), dim3(256), 0, stream(), perm.as<uint32_t>(), nnz, uval.as<uint8_t>(), T.val.as<uint8_t>()));
-  }
+  dispatch_value_size(ts, [&]<int TS>() {
+    hipLaunchKernelGGL((k_assign_move<TS>), dim3(grid_1d(nnz)), dim3(256), 0, stream(), nnz, rowidx.as<uint32_t>(), A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), A.val.as<uint8_t>(), di, dj,
+                       T.rowptr.as<uint32_t>(), oc, ov);
+  });
+  if (rowsort) csr_sort_rows(T, ts, ucol, uval, ccols);
   GRB_HIP(hipStreamSynchronize(stream()));                                   // temporaries are released on scope exit; the pool is stream-ordered
   plan.rowsort = rowsort;
   T.valid = true;
@@ -189,7 +143,7 @@ void assign_region_keep(const DevCSR& C, const ExIdx& I, const DevBuf& inv_i, co
   if (!C.nnz) return;
   DevBuf rowidx(C.nnz * 4 + 4);
   csr_row_indices(C, rowidx.as<uint32_t>());
-  hipLaunchKernelGGL(k_assign_region_keep, dim3(grid_of(C.nnz)), dim3(256), 0, stream(), C.nnz, rowidx.as<uint32_t>(), C.col.as<uint32_t>(), didx(I, &inv_i), didx(J, &inv_j), keep);
+  hipLaunchKernelGGL(k_assign_region_keep, dim3(grid_1d(C.nnz)), dim3(256), 0, stream(), C.nnz, rowidx.as<uint32_t>(), C.col.as<uint32_t>(), didx(I, &inv_i), didx(J, &inv_j), keep);
   GRB_HIP(hipStreamSynchronize(stream()));
 }
 
@@ -197,8 +151,8 @@ void assign_vector(int code, uint64_t n, void* wval, uint8_t* wpres, const uint8
   if (!n) return;
   const DIdx di = didx(I, &inv);
   dispatch_type(code, [&]<class T>() {
-    if (accum >= 0 && binop_needs_math(accum)) hipLaunchKernelGGL((k_assign_vector<T, true>), dim3(grid_of(n)), dim3(256), 0, stream(), n, (T*)wval, wpres, allow, di, (const T*)uval, upres, accum, replace);
-    else hipLaunchKernelGGL((k_assign_vector<T, false>), dim3(grid_of(n)), dim3(256), 0, stream(), n, (T*)wval, wpres, allow, di, (const T*)uval, upres, accum, replace);
+    if (accum >= 0 && binop_needs_math(accum)) hipLaunchKernelGGL((k_assign_vector<T, true>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (T*)wval, wpres, allow, di, (const T*)uval, upres, accum, replace);
+    else hipLaunchKernelGGL((k_assign_vector<T, false>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (T*)wval, wpres, allow, di, (const T*)uval, upres, accum, replace);
   });
 }
 
@@ -207,16 +161,16 @@ void assign_cast_touched(int dst_code, void* dst, int src_code, const void* src,
   const DIdx di = didx(I, &inv);
   dispatch_type(src_code, [&]<class S>() {
     dispatch_type(dst_code, [&]<class D>() {
-      hipLaunchKernelGGL((k_assign_cast_touched<D, S>), dim3(grid_of(n)), dim3(256), 0, stream(), n, (D*)dst, (const S*)src, allow, di, upres);
+      hipLaunchKernelGGL((k_assign_cast_touched<D, S>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (D*)dst, (const S*)src, allow, di, upres);
     });
   });
 }
 
 void assign_line_to_csr(size_t ts, uint64_t n, const void* lval, const uint8_t* lpres, bool as_row, DevCSR& T) {
-  check_ts(ts);
+  check_value_size(ts, "assign");
   T.clear(); T.nrows = as_row ? 1u : (uint32_t)n; T.ncols = as_row ? (uint32_t)n : 1u;
   DevBuf flags((n + 1) * 4), pos_buf;
-  hipLaunchKernelGGL(k_assign_pres_u32, dim3(grid_of(n + 1)), dim3(256), 0, stream(), lpres, n, flags.as<uint32_t>());
+  hipLaunchKernelGGL(k_assign_pres_u32, dim3(grid_1d(n + 1)), dim3(256), 0, stream(), lpres, n, flags.as<uint32_t>());
   // a column's entry positions ARE its row pointer: the scan goes straight into it
   if (as_row) { pos_buf.alloc((n + 1) * 4); T.rowptr.alloc(8); } else T.rowptr.alloc((n + 1) * 4);
   uint32_t* pos = as_row ? pos_buf.as<uint32_t>() : T.rowptr.as<uint32_t>();
@@ -225,7 +179,7 @@ void assign_line_to_csr(size_t ts, uint64_t n, const void* lval, const uint8_t* 
   GRB_HIP(hipMemcpyAsync(&total, pos + n, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
   T.nnz = total; T.col.alloc((size_t)total * 4 + 4); T.val.alloc((size_t)total * ts + 8);
   if (as_row) hipLaunchKernelGGL(k_assign_two, dim3(1), dim3(64), 0, stream(), T.rowptr.as<uint32_t>(), total);
-  if (total) { GRB_AS_TS(ts, hipLaunchKernelGGL((k_assign_line_fill<TS>), dim3(grid_of(n)), dim3(256), 0, stream(), n, (const uint8_t*)lval, lpres, pos, as_row, T.col.as<uint32_t>(), T.val.as<uint8_t>())); }
+  if (total) dispatch_value_size(ts, [&]<int TS>() { hipLaunchKernelGGL((k_assign_line_fill<TS>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (const uint8_t*)lval, lpres, pos, as_row, T.col.as<uint32_t>(), T.val.as<uint8_t>()); });
   GRB_HIP(hipStreamSynchronize(stream()));
   T.valid = true;
 }

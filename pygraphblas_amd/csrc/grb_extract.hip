@@ -18,31 +18,14 @@
 //            each output row is sorted by column afterwards (rocPRIM segmented radix sort on (column, position), then one gather of the values).
 //   traffic  2 x (4 + ts) bytes per entry of the selected rows read (column twice, value once in the fill: (8 + ts)), (4 + ts) per output entry written.
 // No atomics anywhere: every output position has exactly one writer.
-#include "grb_extract.hpp"
-#include "grb_device.hpp"
+#include "grb_index.hpp"
+#include "grb_matops.hpp"
 
 namespace grb {
-
-void segmented_sort_pairs_u32(const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t n, uint32_t nseg, const uint32_t* begins, const uint32_t* ends, int end_bit);   // grb_prims.hip
-
 namespace {
 
 constexpr uint32_t PART = 2048;        // entries per part (one wave)
 constexpr int WAVES = 4;               // waves per workgroup
-
-template <int TS> struct WordOf { typedef typename std::conditional<TS == 8, uint64_t, typename std::conditional<TS == 4, uint32_t, typename std::conditional<TS == 2, uint16_t, uint8_t>::type>::type>::type type; };
-
-// index argument on the device
-struct DIdx { int kind; uint32_t lo, step; const uint32_t* list; };
-__device__ __forceinline__ uint32_t idx_at(const DIdx& x, uint64_t k) {
-  switch (x.kind) {
-    case EX_ALL: return (uint32_t)k;
-    case EX_RANGE: return x.lo + (uint32_t)k * x.step;
-    case EX_BACK: return x.lo - (uint32_t)k * x.step;
-    default: return x.list[k];
-  }
-}
-DIdx didx(const ExIdx& x) { return DIdx{x.kind, x.lo, x.step, x.list}; }
 
 // column map on the device
 enum { CM_ALL = 0, CM_RANGE = 1, CM_TABLE = 2, CM_BISECT = 3 };
@@ -51,20 +34,11 @@ struct DCols {
   uint32_t lo, step, n;                  // range: n positions; list modes: n = length of the sorted list
   const uint32_t* sorted; const uint32_t* perm; const uint32_t* first;      // perm == nullptr: identity
 };
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* a, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < x) lo = mid + 1; else hi = mid; }
-  return lo;
-}
 // hits of source column c: positions [h0, h0 + nh) of the sorted list (list modes), or the output column h0 itself (all / range)
 __device__ __forceinline__ void col_hits(const DCols& J, uint32_t c, uint32_t& h0, uint32_t& nh) {
   switch (J.mode) {
     case CM_ALL: h0 = c; nh = 1; return;
-    case CM_RANGE: {
-      const bool side = J.desc ? c <= J.lo : c >= J.lo;
-      const uint32_t d = J.desc ? J.lo - c : c - J.lo, q = d / J.step;
-      h0 = q; nh = (side && q * J.step == d && q < J.n) ? 1u : 0u; return;
-    }
+    case CM_RANGE: h0 = range_inv(J.desc, J.lo, J.step, J.n, c); nh = h0 != NONE ? 1u : 0u; return;
     case CM_TABLE: h0 = J.first[c]; nh = J.first[c + 1] - h0; return;
     default: {
       h0 = lower_bound_u32(J.sorted, J.n, c);
@@ -139,13 +113,6 @@ __global__ void k_extract_rowptr(uint64_t nout, const uint32_t* __restrict__ par
 __global__ void k_extract_first(const uint32_t* __restrict__ sorted, uint64_t n, uint32_t ncols, uint32_t* __restrict__ first) {
   for (uint64_t c = blockIdx.x * 256ull + threadIdx.x; c <= ncols; c += gridDim.x * 256ull) first[c] = lower_bound_u32(sorted, (uint32_t)n, (uint32_t)c);
 }
-__global__ void k_extract_iota(uint32_t* p, uint64_t n) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) p[i] = (uint32_t)i;
-}
-template <int TS> __global__ void k_extract_gather(const uint32_t* __restrict__ perm, uint64_t n, const uint8_t* __restrict__ val, uint8_t* __restrict__ oval) {
-  typedef typename WordOf<TS>::type W;
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) ((W*)oval)[i] = ((const W*)val)[perm[i]];
-}
 
 // ---- one row / column of a CSR, a sub-vector ---------------------------------------------------------------------------
 // row j of the CSR onto every position (I = ALL): the row's entries scattered into a zeroed bitmap
@@ -174,10 +141,6 @@ template <int TS> __global__ void k_extract_vector(DIdx I, uint64_t n, const uin
   }
 }
 
-inline int grid_of(uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (int)b; }
-inline void check_ts(size_t ts) { if (ts != 1 && ts != 2 && ts != 4 && ts != 8) fail(GrB_DOMAIN_MISMATCH, "extract: values of this size have no device route"); }
-#define GRB_EX_TS(ts, CALL) switch (ts) { case 1: { constexpr int TS = 1; CALL; } break; case 2: { constexpr int TS = 2; CALL; } break; case 4: { constexpr int TS = 4; CALL; } break; default: { constexpr int TS = 8; CALL; } break; }
-
 }  // namespace
 
 void extract_upload(ExIdx& x, DevBuf& keep) {
@@ -189,7 +152,7 @@ void extract_upload(ExIdx& x, DevBuf& keep) {
 }
 
 void extract_csr(const DevCSR& A, size_t ts, const ExIdx& I, const ExIdx& J, bool force_bisect, DevCSR& T, ExtractPlan& plan) {
-  check_ts(ts);
+  check_value_size(ts, "extract");
   const uint64_t nout = I.n, ncout = J.n;
   T.clear(); T.nrows = (uint32_t)nout; T.ncols = (uint32_t)ncout; T.nnz = 0;
   T.rowptr.alloc((nout + 1) * 4);
@@ -208,7 +171,7 @@ void extract_csr(const DevCSR& A, size_t ts, const ExIdx& I, const ExIdx& J, boo
     if (J.increasing) dj.sorted = J.list;                                    // its own sorted list, perm = identity
     else {
       DevBuf iota(ncout * 4); sorted_buf.alloc(ncout * 4); perm_buf.alloc(ncout * 4);
-      hipLaunchKernelGGL(k_extract_iota, dim3(grid_of(ncout)), dim3(256), 0, stream(), iota.as<uint32_t>(), ncout);
+      fill_iota_u32(iota.as<uint32_t>(), ncout);
       int bits = 1; while (bits < 32 && (1ull << bits) < (uint64_t)A.ncols) bits++;
       sort_pairs_u32(J.list, sorted_buf.as<uint32_t>(), iota.as<uint32_t>(), perm_buf.as<uint32_t>(), ncout, bits);
       GRB_HIP(hipStreamSynchronize(stream()));                               // (iota returns to the pool)
@@ -216,21 +179,21 @@ void extract_csr(const DevCSR& A, size_t ts, const ExIdx& I, const ExIdx& J, boo
     }
     if (!force_bisect && (uint64_t)A.ncols + 1 <= EXTRACT_TABLE_MAX_COLS) {
       first_buf.alloc(((size_t)A.ncols + 1) * 4);
-      hipLaunchKernelGGL(k_extract_first, dim3(grid_of((uint64_t)A.ncols + 1)), dim3(256), 0, stream(), dj.sorted, ncout, A.ncols, first_buf.as<uint32_t>());
+      hipLaunchKernelGGL(k_extract_first, dim3(grid_1d((uint64_t)A.ncols + 1)), dim3(256), 0, stream(), dj.sorted, ncout, A.ncols, first_buf.as<uint32_t>());
       dj.first = first_buf.as<uint32_t>(); dj.mode = CM_TABLE; plan.cols = "table";
     } else { dj.mode = CM_BISECT; plan.cols = "bisect"; }
   }
   // ---- parts ----
   const DIdx di = didx(I);
   DevBuf nparts_buf((nout + 1) * 4), partstart((nout + 1) * 4), part_row;
-  hipLaunchKernelGGL(k_extract_nparts, dim3(grid_of(nout + 1)), dim3(256), 0, stream(), di, nout, A.rowptr.as<uint32_t>(), nparts_buf.as<uint32_t>());
+  hipLaunchKernelGGL(k_extract_nparts, dim3(grid_1d(nout + 1)), dim3(256), 0, stream(), di, nout, A.rowptr.as<uint32_t>(), nparts_buf.as<uint32_t>());
   exclusive_scan_u32(nparts_buf.as<uint32_t>(), partstart.as<uint32_t>(), nout + 1);
   uint32_t nparts32 = 0;
   GRB_HIP(hipMemcpyAsync(&nparts32, partstart.as<uint32_t>() + nout, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
   const uint64_t nparts = nparts32;
   if (nparts < nout) fail(GrB_INSUFFICIENT_SPACE, "extract: more than 2^32 parts of rows");
   const bool identity = nparts == nout;
-  if (!identity) { part_row.alloc(nparts * 4); hipLaunchKernelGGL(k_extract_partmap, dim3(grid_of(nout)), dim3(256), 0, stream(), nout, partstart.as<uint32_t>(), part_row.as<uint32_t>()); }
+  if (!identity) { part_row.alloc(nparts * 4); hipLaunchKernelGGL(k_extract_partmap, dim3(grid_1d(nout)), dim3(256), 0, stream(), nout, partstart.as<uint32_t>(), part_row.as<uint32_t>()); }
   // ---- count -> scan -> fill ----
   DevBuf partcount((nparts + 1) * 8), partoff((nparts + 1) * 8);
   GRB_HIP(hipMemsetAsync((uint8_t*)partcount.p + nparts * 8, 0, 8, stream()));
@@ -241,23 +204,18 @@ void extract_csr(const DevCSR& A, size_t ts, const ExIdx& I, const ExIdx& J, boo
   uint64_t total = 0;
   GRB_HIP(hipMemcpyAsync(&total, partoff.as<uint64_t>() + nparts, 8, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
   if (total > 0xFFFFFFF0ull) fail(GrB_INSUFFICIENT_SPACE, "extract: more than 2^32 entries in the result");
-  hipLaunchKernelGGL(k_extract_rowptr, dim3(grid_of(nout + 1)), dim3(256), 0, stream(), nout, partstart.as<uint32_t>(), identity, partoff.as<uint64_t>(), total, T.rowptr.as<uint32_t>());
+  hipLaunchKernelGGL(k_extract_rowptr, dim3(grid_1d(nout + 1)), dim3(256), 0, stream(), nout, partstart.as<uint32_t>(), identity, partoff.as<uint64_t>(), total, T.rowptr.as<uint32_t>());
   T.nnz = total; T.col.alloc(total * 4 + 4); T.val.alloc(total * ts + 8);
   if (total) {
     rowsort = rowsort && ncout > 1;
     DevBuf ucol, uval;                                                       // unsorted columns / values when the rows are sorted afterwards
     if (rowsort) { ucol.alloc(total * 4); uval.alloc(total * ts); }
     uint32_t* oc = rowsort ? ucol.as<uint32_t>() : T.col.as<uint32_t>(); uint8_t* ov = rowsort ? uval.as<uint8_t>() : T.val.as<uint8_t>();
-    GRB_EX_TS(ts, hipLaunchKernelGGL((k_extract_rows<true, TS>), grid, block, 0, stream(), di, dj, nparts, part_row.as<uint32_t>(), partstart.as<uint32_t>(), A.rowptr.as<uint32_t>(),
-                                     A.col.as<uint32_t>(), A.val.as<uint8_t>(), (uint64_t*)nullptr, partoff.as<uint64_t>(), oc, ov));
-    if (rowsort) {
-      DevBuf iota(total * 4), perm(total * 4);
-      hipLaunchKernelGGL(k_extract_iota, dim3(grid_of(total)), dim3(256), 0, stream(), iota.as<uint32_t>(), total);
-      int bits = 1; while (bits < 32 && (1ull << bits) < ncout) bits++;
-      segmented_sort_pairs_u32(ucol.as<uint32_t>(), T.col.as<uint32_t>(), iota.as<uint32_t>(), perm.as<uint32_t>(), total, (uint32_t)nout, T.rowptr.as<uint32_t>(), T.rowptr.as<uint32_t>() + 1, bits);
-      GRB_EX_TS(ts, hipLaunchKernelGGL((k_extract_gather<TS>), dim3(grid_of(total)), dim3(256), 0, stream(), perm.as<uint32_t>(), total, uval.as<uint8_t>(), T.val.as<uint8_t>()));
-      GRB_HIP(hipStreamSynchronize(stream()));
-    }
+    dispatch_value_size(ts, [&]<int TS>() {
+      hipLaunchKernelGGL((k_extract_rows<true, TS>), grid, block, 0, stream(), di, dj, nparts, part_row.as<uint32_t>(), partstart.as<uint32_t>(), A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(),
+                         A.val.as<uint8_t>(), (uint64_t*)nullptr, partoff.as<uint64_t>(), oc, ov);
+    });
+    if (rowsort) csr_sort_rows(T, ts, ucol, uval, ncout);
   }
   GRB_HIP(hipStreamSynchronize(stream()));                                   // temporaries are released on scope exit; the pool is stream-ordered
   plan.rowsort = rowsort && total != 0;
@@ -265,21 +223,23 @@ void extract_csr(const DevCSR& A, size_t ts, const ExIdx& I, const ExIdx& J, boo
 }
 
 void extract_line(const DevCSR& A, size_t ts, bool row_of_csr, uint32_t j, const ExIdx& I, void* tval, uint8_t* tpres) {
-  check_ts(ts);
+  check_value_size(ts, "extract");
   const uint64_t n = I.n; if (!n) return;
   if (row_of_csr && I.kind == EX_ALL) {
     GRB_HIP(hipMemsetAsync(tval, 0, n * ts, stream())); GRB_HIP(hipMemsetAsync(tpres, 0, n, stream()));
-    if (A.nnz) { GRB_EX_TS(ts, hipLaunchKernelGGL((k_extract_row_scatter<TS>), dim3(64), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), A.val.as<uint8_t>(), j, (uint8_t*)tval, tpres)); }
+    if (A.nnz) dispatch_value_size(ts, [&]<int TS>() { hipLaunchKernelGGL((k_extract_row_scatter<TS>), dim3(64), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), A.val.as<uint8_t>(), j, (uint8_t*)tval, tpres); });
     return;
   }
   if (!A.nnz) { GRB_HIP(hipMemsetAsync(tval, 0, n * ts, stream())); GRB_HIP(hipMemsetAsync(tpres, 0, n, stream())); return; }
-  GRB_EX_TS(ts, hipLaunchKernelGGL((k_extract_lookup<TS>), dim3(grid_of(n)), dim3(256), 0, stream(), didx(I), n, row_of_csr, j, A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), A.val.as<uint8_t>(), (uint8_t*)tval, tpres));
+  dispatch_value_size(ts, [&]<int TS>() {
+    hipLaunchKernelGGL((k_extract_lookup<TS>), dim3(grid_1d(n)), dim3(256), 0, stream(), didx(I), n, row_of_csr, j, A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), A.val.as<uint8_t>(), (uint8_t*)tval, tpres);
+  });
 }
 
 void extract_vector(size_t ts, const void* uval, const uint8_t* upres, const ExIdx& I, void* tval, uint8_t* tpres) {
-  check_ts(ts);
+  check_value_size(ts, "extract");
   const uint64_t n = I.n; if (!n) return;
-  GRB_EX_TS(ts, hipLaunchKernelGGL((k_extract_vector<TS>), dim3(grid_of(n)), dim3(256), 0, stream(), didx(I), n, (const uint8_t*)uval, upres, (uint8_t*)tval, tpres));
+  dispatch_value_size(ts, [&]<int TS>() { hipLaunchKernelGGL((k_extract_vector<TS>), dim3(grid_1d(n)), dim3(256), 0, stream(), didx(I), n, (const uint8_t*)uval, upres, (uint8_t*)tval, tpres); });
 }
 
 }  // namespace grb

@@ -175,51 +175,56 @@ bool strictly_increasing(const std::vector<uint64_t>& v) { for (size_t k = 1; k 
 // host-resident containers — notebook slices — keep the host route.  GRB_MI355X_EXTRACT=0 forces the host route, =1 the device route
 // wherever it is legal; GRB_MI355X_EXTRACT_BISECT=1 makes a column list bisect instead of using its table (both read per call: test hooks).
 constexpr uint64_t EXTRACT_DEVICE_MIN_ENTRIES = 10000;
-int extract_env() { const char* e = getenv("GRB_MI355X_EXTRACT"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }
+int route_env(const char* name) { const char* e = getenv(name); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }      // a route's test hook: 0 host, 1 device, -1 not set
 bool extract_bisect_env() { const char* e = getenv("GRB_MI355X_EXTRACT_BISECT"); return e && atoi(e) != 0; }
 bool dev_capable(GrB_Matrix A) { return !A || (!is_hyper(A) && A->type->code < T_FC32 && !A->iso_full); }
 bool dev_capable(GrB_Vector v) { return !v || (!is_hyper(v) && v->type->code < T_FC32 && !v->iso_full); }
 bool extract_on_device(GrB_Matrix A, bool others_capable) {
-  const int env = extract_env();
+  const int env = route_env("GRB_MI355X_EXTRACT");
   if (env == 0 || !device_ok() || !others_capable || !dev_capable(A) || mat_bitmap_only(A)) return false;
   if (env == 1) return true;
   if (A->dev_valid && !A->host_valid) return true;                      // it lives in HBM: it is not downloaded for this
   return A->host_valid && mat_nvals(A) >= EXTRACT_DEVICE_MIN_ENTRIES;   // (the count of a valid host mirror: no device work)
 }
 bool extract_on_device(GrB_Vector u, bool others_capable) {
-  const int env = extract_env();
+  const int env = route_env("GRB_MI355X_EXTRACT");
   if (env == 0 || !device_ok() || !others_capable || !dev_capable(u)) return false;
   if (env == 1) return true;
   vec_gate(u);                                                          // deferred work that involves u is completed first, as every reader does
   if (u->dev_valid && !u->host_valid) return true;
   return u->host_valid && vec_nvals(u) >= EXTRACT_DEVICE_MIN_ENTRIES;
 }
-const char* const EXTRACT_DIM_MSG_V = "extract: output size must equal the number of indices";
+const char* kind_name(const ExIdx& x) { return x.kind == EX_ALL ? "all" : x.kind == EX_LIST ? "list" : "range"; }
+
+// The prelude of the two vector-valued extracts (vector_prelude with the index argument parsed first and the accumulator checked before the mask is touched):
+// `idx` over `dim` positions, the checks in the host route's order, the mask as `allow`.  True: nothing may be written — w has been cleared under replace, and
+// the caller returns.
+bool extract_vector_prelude(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const GrB_Index* I, GrB_Index ni, uint64_t dim, const DescView& dv, ExIdx& idx, DevBuf& allow_buf, const uint8_t*& allow) {
+  extract_parse(idx, I, ni, dim, "extract");
+  if (w->n != idx.n || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "extract: output size must equal the number of indices");
+  if (accum) check_binop(accum, "accum");
+  bool nothing = false;
+  allow = vector_allow(mask, dv, w->n, allow_buf, &nothing);
+  if (nothing && dv.replace) GrB_Vector_clear(w);
+  return nothing;
+}
 
 void extract_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, const GrB_Index* I, GrB_Index ni, const DescView& dv) {
-  ExIdx idx; extract_parse(idx, I, ni, u->n, "extract");
-  if (w->n != idx.n || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, EXTRACT_DIM_MSG_V);
-  if (accum) check_binop(accum, "accum");
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, w->n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  ExIdx idx; DevBuf allow_buf; const uint8_t* allow;
+  if (extract_vector_prelude(w, mask, accum, I, ni, u->n, dv, idx, allow_buf, allow)) return;
   vec_to_device(u);
   const uint64_t n = idx.n; const size_t ts = u->type->size;
   DevBuf keep, tval(n * ts + 8), tpres(n + 1);
   extract_upload(idx, keep);
   extract_vector(ts, u->dval.p, u->dpres.as<uint8_t>(), idx, tval.p, tpres.as<uint8_t>());
   if (keep.p) GRB_HIP(hipStreamSynchronize(stream()));                  // (the uploaded list returns to the pool)
-  g_last_plan = std::string("extract_vector<index=") + (idx.kind == EX_ALL ? "all" : idx.kind == EX_LIST ? "list" : "range") + "> k_extract_vector ";
+  g_last_plan = std::string("extract_vector<index=") + kind_name(idx) + "> k_extract_vector ";
   vector_write_back(w, u->type->code, tval, tpres, allow, accum, dv.replace, false);
 }
 
 void extract_col_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Matrix A, const GrB_Index* I, GrB_Index ni, GrB_Index j, const DescView& dv, uint64_t ar) {
-  ExIdx idx; extract_parse(idx, I, ni, ar, "extract");
-  if (w->n != idx.n || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, EXTRACT_DIM_MSG_V);
-  if (accum) check_binop(accum, "accum");
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, w->n, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  ExIdx idx; DevBuf allow_buf; const uint8_t* allow;
+  if (extract_vector_prelude(w, mask, accum, I, ni, ar, dv, idx, allow_buf, allow)) return;
   mat_to_device(A);
   const uint64_t n = idx.n; const size_t ts = A->type->size;
   DevBuf keep, tval(n * ts + 8), tpres(n + 1);
@@ -227,7 +232,7 @@ void extract_col_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_M
   extract_line(A->csr, ts, dv.tran0, (uint32_t)j, idx, tval.p, tpres.as<uint8_t>());
   if (keep.p) GRB_HIP(hipStreamSynchronize(stream()));
   const bool scatter = dv.tran0 && idx.kind == EX_ALL;
-  g_last_plan = std::string("extract_col<") + (dv.tran0 ? "row of the CSR" : "column of the CSR") + ",index=" + (idx.kind == EX_ALL ? "all" : idx.kind == EX_LIST ? "list" : "range") + "> " +
+  g_last_plan = std::string("extract_col<") + (dv.tran0 ? "row of the CSR" : "column of the CSR") + ",index=" + kind_name(idx) + "> " +
                 (scatter ? "k_extract_row_scatter " : "k_extract_lookup ");
   vector_write_back(w, A->type->code, tval, tpres, allow, accum, dv.replace, false);
 }
@@ -379,25 +384,23 @@ constexpr uint64_t ASSIGN_DEVICE_MIN_ENTRIES = 30000;            // GrB_Matrix_a
 constexpr uint64_t ASSIGN_ROW_DEVICE_MIN_ENTRIES = 3000000;      // GrB_Row_assign: the host replaces the row's run of tuples in place, cheap up to ~1e6 entries
 constexpr uint64_t ASSIGN_COL_DEVICE_MIN_ENTRIES = 100000;       // GrB_Col_assign: the host's one merge pass
 constexpr uint64_t ASSIGN_VEC_DEVICE_MIN_ENTRIES = 500;          // GrB_Vector_assign: the host route is map-based for every shape (the smallest size measured; the device route won all)
-int assign_env() { const char* e = getenv("GRB_MI355X_ASSIGN"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }
 uint64_t entries_known(GrB_Vector u) { return u->host_valid ? vec_nvals(u) : (u->dnvals_known ? u->dnvals : 0); }      // (no device work for a count)
 // `operand_entries`: asked only after the variable, the device and the residency of C have not decided
 template <class F> bool assign_on_device(GrB_Matrix C, bool others_capable, uint64_t min_entries, F&& operand_entries) {
-  const int env = assign_env();
+  const int env = route_env("GRB_MI355X_ASSIGN");
   if (env == 0 || !device_ok() || !others_capable || !dev_capable(C) || mat_bitmap_only(C)) return false;
   if (env == 1) return true;
   if (C->dev_valid && !C->host_valid) return true;                      // it lives in HBM: it is not downloaded for this
   return mat_nvals(C) >= min_entries || operand_entries() >= min_entries;
 }
 template <class F> bool assign_on_device(GrB_Vector w, bool others_capable, uint64_t min_entries, F&& operand_entries) {
-  const int env = assign_env();
+  const int env = route_env("GRB_MI355X_ASSIGN");
   if (env == 0 || !device_ok() || !others_capable || !dev_capable(w)) return false;
   if (env == 1) return true;
   if (w->dev_valid && !w->host_valid) return true;
   return entries_known(w) >= min_entries || operand_entries() >= min_entries;
 }
 bool mat_capable(GrB_Matrix A) { return dev_capable(A) && !(A && mat_bitmap_only(A)); }
-const char* kind_name(const ExIdx& x) { return x.kind == EX_ALL ? "all" : x.kind == EX_LIST ? "list" : "range"; }
 const char* accum_name(GrB_BinaryOp accum) { return accum ? accum->name : "none"; }
 
 // C(I, J) := T (T in C's coordinates, nothing outside I x J), then C<M, replace> = that: Z = (C without its entries inside I x J) u T, written back
@@ -504,11 +507,10 @@ bool assign_line_device(GrB_Matrix C, GrB_Vector mask, GrB_BinaryOp accum, GrB_V
 // GRB_MI355X_KRON_TIME=1 puts HIP events around the fill kernel; GrBX_kron_fill_ms returns what they measured (tools/kron_probe.py).
 constexpr uint64_t KRON_DEVICE_MIN_ENTRIES = 1000;              // provisional: reasoned from the assign route's fixed cost, not yet measured
 thread_local float g_kron_fill_ms = 0.0f;
-int kron_env() { const char* e = getenv("GRB_MI355X_KRON"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }
 bool hbm_only(GrB_Matrix A) { return A->dev_valid && !A->host_valid; }
 uint64_t entries_of(GrB_Matrix A) { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }      // (the count of a valid host mirror, or of the device CSR: no device work)
 bool kron_on_device(GrB_Matrix C, GrB_Matrix Mask, GrB_Matrix A, GrB_Matrix B, const DescView& dv) {
-  const int env = kron_env();
+  const int env = route_env("GRB_MI355X_KRON");
   if (env == 0 || !device_ok() || !mat_capable(C) || !mat_capable(A) || !mat_capable(B) || !mat_capable(Mask)) return false;
   if (A == C || B == C || (!Mask && dv.mask_comp)) return false;
   if (C->nrows > GRB_DIM_DEVICE_MAX || C->ncols > GRB_DIM_DEVICE_MAX) return false;

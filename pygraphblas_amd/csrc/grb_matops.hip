@@ -7,14 +7,13 @@
 // merge of (row, column) keys): a power-law graph has rows of 10^5 entries, and kernels that give a row to one thread ran at
 // 1-2 G entries/s on R-MAT-22.  The heavy lifting of the hot path is in grb_spgemm.hip / grb_spmv_kernels.hpp, not here.
 #include "grb_api.hpp"
-#include "grb_device.hpp"
+#include "grb_index.hpp"
 #include "grb_atomics.hpp"
 #include "grb_matops.hpp"
 
 namespace grb {
 
 static inline unsigned grid_rows(uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 65535u * 16) b = 65535u * 16; return (unsigned)b; }
-static inline unsigned grid_n(uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (unsigned)b; }
 
 // ---- mask helpers --------------------------------------------------------------------------------------------
 // truth of mask entry p (valued mask: stored AND non-zero; structural: stored)
@@ -40,14 +39,38 @@ __device__ __forceinline__ bool mask_truth(const void* mval, int mcode, uint32_t
 //                       merged entries before row r is arp[r] + brp[r], so the new row pointers are a gather from the scan;
 //   write-back          Z = accum(C, T) as a union, Z restricted to the mask by compaction, C's entries outside the mask kept
 //                       (unless replace) by a second compaction, the two disjoint parts merged.
+// (A thread per row writing its entries one after the other took 7.2 ms on the symmetric R-MAT-22 — its hub rows hold 10^5 entries — of the 28 ms a BFS's
+// first run spent building the transpose.)
 static __global__ void k_mark_row_starts(const uint32_t* __restrict__ rowptr, uint32_t nrows, uint32_t* __restrict__ rowidx) {
   for (uint64_t r = blockIdx.x * 256ull + threadIdx.x; r < nrows; r += (uint64_t)gridDim.x * 256ull) { const uint32_t s = rowptr[r]; if (rowptr[r + 1] > s) rowidx[s] = (uint32_t)r; }
 }
 void csr_row_indices(const DevCSR& A, uint32_t* rowidx) {
   if (!A.nnz) return;
   GRB_HIP(hipMemsetAsync(rowidx, 0, A.nnz * 4, stream()));
-  hipLaunchKernelGGL(k_mark_row_starts, dim3(grid_n(A.nrows)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), A.nrows, rowidx);
+  hipLaunchKernelGGL(k_mark_row_starts, dim3(grid_1d(A.nrows)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), A.nrows, rowidx);
   inclusive_scan_max_u32(rowidx, rowidx, A.nnz);
+}
+
+// ---- moving values through a permutation: the tail of every "fill unordered, then sort" (extract, assign), the iota also csr_transpose's ----
+static __global__ void k_iota(uint32_t* p, uint64_t n) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) p[i] = (uint32_t)i;
+}
+template <int TS> __global__ void k_gather_values(const uint32_t* __restrict__ perm, uint64_t n, const uint8_t* __restrict__ val, uint8_t* __restrict__ oval) {
+  typedef typename WordOf<TS>::type W;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) ((W*)oval)[i] = ((const W*)val)[perm[i]];
+}
+void fill_iota_u32(uint32_t* p, uint64_t n) { hipLaunchKernelGGL(k_iota, dim3(grid_1d(n)), dim3(256), 0, stream(), p, n); }
+void gather_values(size_t ts, const uint32_t* perm, uint64_t n, const void* in, void* out) {
+  dispatch_value_size(ts, [&]<int TS>() { hipLaunchKernelGGL((k_gather_values<TS>), dim3(grid_1d(n)), dim3(256), 0, stream(), perm, n, (const uint8_t*)in, (uint8_t*)out); });
+}
+void csr_sort_rows(DevCSR& T, size_t ts, const DevBuf& ucol, const DevBuf& uval, uint64_t ncols) {
+  const uint64_t n = T.nnz;
+  DevBuf iota(n * 4), perm(n * 4);
+  fill_iota_u32(iota.as<uint32_t>(), n);
+  int bits = 1; while (bits < 32 && (1ull << bits) < ncols) bits++;
+  segmented_sort_pairs_u32(ucol.as<uint32_t>(), T.col.as<uint32_t>(), iota.as<uint32_t>(), perm.as<uint32_t>(), n, T.nrows, T.rowptr.as<uint32_t>(), T.rowptr.as<uint32_t>() + 1, bits);
+  gather_values(ts, perm.as<uint32_t>(), n, uval.p, T.val.p);
+  GRB_HIP(hipStreamSynchronize(stream()));                                   // (iota / perm return to the pool)
 }
 
 static __global__ void k_keep_to_u32(const uint8_t* __restrict__ keep, uint64_t n, uint32_t* __restrict__ out) {
@@ -58,7 +81,7 @@ static __global__ void k_gather_rowptr(const uint32_t* __restrict__ rowptr, uint
 }
 template <int TS> __global__ void k_compact_entries(uint64_t n, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ col, const uint8_t* __restrict__ val,
                                                     uint32_t* __restrict__ ocol, uint8_t* __restrict__ oval) {
-  typedef typename std::conditional<TS == 8, uint64_t, typename std::conditional<TS == 4, uint32_t, typename std::conditional<TS == 2, uint16_t, uint8_t>::type>::type>::type W;
+  typedef typename WordOf<TS>::type W;
   for (uint64_t p = blockIdx.x * 256ull + threadIdx.x; p < n; p += gridDim.x * 256ull) if (keep[p]) { const uint32_t w = pos[p]; ocol[w] = col[p]; ((W*)oval)[w] = ((const W*)val)[p]; }
 }
 void csr_compact(const DevCSR& A, const void* aval, size_t ts, const uint8_t* keep, DevCSR& out) {
@@ -66,17 +89,16 @@ void csr_compact(const DevCSR& A, const void* aval, size_t ts, const uint8_t* ke
   out.clear(); out.nrows = nrows; out.ncols = A.ncols;
   out.rowptr.alloc(((size_t)nrows + 1) * 4);
   DevBuf flags((n + 1) * 4 + 4), pos((n + 1) * 4 + 4);
-  hipLaunchKernelGGL(k_keep_to_u32, dim3(grid_n(n + 1)), dim3(256), 0, stream(), keep, n, flags.as<uint32_t>());
+  hipLaunchKernelGGL(k_keep_to_u32, dim3(grid_1d(n + 1)), dim3(256), 0, stream(), keep, n, flags.as<uint32_t>());
   exclusive_scan_u32(flags.as<uint32_t>(), pos.as<uint32_t>(), n + 1);
-  hipLaunchKernelGGL(k_gather_rowptr, dim3(grid_n((uint64_t)nrows + 1)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), nrows, pos.as<uint32_t>(), out.rowptr.as<uint32_t>());
+  hipLaunchKernelGGL(k_gather_rowptr, dim3(grid_1d((uint64_t)nrows + 1)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), nrows, pos.as<uint32_t>(), out.rowptr.as<uint32_t>());
   uint32_t total = 0;
   GRB_HIP(hipMemcpyAsync(&total, pos.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
   out.nnz = total; out.col.alloc((size_t)total * 4 + 4); out.val.alloc((size_t)total * ts + 8);
   if (n) {
-#define GRB_COMPACT(TS) hipLaunchKernelGGL((k_compact_entries<TS>), dim3(grid_n(n)), dim3(256), 0, stream(), n, keep, pos.as<uint32_t>(), A.col.as<uint32_t>(), (const uint8_t*)aval, \
-                                           out.col.as<uint32_t>(), out.val.as<uint8_t>())
-    switch (ts) { case 1: GRB_COMPACT(1); break; case 2: GRB_COMPACT(2); break; case 4: GRB_COMPACT(4); break; default: GRB_COMPACT(8); break; }
-#undef GRB_COMPACT
+    dispatch_value_size(ts, [&]<int TS>() {
+      hipLaunchKernelGGL((k_compact_entries<TS>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, keep, pos.as<uint32_t>(), A.col.as<uint32_t>(), (const uint8_t*)aval, out.col.as<uint32_t>(), out.val.as<uint8_t>());
+    });
   }
   GRB_HIP(hipGetLastError());
   GRB_HIP(hipStreamSynchronize(stream()));       // flags / pos return to the pool
@@ -95,7 +117,7 @@ void select_positional_flags(const DevCSR& A, int sel, int64_t k, uint8_t* keep)
   if (!A.nnz) return;
   DevBuf rowidx(A.nnz * 4 + 4);
   csr_row_indices(A, rowidx.as<uint32_t>());
-  hipLaunchKernelGGL(k_select_positional, dim3(grid_n(A.nnz)), dim3(256), 0, stream(), A.nnz, rowidx.as<uint32_t>(), A.col.as<uint32_t>(), sel, k, keep);
+  hipLaunchKernelGGL(k_select_positional, dim3(grid_1d(A.nnz)), dim3(256), 0, stream(), A.nnz, rowidx.as<uint32_t>(), A.col.as<uint32_t>(), sel, k, keep);
   GRB_HIP(hipStreamSynchronize(stream()));
 }
 
@@ -114,7 +136,7 @@ static void mask_flags_ex(const DevCSR& Tm, const DevCSR& M, int mcode, bool mst
   if (!Tm.nnz) return;
   DevBuf rowidx(Tm.nnz * 4 + 4);
   csr_row_indices(Tm, rowidx.as<uint32_t>());
-  hipLaunchKernelGGL(k_mask_flags, dim3(grid_n(Tm.nnz)), dim3(256), 0, stream(), Tm.nnz, rowidx.as<uint32_t>(), Tm.col.as<uint32_t>(), M.rowptr.as<uint32_t>(), M.col.as<uint32_t>(), M.val.p, mcode,
+  hipLaunchKernelGGL(k_mask_flags, dim3(grid_1d(Tm.nnz)), dim3(256), 0, stream(), Tm.nnz, rowidx.as<uint32_t>(), Tm.col.as<uint32_t>(), M.rowptr.as<uint32_t>(), M.col.as<uint32_t>(), M.val.p, mcode,
                      mstruct, mcomp, invert, keep);
   GRB_HIP(hipStreamSynchronize(stream()));
 }
@@ -173,13 +195,13 @@ static bool ewise_merge(const DevCSR& A, const DevCSR& B, bool is_union, DevCSR&
   DevBuf ka(na * 8 + 8), kb(nb * 8 + 8), ia(na * 4 + 4), ib(nb * 4 + 4);
   mg.km.alloc(n * 8 + 8); mg.im.alloc(n * 4 + 4); mg.e.alloc((n + 1) * 4 + 4); mg.pos.alloc((n + 1) * 4 + 4);
   { DevBuf rowidx((na > nb ? na : nb) * 4 + 4);
-    if (na) { csr_row_indices(A, rowidx.as<uint32_t>()); hipLaunchKernelGGL(k_entry_keys, dim3(grid_n(na)), dim3(256), 0, stream(), na, rowidx.as<uint32_t>(), A.col.as<uint32_t>(), 0u, (unsigned long long*)ka.p, ia.as<uint32_t>()); }
-    if (nb) { csr_row_indices(B, rowidx.as<uint32_t>()); hipLaunchKernelGGL(k_entry_keys, dim3(grid_n(nb)), dim3(256), 0, stream(), nb, rowidx.as<uint32_t>(), B.col.as<uint32_t>(), 0x80000000u, (unsigned long long*)kb.p, ib.as<uint32_t>()); }
+    if (na) { csr_row_indices(A, rowidx.as<uint32_t>()); hipLaunchKernelGGL(k_entry_keys, dim3(grid_1d(na)), dim3(256), 0, stream(), na, rowidx.as<uint32_t>(), A.col.as<uint32_t>(), 0u, (unsigned long long*)ka.p, ia.as<uint32_t>()); }
+    if (nb) { csr_row_indices(B, rowidx.as<uint32_t>()); hipLaunchKernelGGL(k_entry_keys, dim3(grid_1d(nb)), dim3(256), 0, stream(), nb, rowidx.as<uint32_t>(), B.col.as<uint32_t>(), 0x80000000u, (unsigned long long*)kb.p, ib.as<uint32_t>()); }
     GRB_HIP(hipStreamSynchronize(stream())); }
   merge_pairs_u64((const uint64_t*)ka.p, (const uint64_t*)kb.p, (uint64_t*)mg.km.p, ia.as<uint32_t>(), ib.as<uint32_t>(), mg.im.as<uint32_t>(), na, nb);
-  hipLaunchKernelGGL(k_merge_emit, dim3(grid_n(n + 1)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, is_union, mg.e.as<uint32_t>());
+  hipLaunchKernelGGL(k_merge_emit, dim3(grid_1d(n + 1)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, is_union, mg.e.as<uint32_t>());
   exclusive_scan_u32(mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), n + 1);
-  hipLaunchKernelGGL(k_merge_rowptr, dim3(grid_n((uint64_t)nrows + 1)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), B.rowptr.as<uint32_t>(), nrows, mg.pos.as<uint32_t>(), out.rowptr.as<uint32_t>());
+  hipLaunchKernelGGL(k_merge_rowptr, dim3(grid_1d((uint64_t)nrows + 1)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), B.rowptr.as<uint32_t>(), nrows, mg.pos.as<uint32_t>(), out.rowptr.as<uint32_t>());
   uint32_t total = 0;
   GRB_HIP(hipMemcpyAsync(&total, mg.pos.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
   out.nnz = total;
@@ -191,7 +213,7 @@ void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, con
   const uint64_t n = mg.n, total = out.nnz;
   dispatch_type(code, [&]<class T>() {
     out.col.alloc((size_t)total * 4 + 4); out.val.alloc((size_t)total * sizeof(T) + 8);
-#define GRB_EW_FILL(MATH) hipLaunchKernelGGL((k_merge_fill<T, MATH>), dim3(grid_n(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
+#define GRB_EW_FILL(MATH) hipLaunchKernelGGL((k_merge_fill<T, MATH>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
                                              (const T*)aval, (const T*)bval, op, out.col.as<uint32_t>(), out.val.as<T>())
     if (binop_needs_math(op)) GRB_EW_FILL(true); else GRB_EW_FILL(false);
 #undef GRB_EW_FILL
@@ -207,7 +229,7 @@ void csr_ewise_aligned(int code, const DevCSR& A, const void* aval, const DevCSR
   const uint64_t n = mg.n, total = out.nnz;
   out.col.alloc((size_t)total * 4 + 4); out.val.alloc((size_t)total * ts + 16);
   xval.alloc((size_t)total * ts + 16); yval.alloc((size_t)total * ts + 16); both.alloc((size_t)total + 16);
-#define GRB_EW_ALIGN(W) hipLaunchKernelGGL((k_merge_align<W>), dim3(grid_n(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
+#define GRB_EW_ALIGN(W) hipLaunchKernelGGL((k_merge_align<W>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
                                            (const W*)aval, (const W*)bval, out.col.as<uint32_t>(), xval.as<W>(), yval.as<W>(), both.as<uint8_t>())
   switch (ts) { case 1: GRB_EW_ALIGN(uint8_t); break; case 2: GRB_EW_ALIGN(uint16_t); break; case 4: GRB_EW_ALIGN(uint32_t); break; default: GRB_EW_ALIGN(uint64_t); break; }
 #undef GRB_EW_ALIGN
@@ -381,7 +403,7 @@ void csr_position_values(int zcode, const DevCSR& A, int which, void* out) {
   if (!A.nnz) return;
   DevBuf rowidx; const uint32_t* src = A.col.as<uint32_t>();
   if (which < 2) { rowidx.alloc(A.nnz * 4 + 4); csr_row_indices(A, rowidx.as<uint32_t>()); src = rowidx.as<uint32_t>(); }
-  const unsigned g = grid_n(A.nnz);
+  const unsigned g = grid_1d(A.nnz);
   if (zcode == T_INT32) hipLaunchKernelGGL((k_u32_to_index<int32_t>), dim3(g), dim3(256), 0, stream(), src, A.nnz, (int32_t)(which & 1), (int32_t*)out);
   else hipLaunchKernelGGL((k_u32_to_index<int64_t>), dim3(g), dim3(256), 0, stream(), src, A.nnz, (int64_t)(which & 1), (int64_t*)out);
   GRB_HIP(hipGetLastError());
@@ -389,7 +411,7 @@ void csr_position_values(int zcode, const DevCSR& A, int which, void* out) {
 // the same for a vector (an n x 1 column): row = the index, column = 0
 void vec_position_values(int zcode, uint64_t n, int which, void* out) {
   if (!n) return;
-  const unsigned g = grid_n(n);
+  const unsigned g = grid_1d(n);
   if (zcode == T_INT32) hipLaunchKernelGGL((k_index_fill<int32_t>), dim3(g), dim3(256), 0, stream(), n, which, (int32_t*)out);
   else hipLaunchKernelGGL((k_index_fill<int64_t>), dim3(g), dim3(256), 0, stream(), n, which, (int64_t*)out);
   GRB_HIP(hipGetLastError());

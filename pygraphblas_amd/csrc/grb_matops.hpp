@@ -20,7 +20,11 @@ void csr_reduce_rows(int code, const DevCSR& A, const void* aval, int op, void* 
 bool csr_reduce_cols(int code, const DevCSR& A, const void* aval, int op, const void* identity, void* tval, uint8_t* tpres);
 bool csr_reduce_cols_few_rows(int code, const DevCSR& A, const void* aval, int op, void* tval, uint8_t* tpres);   // <= 64 rows, FP types: row after row, fixed order, no atomics
 uint64_t csr_find_entry(const DevCSR& A, uint32_t i, uint32_t j);        // position of (i, j) in col / val, ~0 when not stored (one host round trip)
-void csr_row_indices(const DevCSR& A, uint32_t* rowidx);
+void csr_row_indices(const DevCSR& A, uint32_t* rowidx);       // rowidx[p] = row of entry p
+void fill_iota_u32(uint32_t* p, uint64_t n);                   // p[i] = i
+void gather_values(size_t ts, const uint32_t* perm, uint64_t n, const void* in, void* out);      // out[i] = in[perm[i]], values of `ts` bytes (1, 2, 4, 8)
+// T.col / T.val from the unsorted copies `ucol` / `uval`, every row of T.rowptr put in column order (columns < ncols): the tail of a fill that does not keep rows sorted
+void csr_sort_rows(DevCSR& T, size_t ts, const DevBuf& ucol, const DevBuf& uval, uint64_t ncols);
 void csr_dense_fill(uint32_t nrows, uint32_t ncols, const void* scalar, size_t ts, DevCSR& out);     // every position holds `scalar`: rowptr[i] = i ncols, col[e] = e mod ncols
 // positional unary operators (GxB_POSITIONI / I1 / J / J1): the row (which 0 / 1: + 1) or column (2 / 3) index of every entry of A as INT32 / INT64 values; the same for the n positions of a vector
 void csr_position_values(int zcode, const DevCSR& A, int which, void* out);
