@@ -60,6 +60,19 @@ def build_range(rslice, stop_val):
     return _p(keep), ni, size, keep
 
 
+_diag_min = None
+
+
+def _diag_matrix_min_entries():
+    """Entries from which `GxB_Matrix_diag` takes its device route (the library's own number: GrBX_diag_thresholds); infinite without a device."""
+    global _diag_min
+    if _diag_min is None:
+        a, b = u64(0), u64(0)
+        check(lib.GrBX_diag_thresholds(C.byref(a), C.byref(b)))
+        _diag_min = a.value if _capi.device_info()["ok"] else float("inf")
+    return _diag_min
+
+
 class Matrix:
     _kind = "matrix"
 
@@ -288,8 +301,12 @@ class Matrix:
 
     @classmethod
     def identity(cls, typ, nrows, one=None):
+        one = typ.default_one if one is None else one
+        if nrows >= _diag_matrix_min_entries():               # a fill and the all-present path of from_diag in HBM: no tuples on the host
+            from .vector import Vector
+            return cls.from_diag(Vector.dense(typ, nrows, fill=one))
         idx = np.arange(nrows, dtype=np.uint64)
-        return cls.from_arrays(idx, idx, np.full(nrows, typ.default_one if one is None else one, typ._np), nrows, nrows, typ)
+        return cls.from_arrays(idx, idx, np.full(nrows, one, typ._np), nrows, nrows, typ)
 
     @classmethod
     def random(cls, typ, nvals, nrows=None, ncols=None, make_pattern=False, make_symmetric=False, make_skew_symmetric=False,
@@ -730,6 +747,10 @@ class Matrix:
 
     def triu(self, thunk=None):
         return self.select("TRIU", thunk)
+
+    def diag(self, thunk=None):
+        """The entries of the `thunk`-th diagonal, as a matrix of the same shape (reference: matrix.py:2202-2230)."""
+        return self.select("DIAG", thunk)
 
     def offdiag(self, thunk=None):
         return self.select("OFFDIAG", thunk)
