@@ -11,7 +11,7 @@
 // the C<M,replace> = accum(C,T) write-back, so the output may alias any input.
 #include "grb_opcommon.hpp"
 #include "grb_matops.hpp"
-#include "grb_extract.hpp"
+#include "grb_assign_scalar.hpp"
 #include "grb_lazy.hpp"
 
 using namespace grb;
@@ -321,7 +321,45 @@ void do_reduce_vector(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Mon
   vector_write_back(w, mc, tval, tpres, allow, accum, dv.replace, false);
 }
 
-// C<M>(I,J) = accum(C(I,J), x): built as a T with the scalar at every (i,j) of I x J, then assign semantics
+// ---- C<M>(I,J) = accum(C(I,J), x): a T that holds the scalar wherever the write-back may read it, then assign semantics ----------------------------
+// The device routes (grb_assign_scalar.hip) build T in HBM from the index arguments as they are — GrB_ALL and ranges never expanded, explicit lists uploaded once
+// and inverted by assign_inverse:
+//   mask=pattern       a mask object without GrB_COMP: T = M's true entries inside I x J.  The write-back reads T only where M allows a write, so this T and the
+//                      full block give the same C — at O(nnz(M) + nnz(C)) whatever |I| |J| is, and with no limit on the region.
+//   mask=none | comp   T = all of I x J in closed form; |I| |J| <= SCALAR_REGION_MAX as ever.
+// A list that names an index twice, a list over more than ASSIGN_TABLE_MAX_DIM positions, a complex valued mask and GRB_MI355X_ASSIGN_SCALAR=0 (read per
+// call: a test hook, and the yardstick of tools/assign_scalar_probe.py) keep the host-built block below.  There is no size threshold: measured from 1e2 positions
+// up, the device block never loses to the host-built one by more than the spread between runs.
+const char* scalar_kind_name(const ExIdx& x) { return x.kind == EX_ALL ? "all" : x.kind == EX_LIST ? "list" : "range"; }
+
+// the write-back of every route: assign keeps the entries of C outside the region, and inside it T's replace C's — that is accum = SECOND on the union of
+// the patterns when the caller gave no accumulator
+void scalar_write_back(GrB_Matrix C, DevCSR& T, GrB_Matrix M, const DescView& dv, GrB_BinaryOp accum, bool t_masked) {
+  GrB_BinaryOp_opaque second{GRB_MAGIC, B_SECOND, C->type, C->type, C->type, "assign_second", nullptr};
+  matrix_write_back(C, T, C->type->code, M, dv, accum ? accum : &second, t_masked);
+}
+
+// false: nothing was written and the caller takes the host-built block (which raises the same errors in the same order)
+bool assign_scalar_device(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, const DescView& dv) {
+  const char* e = getenv("GRB_MI355X_ASSIGN_SCALAR");
+  if (e && *e && atoi(e) == 0) return false;
+  const bool pattern = M && !dv.mask_comp;
+  if (pattern && !dv.mask_struct && M->type->code >= T_FC32) return false;
+  ExIdx ri, ci; extract_parse(ri, I, ni, C->nrows, "assign (rows)"); extract_parse(ci, J, nj, C->ncols, "assign (columns)");
+  if (!pattern && !scalar_region_fits(ri.n, ci.n)) fail(GrB_OUT_OF_MEMORY, "assign: region too large");
+  DevBuf keep_i, keep_j, inv_i, inv_j; extract_upload(ri, keep_i); extract_upload(ci, keep_j);
+  if (!assign_inverse(ri, C->nrows, inv_i) || !assign_inverse(ci, C->ncols, inv_j)) return false;
+  const int ccode = C->type->code; const size_t ts = C->type->size;
+  uint8_t s[16]; cast_scalar(ccode, s, xcode, x);
+  DevCSR T;
+  if (pattern) { mat_to_device(M); scalar_from_mask(M->csr, M->type->code, dv.mask_struct, ri, inv_i, ci, inv_j, s, ts, T); }      // (M may be C itself: T is complete before the write-back starts)
+  else scalar_block((uint32_t)C->nrows, (uint32_t)C->ncols, ri, inv_i, ci, inv_j, s, ts, T);
+  g_last_plan = std::string("assign_scalar<rows=") + scalar_kind_name(ri) + ",cols=" + scalar_kind_name(ci) + ",mask=" + (pattern ? "pattern" : dv.mask_comp ? "comp" : "none") + ",accum=" + (accum ? accum->name : "none") + "> " +
+                (pattern ? "k_assign_scalar_flags csr_compact k_assign_scalar_fill<values> " : "k_assign_scalar_rowflag k_assign_scalar_rowptr k_assign_scalar_fill<block> ") + "entries=" + std::to_string(T.nnz) + " ";
+  scalar_write_back(C, T, M, dv, accum, pattern);
+  return true;
+}
+
 void do_assign_scalar(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, GrB_Descriptor desc) {
   // no HBM layout for this container (hypersparse dimensions, or complex entries): bookkeeping on the host mirror
   if (C->nrows > GRB_DIM_DEVICE_MAX || C->ncols > GRB_DIM_DEVICE_MAX || C->type->code >= T_FC32) { host_assign_scalar(C, M, accum, x, xcode, I, ni, J, nj, desc); return; }
@@ -335,6 +373,8 @@ void do_assign_scalar(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const void
     adopt(C, T, C->type->code);
     return;
   }
+  if (assign_scalar_device(C, M, accum, x, xcode, I, ni, J, nj, dv)) return;
+  // ---- the host-built block: the fallback, and the yardstick ----
   // (indices are validated as 64-bit values before they are narrowed to the device layout's 32 bits)
   const std::vector<uint64_t> rows64 = expand_index_list(I, ni, C->nrows, "assign (rows)"), cols64 = expand_index_list(J, nj, C->ncols, "assign (columns)");
   std::vector<uint32_t> rows(rows64.begin(), rows64.end()), cols(cols64.begin(), cols64.end());
@@ -358,11 +398,7 @@ void do_assign_scalar(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const void
   if (!cc.empty()) { GRB_HIP(hipMemcpyAsync(T.col.p, cc.data(), cc.size() * 4, hipMemcpyHostToDevice, stream()));
                      GRB_HIP(hipMemcpyAsync(T.val.p, vv.data(), vv.size(), hipMemcpyHostToDevice, stream())); }
   GRB_HIP(hipStreamSynchronize(stream())); T.valid = true;
-  // assign keeps entries of C outside the region: Z = C with the region overwritten (or accumulated).
-  // Expressed with the write-back merge by using FIRST/SECOND-style accumulation: with no accum the
-  // region entries replace C's, entries of C outside stay => that is accum = SECOND on the union.
-  GrB_BinaryOp_opaque second{GRB_MAGIC, B_SECOND, C->type, C->type, C->type, "assign_second", nullptr};
-  matrix_write_back(C, T, ccode, M, dv, accum ? accum : &second, false);
+  scalar_write_back(C, T, M, dv, accum, false);
 }
 
 }  // namespace

@@ -91,12 +91,17 @@ class Matrix:
 
     # ---- construction ---------------------------------------------------------------------------------
     @classmethod
-    def sparse(cls, typ, nrows=None, ncols=None):
+    def sparse(cls, typ, nrows=None, ncols=None, fill=None, mask=None):
+        """An empty matrix; with `mask`, one that holds `fill` (default: the type's zero) where the mask is true — `fill` without a mask is ignored
+        (reference: matrix.py:120-181)."""
         imax = _capi.constants["GxB_INDEX_MAX"]
         h = C.c_void_p()
         check(lib.GrB_Matrix_new(C.byref(h), C.c_void_p(typ._h), u64(imax if nrows is None else nrows),
                                  u64(imax if ncols is None else ncols)))
-        return cls(h, typ)
+        m = cls(h, typ)
+        if mask is not None:
+            m.assign_scalar(typ.default_zero if fill is None else fill, mask=mask)
+        return m
 
     @classmethod
     def dense(cls, typ, nrows, ncols, fill=None):
@@ -406,12 +411,20 @@ class Matrix:
         return iter(zip(I.tolist(), J.tolist(), X.tolist()))
 
     def __setitem__(self, index, value):
-        """`M[i, j] = x`, `M[i] = v` / `M[i, :] = v` (row), `M[:, j] = v` (column), `M[I, J] = A` (sub-matrix) — reference: matrix.py:3236-3330."""
+        """`M[i, j] = x`, `M[i] = v` / `M[i, :] = v` (row), `M[:, j] = v` (column), `M[I, J] = A` (sub-matrix), `M[Mask] = A` (masked), and a scalar
+        in place of the vector or matrix: `M[i] = s`, `M[a:b] = s`, `M[i, J] = s`, `M[I, j] = s`, `M[I, J] = s`, `M[Mask] = s` — reference: matrix.py:3236-3330."""
         from .vector import Vector
+        scalar = isinstance(value, (bool, int, float, complex, np.generic))
         if isinstance(index, int):
-            return self.assign_row(index, value)
+            return self.assign_scalar(value, index) if scalar else self.assign_row(index, value)
         if isinstance(index, slice):
-            return self.assign_matrix(value, index, None)
+            return self.assign_scalar(value, index, None) if scalar else self.assign_matrix(value, index, None)
+        if isinstance(index, Matrix):
+            if isinstance(value, Matrix):
+                return self.assign_matrix(value, mask=index)
+            if not scalar:
+                raise TypeError("a masked assignment takes a matrix or a scalar")
+            return self.assign_scalar(value, mask=index)
         i, j = index
         if isinstance(i, int) and isinstance(j, int):
             fn = getattr(lib, "GrB_Matrix_setElement_" + self.type.__name__)
@@ -422,6 +435,8 @@ class Matrix:
             self.assign_col(j, value, i)
         elif isinstance(value, Matrix):
             self.assign_matrix(value, i, j)
+        elif scalar:
+            self.assign_scalar(value, i, j)
         else:
             raise TypeError("unsupported index / value combination")
 
@@ -718,6 +733,21 @@ class Matrix:
         check(lib.GrB_Matrix_assign(self._h, mh, ah, value._h, I, u64(ni), J, u64(nj), dh), self)
 
     assign = assign_matrix
+
+    def assign_scalar(self, value, row_slice=None, col_slice=None, mask=None, accum=None, desc=None):
+        """`C(I,J)<mask> = accum(C(I,J), value)` (reference: pygraphblas/matrix.py:3106-3239): `None` is every row / column, an int that one, a slice
+        includes its stop, a list names explicit indices.  T is built in HBM (grb_assign_scalar.hip): from the mask's pattern when there is a mask that is
+        not complemented — `A[M] = s` costs O(nvals(M) + nvals(A)) whatever the region's size —, else as the block in closed form."""
+        mh, ah, dh = get_args(mask, accum, desc)
+        if isinstance(row_slice, (int, np.integer)):
+            row_slice = slice(int(row_slice), int(row_slice))
+        if isinstance(col_slice, (int, np.integer)):
+            col_slice = slice(int(col_slice), int(col_slice))
+        I, ni, _s1, k1 = build_range(row_slice, self.nrows - 1); J, nj, _s2, k2 = build_range(col_slice, self.ncols - 1)
+        fn = self.type.__dict__.get("_matrix_assign_fn")
+        if fn is None:
+            fn = getattr(lib, "GrB_Matrix_assign_" + self.type.__name__); setattr(self.type, "_matrix_assign_fn", fn)      # (looked up once per type)
+        check(fn(self._h, mh, ah, self.type._c(value), I, u64(ni), J, u64(nj), dh), self)
 
     def select(self, op, thunk=None, out=None, mask=None, accum=None, desc=None):
         """`GxB_Matrix_select` with a built-in select operator name ("TRIL", ">0", ...) or a `@select_op` operator (reference: matrix.py:2042-2140)."""
