@@ -12,6 +12,8 @@
 #include "grb_device.hpp"
 #include "grb_matops.hpp"
 #include "grb_userop.hpp"
+#include "grb_edit.hpp"
+#include "grb_edit_list.hpp"
 #include <algorithm>
 #include <numeric>
 #include <string.h>
@@ -68,10 +70,70 @@ void mat_invalidate_host(GrB_Matrix A) {
   A->csr.heads_valid = false; A->csr.range_state = 0;      // (the device copy was rewritten: whatever was derived from its values goes with the plans)
 }
 
+// ---- the edit queue of a container that lives in HBM only ------------------------------------------------------------------------------
+// `A[i, j] = x`, `del A[i, j]`, `v[i] = x` on a container whose only valid image is the HBM one append today's Pending record and nothing else: no download, nothing
+// invalidated.  The queue is applied on the device (grb_edit.hip) before anything reads or replaces that image: mat_to_device / mat_to_host / mat_nvals / dup / wait /
+// resize for matrices, vec_gate (which every reader of a vector passes) for vectors; extractElement looks in the queue first.  Whoever replaces the image as a whole
+// clears `pending` (mat_invalidate_host, GrB_Matrix_clear, the vector drivers).  GRB_MI355X_EDIT=0 forces the host route everywhere.
+// The plan string of a flush goes IN FRONT of what the plan holds: most flushes run inside an operation (mat_to_device / mat_nvals / vec_gate of its operands and
+// output), whose own plan stays behind it.  The entry points that are flush points of their own (nvals, wait, dup, extractElement, extractTuples) start from an
+// empty plan when edits are queued.
+static bool edit_env_off() { const char* e = getenv("GRB_MI355X_EDIT"); return e && *e && atoi(e) == 0; }
+static bool mat_edit_route(GrB_Matrix A) {
+  return A->dev_valid && !A->host_valid && !A->iso_full && A->csr.valid && A->type->code < T_FC32 && A->nrows <= GRB_DIM_DEVICE_MAX && A->ncols <= GRB_DIM_DEVICE_MAX &&
+         device_ok() && !edit_env_off();
+}
+static bool vec_edit_route(GrB_Vector v) {
+  return v->dev_valid && !v->host_valid && !v->iso_full && v->lazy == 0 && v->q_reads == 0 && v->type->code < T_FC32 && v->n <= GRB_DIM_DEVICE_MAX && device_ok() && !edit_env_off();
+}
+// what was derived from the structure of the device CSR (the list of mat_invalidate_host, and the bitmap cache)
+static void mat_drop_derived(GrB_Matrix A) {
+  A->csc.clear(); A->bm.clear(); A->csr.has_plan = false; A->csr.plan_blocks.reset(); A->csr.plan_aux.reset();
+  A->csr.wp_rs.reset(); A->csr.wp_hot.reset(); A->csr.wp_pcol.reset(); A->csr.wp_tsize = 0; A->csr.xcd.reset();
+  A->csr.heads_valid = false; A->csr.range_state = 0; A->csr.locality_pct = -1; A->csr.pipe_uses = 0;
+}
+// every cached fact about the device image of a vector (the list of vec_invalidate_device); the entry count is recounted when asked for
+static void vec_drop_facts(GrB_Vector v) {
+  v->holes_zero = false; v->holes_big = false; v->lor_state = 0; v->abs_bound = -1; v->small_valid = false; v->code_valid = false; v->dnvals_known = false; v->fe_lb = 0; v->fe_lb_key = 0;
+}
+void mat_edit_flush(GrB_Matrix A) {
+  if (!mat_edits_queued(A)) return;
+  if (!A->dev_valid || !A->csr.valid) fail(GrB_PANIC, "edit: queued element edits without a device image");
+  const size_t ts = A->type->size; auto& P = A->pending;
+  const std::vector<uint32_t> ord = edit_normalise_ij(P);
+  const uint32_t k = (uint32_t)ord.size();
+  std::vector<uint32_t> ei(k), ej(k); std::vector<uint8_t> del(k), x((size_t)k * ts);
+  for (uint32_t e = 0; e < k; e++) { const auto& r = P[ord[e]]; ei[e] = (uint32_t)r.i; ej[e] = (uint32_t)r.j; del[e] = r.del ? 1 : 0; memcpy(&x[(size_t)e * ts], r.x, ts); }
+  DevCSR out; bool structural = false;
+  const EditCounts n = csr_apply_edits(A->csr, ts, k, ei.data(), ej.data(), del.data(), x.data(), out, &structural);      // (neither csr_apply_edits nor anything it calls comes back here)
+  P.clear(); P.shrink_to_fit();                              // only now: a flush that failed (allocation, launch, the entry-count limit) leaves the queue as it was, and the caller its error
+  if (structural) { A->csr = std::move(out); mat_drop_derived(A); }
+  else if (n.set) {                                          // values only: what an overwrite in place drops (mat_set)
+    A->csc.clear(); A->csr.xcd.reset(); A->csr.range_state = 0; A->bm.clear(); A->csr.heads_valid = false;
+  }
+  g_last_plan = "edit<on=matrix,set=" + std::to_string(n.set) + ",ins=" + std::to_string(n.ins) + ",del=" + std::to_string(n.del) + "> k_edit_locate " +
+                (structural ? "k_edit_rowptr k_edit_stream k_edit_place " : n.set ? "k_edit_values " : "") + g_last_plan;
+}
+void vec_edit_flush(GrB_Vector v) {
+  if (!vec_edits_queued(v)) return;
+  if (!v->dev_valid) fail(GrB_PANIC, "edit: queued element edits without a device image");
+  const size_t ts = v->type->size; auto& P = v->pending;
+  const std::vector<uint32_t> ord = edit_normalise_i(P);
+  const uint32_t k = (uint32_t)ord.size(); uint32_t nset = 0;
+  std::vector<uint32_t> idx(k); std::vector<uint8_t> del(k), x((size_t)k * ts);
+  for (uint32_t e = 0; e < k; e++) { const auto& r = P[ord[e]]; idx[e] = (uint32_t)r.i; del[e] = r.del ? 1 : 0; nset += r.del ? 0 : 1; memcpy(&x[(size_t)e * ts], r.x, ts); }
+  vec_drop_facts(v);
+  vec_apply_edits(ts, v->n, k, idx.data(), del.data(), x.data(), v->dval.p, v->dpres.as<uint8_t>());
+  P.clear(); P.shrink_to_fit();                              // only now: a flush that failed leaves the queue as it was (the scatter stores the same bytes when it runs again)
+  // (a bitmap store does not tell an overwrite from an insert: `set` counts both, `ins` is not known)
+  g_last_plan = "edit<on=vector,set=" + std::to_string(nset) + ",ins=-,del=" + std::to_string(k - nset) + "> k_edit_vector " + g_last_plan;      
+}
+
 void mat_to_host(GrB_Matrix A) {
   if (A->iso_full) fail(GrB_INSUFFICIENT_SPACE, ISO_MSG);
   if (A->host_valid) { mat_host_assemble(A); return; }
   if (mat_bitmap_only(A)) mat_to_device(A);                  // a batch matrix that lives as a bitmap: its CSR first
+  mat_edit_flush(A);                                         // queued element edits reach the device image first
   // download the device CSR and expand to sorted tuples
   const DevCSR& c = A->csr; const size_t ts = A->type->size;
   std::vector<uint32_t> rp(c.nrows + 1), col(c.nnz);
@@ -89,7 +151,7 @@ void mat_to_host(GrB_Matrix A) {
 }
 
 void mat_to_device(GrB_Matrix A) {
-  if (A->dev_valid) return;
+  if (A->dev_valid) { mat_edit_flush(A); return; }
   if (mat_bitmap_only(A)) { mat_bitmap_to_csr(A); return; }
   if (A->type->code >= T_FC32) fail(GrB_DOMAIN_MISMATCH, "complex matrices are host-side containers here: no device arithmetic on them");
   need_device();
@@ -117,6 +179,7 @@ uint64_t mat_nvals(GrB_Matrix A) {
   if (A->iso_full) { const unsigned __int128 t = (unsigned __int128)A->nrows * A->ncols; return t > UINT64_MAX ? UINT64_MAX : (uint64_t)t; }
   if (A->host_valid) { mat_host_assemble(A); return A->hi.size(); }
   if (mat_bitmap_only(A)) return mat_bitmap_nvals(A);
+  mat_edit_flush(A);
   return A->csr.nnz;
 }
 
@@ -354,6 +417,7 @@ GrB_Info GrB_Matrix_dup(GrB_Matrix* C, const GrB_Matrix A) {
   if (!C) return GrB_NULL_POINTER; CHECK_MAT(A);
   GrB_Matrix m = nullptr; GrB_Info info = GrB_Matrix_new(&m, A->type, A->nrows, A->ncols); if (info) return info;
   info = guarded(A, [&] {
+    if (mat_edits_queued(A)) g_last_plan.clear();
     m->format = A->format; m->sparsity_control = A->sparsity_control; m->hyper_switch = A->hyper_switch;
     if (A->iso_full) { m->iso_full = true; memcpy(m->iso_val, A->iso_val, 16); }
     else if (A->host_valid) { mat_host_assemble(A); m->hi = A->hi; m->hj = A->hj; m->hx = A->hx; m->host_valid = true; }
@@ -364,6 +428,7 @@ GrB_Info GrB_Matrix_dup(GrB_Matrix* C, const GrB_Matrix A) {
       GRB_HIP(hipMemcpyAsync(m->bm.pres.p, A->bm.pres.p, np, hipMemcpyDeviceToDevice, stream()));
       m->bm.valid = true; m->bm.nvals = A->bm.nvals; m->bm.nvals_known = A->bm.nvals_known; m->host_valid = false; m->dev_valid = false;
     } else {
+      mat_edit_flush(A);
       const DevCSR& s = A->csr; DevCSR& d = m->csr; const size_t ts = A->type->size;
       d.nrows = s.nrows; d.ncols = s.ncols; d.nnz = s.nnz;
       d.rowptr.alloc(((size_t)s.nrows + 1) * 4); d.col.alloc(s.nnz * 4); d.val.alloc(s.nnz * ts);
@@ -382,11 +447,11 @@ GrB_Info GrB_Matrix_clear(GrB_Matrix A) {
 GrB_Info GrB_Matrix_nrows(GrB_Index* n, const GrB_Matrix A) { if (!n) return GrB_NULL_POINTER; CHECK_MAT(A); *n = A->nrows; return GrB_SUCCESS; }
 GrB_Info GrB_Matrix_ncols(GrB_Index* n, const GrB_Matrix A) { if (!n) return GrB_NULL_POINTER; CHECK_MAT(A); *n = A->ncols; return GrB_SUCCESS; }
 GrB_Info GrB_Matrix_nvals(GrB_Index* n, const GrB_Matrix A) {
-  if (!n) return GrB_NULL_POINTER; CHECK_MAT(A); return guarded(A, [&] { *n = mat_nvals(A); });
+  if (!n) return GrB_NULL_POINTER; CHECK_MAT(A); return guarded(A, [&] { if (mat_edits_queued(A)) g_last_plan.clear(); *n = mat_nvals(A); });
 }
 GrB_Info GrB_Matrix_wait(GrB_Matrix* A) {
   if (!A) return GrB_NULL_POINTER; CHECK_MAT(*A);
-  return guarded(*A, [&] { if ((*A)->host_valid && !(*A)->iso_full) mat_host_assemble(*A); if (device_ok()) GRB_HIP(hipStreamSynchronize(stream())); });
+  return guarded(*A, [&] { if ((*A)->host_valid && !(*A)->iso_full) mat_host_assemble(*A); if (mat_edits_queued(*A)) g_last_plan.clear(); mat_edit_flush(*A); if (device_ok()) GRB_HIP(hipStreamSynchronize(stream())); });
 }
 // the reference asks `self` for the message even when the failing object was the output (pygraphblas/matrix.py:43-51)
 GrB_Info GrB_Matrix_error(const char** s, const GrB_Matrix A) { if (!s) return GrB_NULL_POINTER; CHECK_MAT(A); *s = A->err.empty() ? g_last_error.c_str() : A->err.c_str(); return GrB_SUCCESS; }
@@ -394,6 +459,28 @@ GrB_Info GxB_Matrix_type(GrB_Type* t, const GrB_Matrix A) { if (!t) return GrB_N
 GrB_Info GrB_Matrix_resize(GrB_Matrix A, GrB_Index nr, GrB_Index nc) {
   CHECK_MAT(A); if (nr > GXB_INDEX_MAX || nc > GXB_INDEX_MAX) return GrB_INVALID_VALUE;
   return guarded(A, [&] {
+    if (mat_edit_route(A) && nr <= GRB_DIM_DEVICE_MAX && nc <= GRB_DIM_DEVICE_MAX) {      // it lives in HBM and stays there (a dimension beyond the device range: the host route below)
+      mat_edit_flush(A);
+      const size_t ts = A->type->size; const uint32_t nr32 = (uint32_t)nr, nc32 = (uint32_t)nc;
+      const bool changed = nr32 != A->csr.nrows || nc32 != A->csr.ncols;
+      if (nr32 != A->csr.nrows) {                            // fewer rows: the row pointer truncated; more: extended with its last word.  The entries stay where they are.
+        DevCSR t; t.nrows = nr32; t.ncols = A->csr.ncols;
+        t.nnz = csr_resize_rowptr(A->csr, nr32, t.rowptr);
+        t.col = std::move(A->csr.col); t.val = std::move(A->csr.val); t.valid = true;
+        A->csr = std::move(t);
+      }
+      if (nc32 < A->csr.ncols && A->csr.nnz) {               // fewer columns: keep bytes, then the compaction every select uses
+        DevBuf keep(A->csr.nnz + 16); DevCSR t;
+        csr_keep_cols_below(A->csr, nc32, keep.as<uint8_t>());
+        csr_compact(A->csr, A->csr.val.p, ts, keep.as<uint8_t>(), t);
+        A->csr = std::move(t);
+      }
+      A->csr.ncols = nc32;
+      if (changed) mat_drop_derived(A);
+      A->nrows = nr; A->ncols = nc;
+      g_last_plan = "resize<on=matrix,rows=" + std::to_string(nr) + ",cols=" + std::to_string(nc) + "> ";
+      return;
+    }
     mat_to_host(A); const size_t ts = A->type->size; size_t w = 0;
     for (size_t k = 0; k < A->hi.size(); k++) if (A->hi[k] < nr && A->hj[k] < nc) {
       if (w != k) { A->hi[w] = A->hi[k]; A->hj[w] = A->hj[k]; memmove(&A->hx[w * ts], &A->hx[k * ts], ts); } w++; }
@@ -402,7 +489,10 @@ GrB_Info GrB_Matrix_resize(GrB_Matrix A, GrB_Index nr, GrB_Index nc) {
 }
 GrB_Info GrB_Matrix_removeElement(GrB_Matrix A, GrB_Index i, GrB_Index j) {
   CHECK_MAT(A); if (i >= A->nrows || j >= A->ncols) return GrB_INVALID_INDEX;
-  return guarded(A, [&] { mat_to_host(A); GrB_Matrix_opaque::Pending p{i, j, true, {0}}; A->pending.push_back(p); mat_invalidate_device(A); });
+  return guarded(A, [&] {
+    GrB_Matrix_opaque::Pending p{i, j, true, {0}};
+    if (mat_edit_route(A)) { A->pending.push_back(p); A->bm.clear(); return; }      // it lives in HBM: queued for the device (the bitmap cache beside the CSR has its own readers: dropped now)
+    mat_to_host(A); A->pending.push_back(p); mat_invalidate_device(A); });
 }
 GrB_Info GxB_Matrix_Option_set(GrB_Matrix A, int field, ...) {
   CHECK_MAT(A); va_list ap; va_start(ap, field); GrB_Info info = GrB_SUCCESS;
@@ -421,7 +511,7 @@ GrB_Info GxB_Matrix_Option_get(GrB_Matrix A, int field, ...) {
     case 1: { int* p = va_arg(ap, int*); if (p) *p = A->format; break; }
     case 0: { double* p = va_arg(ap, double*); if (p) *p = A->hyper_switch; break; }
     case 32: { int* p = va_arg(ap, int*); if (p) *p = A->sparsity_control; break; }
-    case 33: { int* p = va_arg(ap, int*); if (p) *p = A->iso_full ? 8 : (A->nrows > GRB_DIM_DEVICE_MAX || A->hyper_switch >= 1.0 || mat_nvals(A) == 0) ? 1 : 2; break; }  // what SuiteSparse would report: hypersparse for huge or empty matrices and under hyper_switch = GxB_ALWAYS_HYPER (a stored option here), else sparse
+    case 33: { int* p = va_arg(ap, int*); uint64_t nv = 1; if (!A->iso_full) info = guarded(A, [&] { nv = mat_nvals(A); }); if (p) *p = A->iso_full ? 8 : (A->nrows > GRB_DIM_DEVICE_MAX || A->hyper_switch >= 1.0 || nv == 0) ? 1 : 2; break; }  // what SuiteSparse would report: hypersparse for huge or empty matrices and under hyper_switch = GxB_ALWAYS_HYPER (a stored option here), else sparse
     case 34: { double* p = va_arg(ap, double*); if (p) *p = 0.04; break; }
     default: info = GrB_INVALID_VALUE;
   }
@@ -462,8 +552,9 @@ static GrB_Info mat_set(GrB_Matrix C, const void* x, int xcode, GrB_Index i, GrB
       }
     }
     if (C->iso_full) fail(GrB_INSUFFICIENT_SPACE, ISO_MSG);
-    if (!C->host_valid) mat_to_host(C);
     GrB_Matrix_opaque::Pending p{i, j, false, {0}}; cast_scalar(C->type->code, p.x, xcode, x);
+    if (mat_edit_route(C)) { C->pending.push_back(p); C->bm.clear(); return; }      // it lives in HBM (a new position, or edits are queued already: order is kept): queued for the device
+    if (!C->host_valid) mat_to_host(C);
     C->pending.push_back(p); mat_invalidate_device(C);
   });
 }
@@ -477,6 +568,11 @@ static GrB_Info mat_get(void* x, int xcode, GrB_Matrix A, GrB_Index i, GrB_Index
   GrB_Info r = GrB_SUCCESS;
   GrB_Info info = guarded(A, [&] {
     if (A->iso_full) { cast_scalar(xcode, x, A->type->code, A->iso_val); return; }
+    if (mat_edits_queued(A)) {                                 // the last queued edit of the coordinate answers; else the device image does, edits applied
+      if (const auto* e = edit_lookup(A->pending, [&](const GrB_Matrix_opaque::Pending& q) { return q.i == i && q.j == j; })) {
+        if (e->del) r = GrB_NO_VALUE; else cast_scalar(xcode, x, A->type->code, e->x); return; }
+      g_last_plan.clear(); mat_edit_flush(A);
+    }
     if (mat_device_only(A)) {
       const uint64_t pos = csr_find_entry(A->csr, (uint32_t)i, (uint32_t)j);
       if (pos == ~0ull) { r = GrB_NO_VALUE; return; }
@@ -491,6 +587,7 @@ static GrB_Info mat_get(void* x, int xcode, GrB_Matrix A, GrB_Index i, GrB_Index
 static GrB_Info mat_tuples(GrB_Index* I, GrB_Index* J, void* X, int xcode, GrB_Index* n, GrB_Matrix A) {
   if (!n) return GrB_NULL_POINTER; CHECK_MAT(A);
   return guarded(A, [&] {
+    if (mat_edits_queued(A)) g_last_plan.clear();
     mat_to_host(A); const GrB_Index nv = A->hi.size();
     if ((I || J || X) && *n < nv) fail(GrB_INSUFFICIENT_SPACE, "extractTuples: output arrays too small");
     const size_t ts = A->type->size, xs = type_size(xcode);
@@ -522,6 +619,7 @@ GrB_Info GrB_Vector_dup(GrB_Vector* w, const GrB_Vector u) {
   if (!w) return GrB_NULL_POINTER; CHECK_VEC(u);
   GrB_Vector r = nullptr; GrB_Info info = GrB_Vector_new(&r, u->type, u->n); if (info) return info;
   info = guarded(u, [&] {
+    if (vec_edits_queued(u)) g_last_plan.clear();
     vec_gate(u);
     if (u->iso_full) { r->iso_full = true; memcpy(r->iso_val, u->iso_val, 16); }
     else if (u->host_valid) { vec_host_assemble(u); r->hi = u->hi; r->hx = u->hx; }
@@ -537,22 +635,40 @@ GrB_Info GrB_Vector_dup(GrB_Vector* w, const GrB_Vector u) {
 }
 GrB_Info GrB_Vector_clear(GrB_Vector v) { CHECK_VEC(v); if (v->lazy | v->q_reads) { GrB_Info e = guarded(v, [&] { vec_overwritten(v); }); if (e) return e; } v->hi.clear(); v->hx.clear(); v->pending.clear(); v->host_valid = true; v->iso_full = false; vec_invalidate_device(v); return GrB_SUCCESS; }
 GrB_Info GrB_Vector_size(GrB_Index* n, const GrB_Vector v) { if (!n) return GrB_NULL_POINTER; CHECK_VEC(v); *n = v->n; return GrB_SUCCESS; }
-GrB_Info GrB_Vector_nvals(GrB_Index* n, const GrB_Vector v) { if (!n) return GrB_NULL_POINTER; CHECK_VEC(v); return guarded(v, [&] { *n = vec_nvals(v); }); }
+GrB_Info GrB_Vector_nvals(GrB_Index* n, const GrB_Vector v) { if (!n) return GrB_NULL_POINTER; CHECK_VEC(v); return guarded(v, [&] { if (vec_edits_queued(v)) g_last_plan.clear(); *n = vec_nvals(v); }); }
 GrB_Info GrB_Vector_wait(GrB_Vector* v) {
   if (!v) return GrB_NULL_POINTER; CHECK_VEC(*v);
-  return guarded(*v, [&] { vec_gate(*v); if ((*v)->host_valid) vec_host_assemble(*v); if (device_ok()) GRB_HIP(hipStreamSynchronize(stream())); });
+  return guarded(*v, [&] { if (vec_edits_queued(*v)) g_last_plan.clear(); vec_gate(*v); if ((*v)->host_valid) vec_host_assemble(*v); if (device_ok()) GRB_HIP(hipStreamSynchronize(stream())); });
 }
 GrB_Info GrB_Vector_error(const char** s, const GrB_Vector v) { if (!s) return GrB_NULL_POINTER; CHECK_VEC(v); *s = v->err.empty() ? g_last_error.c_str() : v->err.c_str(); return GrB_SUCCESS; }
 GrB_Info GxB_Vector_type(GrB_Type* t, const GrB_Vector v) { if (!t) return GrB_NULL_POINTER; CHECK_VEC(v); *t = v->type; return GrB_SUCCESS; }
 GrB_Info GrB_Vector_resize(GrB_Vector v, GrB_Index n) {
   CHECK_VEC(v); if (n > GXB_INDEX_MAX) return GrB_INVALID_VALUE;
-  return guarded(v, [&] { vec_to_host(v); const size_t ts = v->type->size; size_t w = 0;
+  return guarded(v, [&] {
+    if (!v->host_valid) vec_gate(v);
+    if (vec_edit_route(v) && n <= GRB_DIM_DEVICE_MAX) {       // it lives in HBM and stays there: a new bitmap, the common prefix copied, the tail zero
+      const size_t ts = v->type->size; const uint64_t keep = std::min<uint64_t>(n, v->n);
+      if (n != v->n) {
+        DevBuf nval(n * ts ? n * ts : 1), npres(n ? n : 1);
+        if (keep) dev_copy2(nval.p, v->dval.p, keep * ts, npres.p, v->dpres.p, keep);
+        if (n > keep) { GRB_HIP(hipMemsetAsync((uint8_t*)nval.p + keep * ts, 0, (n - keep) * ts, stream())); GRB_HIP(hipMemsetAsync(npres.as<uint8_t>() + keep, 0, n - keep, stream())); }
+        const bool known = v->dnvals_known && n >= v->n; const uint64_t cnt = v->dnvals;      // (a longer vector holds what it held)
+        vec_drop_facts(v);
+        v->dval = std::move(nval); v->dpres = std::move(npres); v->dcode.reset(); v->n = n; v->dnvals = cnt; v->dnvals_known = known;
+      }
+      g_last_plan = "resize<on=vector,rows=" + std::to_string(n) + ",cols=1> ";
+      return;
+    }
+    vec_to_host(v); const size_t ts = v->type->size; size_t w = 0;
     while (w < v->hi.size() && v->hi[w] < n) w++;
     v->hi.resize(w); v->hx.resize(w * ts); v->n = n; vec_invalidate_device(v); });
 }
 GrB_Info GrB_Vector_removeElement(GrB_Vector v, GrB_Index i) {
   CHECK_VEC(v); if (i >= v->n) return GrB_INVALID_INDEX;
-  return guarded(v, [&] { vec_to_host(v); GrB_Vector_opaque::Pending p{i, true, {0}}; v->pending.push_back(p); vec_invalidate_device(v); });
+  return guarded(v, [&] {
+    GrB_Vector_opaque::Pending p{i, true, {0}};
+    if (!v->host_valid && !v->iso_full) { if (v->lazy | v->q_reads) vec_resolve(v); if (vec_edit_route(v)) { v->pending.push_back(p); vec_drop_facts(v); return; } }      // it lives in HBM (a deferred chain completed first): queued for the device
+    vec_to_host(v); v->pending.push_back(p); vec_invalidate_device(v); });
 }
 GrB_Info GxB_Vector_Option_set(GrB_Vector v, int field, ...) {
   CHECK_VEC(v); va_list ap; va_start(ap, field); GrB_Info info = GrB_SUCCESS;
@@ -584,14 +700,21 @@ static GrB_Info vec_build(GrB_Vector w, const GrB_Index* I, const void* X, int x
 }
 static GrB_Info vec_set(GrB_Vector w, const void* x, int xcode, GrB_Index i) {
   CHECK_VEC(w); if (i >= w->n) return GrB_INVALID_INDEX;
-  return guarded(w, [&] { if (w->iso_full) fail(GrB_INSUFFICIENT_SPACE, ISO_MSG); if (!w->host_valid) vec_to_host(w);
-    GrB_Vector_opaque::Pending p{i, false, {0}}; cast_scalar(w->type->code, p.x, xcode, x); w->pending.push_back(p); vec_invalidate_device(w); });
+  return guarded(w, [&] { if (w->iso_full) fail(GrB_INSUFFICIENT_SPACE, ISO_MSG);
+    GrB_Vector_opaque::Pending p{i, false, {0}}; cast_scalar(w->type->code, p.x, xcode, x);
+    if (!w->host_valid) { if (w->lazy | w->q_reads) vec_resolve(w); if (vec_edit_route(w)) { w->pending.push_back(p); vec_drop_facts(w); return; } vec_to_host(w); }      // it lives in HBM (a deferred chain completed first): queued for the device
+    w->pending.push_back(p); vec_invalidate_device(w); });
 }
 static GrB_Info vec_get(void* x, int xcode, GrB_Vector v, GrB_Index i) {
   if (!x) return GrB_NULL_POINTER; CHECK_VEC(v); if (i >= v->n) return GrB_INVALID_INDEX;
   GrB_Info r = GrB_SUCCESS;
   GrB_Info info = guarded(v, [&] {
     if (v->iso_full) { cast_scalar(xcode, x, v->type->code, v->iso_val); return; }
+    if (vec_edits_queued(v)) {                                 // the last queued edit of the position answers; else the device image does, edits applied (vec_gate)
+      if (const auto* e = edit_lookup(v->pending, [&](const GrB_Vector_opaque::Pending& q) { return q.i == i; })) {
+        if (e->del) r = GrB_NO_VALUE; else cast_scalar(xcode, x, v->type->code, e->x); return; }
+      g_last_plan.clear();
+    }
     vec_gate(v);
     // a large vector that lives in HBM only (`r[vertex]` after a PageRank): the presence byte and the value come over alone — a few
     // dozen reads in a row, then the host mirror takes over (one transfer, no more round trips)
@@ -612,6 +735,7 @@ static GrB_Info vec_get(void* x, int xcode, GrB_Vector v, GrB_Index i) {
 static GrB_Info vec_tuples(GrB_Index* I, void* X, int xcode, GrB_Index* n, GrB_Vector v) {
   if (!n) return GrB_NULL_POINTER; CHECK_VEC(v);
   return guarded(v, [&] {
+    if (vec_edits_queued(v)) g_last_plan.clear();
     vec_to_host(v); const GrB_Index nv = v->hi.size();
     if ((I || X) && *n < nv) fail(GrB_INSUFFICIENT_SPACE, "extractTuples: output arrays too small");
     const size_t ts = v->type->size, xs = type_size(xcode);

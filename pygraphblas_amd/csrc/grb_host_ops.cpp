@@ -511,7 +511,9 @@ bool assign_line_device(GrB_Matrix C, GrB_Vector mask, GrB_BinaryOp accum, GrB_V
 constexpr uint64_t KRON_DEVICE_MIN_ENTRIES = 1000;              // provisional: reasoned from the assign route's fixed cost, not yet measured
 thread_local float g_kron_fill_ms = 0.0f;
 bool hbm_only(GrB_Matrix A) { return A->dev_valid && !A->host_valid; }
-uint64_t entries_of(GrB_Matrix A) { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }      // (the count of a valid host mirror, or of the device CSR: no device work)
+// (the count of a valid host mirror, or of the device CSR: no device work.  With element edits queued on an HBM-only matrix — grb_container.cpp — the CSR header is read
+//  WITHOUT a flush here and in the threshold lambda of GrB_Matrix_assign below: the count is off by at most the queue's length, and it only picks a route.)
+uint64_t entries_of(GrB_Matrix A) { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }
 bool kron_on_device(GrB_Matrix C, GrB_Matrix Mask, GrB_Matrix A, GrB_Matrix B, const DescView& dv) {
   const int env = route_env("GRB_MI355X_KRON");
   if (env == 0 || !device_ok() || !mat_capable(C) || !mat_capable(A) || !mat_capable(B) || !mat_capable(Mask)) return false;

@@ -236,7 +236,13 @@ void hyper_mat_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryO
 void host_assign_scalar(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, GrB_Descriptor desc);
 void host_assign_scalar(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, GrB_Descriptor desc);
 void vec_resolve(GrB_Vector v);           // complete deferred work that involves v (grb_lazy.cpp)
-inline void vec_gate(GrB_Vector v) { if (v->lazy | v->q_reads) vec_resolve(v); }
+// the edit queue of a container that lives in HBM only (grb_container.cpp): `pending` with host_valid == false holds setElement / removeElement records that the
+// device image has not seen yet; they are applied there (grb_edit.hip) before anything reads or replaces that image
+inline bool mat_edits_queued(const GrB_Matrix_opaque* A) { return !A->pending.empty() && !A->host_valid; }
+inline bool vec_edits_queued(const GrB_Vector_opaque* v) { return !v->pending.empty() && !v->host_valid; }
+void mat_edit_flush(GrB_Matrix A);
+void vec_edit_flush(GrB_Vector v);
+inline void vec_gate(GrB_Vector v) { if (v->lazy | v->q_reads) vec_resolve(v); if (vec_edits_queued(v)) vec_edit_flush(v); }
 void vec_overwritten(GrB_Vector v);       // v's value is about to be replaced as a whole: deferred work that only produced it is dropped
 uint32_t* any_true_acquire(uint32_t* tag);        // a device word a BOOL product kernel sets to the (fresh, non-zero) tag when it writes a true value (see lor_state)
 void any_true_written(GrB_Vector w_or_null, const void* key, uint32_t tag, uint64_t fe_key = 0, uint32_t fe_nblocks = 0);    // a kernel honoured it; w's device buffers `key` are the result it describes (nullptr: nobody's); fe_key != 0: the kernel also filled the edge summary (counted in the row pointers with that serial)

@@ -227,7 +227,7 @@ static bool enqueue(Node nd, GrB_Vector w, int tcode) {
   for (int k = 0; k < nin; k++) {
     GrB_Vector x = nd.in[k];
     if (x->lazy == 2) { nd.prev[k] = true; nd.in[k] = nullptr; }
-    else { nd.prev[k] = false; if (!x->dev_valid || x->lazy == 1) vec_to_device(x); }      // (a pending fill of x is written here; an operand the queue already reads is resident)
+    else { nd.prev[k] = false; if (!x->dev_valid || x->lazy == 1 || vec_edits_queued(x)) vec_to_device(x); }      // (a pending fill of x is written here, queued element edits are applied; an operand the queue already reads is resident)
   }
   for (int k = 0; k < nin; k++) if (nd.in[k]) nd.in[k]->q_reads++;
   // the output: what it held is replaced as a whole — unless it is also a stored operand of the queue, its buffers are not needed

@@ -382,6 +382,11 @@ class Matrix:
     def wait(self):
         check(lib.GrB_Matrix_wait(C.byref(self._h)), self)
 
+    def resize(self, nrows=_capi.constants["GxB_INDEX_MAX"], ncols=_capi.constants["GxB_INDEX_MAX"]):
+        """Resize the matrix; entries that fall outside the new dimensions are deleted (reference: matrix.py:978-1001).  A matrix that lives in HBM
+        is resized there (grb_edit.hip) unless a new dimension is beyond the device range."""
+        check(lib.GrB_Matrix_resize(self._h, u64(nrows), u64(ncols)), self)
+
     # ---- element access ---------------------------------------------------------------------------------
     def to_arrays(self):
         n = self.nvals

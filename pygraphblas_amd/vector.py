@@ -112,6 +112,11 @@ class Vector:
     def wait(self):
         check(lib.GrB_Vector_wait(C.byref(self._h)), self)
 
+    def resize(self, size=_capi.constants["GxB_INDEX_MAX"]):
+        """Resize the vector; entries that fall outside the new size are deleted (reference: vector.py:1064-1076).  A vector that lives in HBM is
+        resized there unless the new size is beyond the device range."""
+        check(lib.GrB_Vector_resize(self._h, u64(size)), self)
+
     # ---- element access -----------------------------------------------------------------------------------
     def to_arrays(self):
         n = self.nvals
