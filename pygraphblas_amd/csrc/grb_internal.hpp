@@ -44,8 +44,10 @@ struct GrB_Type_opaque { uint64_t magic; int code; size_t size; char name[32]; }
 // `defn`: a user-defined operator (GxB_UnaryOp_new / GxB_BinaryOp_new, grb_userop.cpp; opcode >= U_USER / B_USER) owns a copy of its C definition; nullptr for built-ins
 struct GrB_UnaryOp_opaque { uint64_t magic; int opcode; GrB_Type_opaque* xtype; GrB_Type_opaque* ztype; char name[40]; void* fn; char* defn; };
 struct GrB_BinaryOp_opaque { uint64_t magic; int opcode; GrB_Type_opaque* xtype; GrB_Type_opaque* ytype; GrB_Type_opaque* ztype; char name[40]; void* fn; char* defn; };
-struct GrB_Monoid_opaque { uint64_t magic; GrB_BinaryOp_opaque* op; uint8_t identity[16]; bool has_terminal; uint8_t terminal[16]; char name[48]; bool builtin; };
-struct GrB_Semiring_opaque { uint64_t magic; GrB_Monoid_opaque* add; GrB_BinaryOp_opaque* mul; char name[56]; bool builtin; };
+// `usersr`: made by GrBX_Monoid_new_user / GrBX_Semiring_new_user (grb_usersr.cpp) — such an object always runs through the compiled kernels of user-defined semirings,
+// also when all of its operators are built-in, so that its rules (the identity is never combined into a result) do not depend on what it is made of
+struct GrB_Monoid_opaque { uint64_t magic; GrB_BinaryOp_opaque* op; uint8_t identity[16]; bool has_terminal; uint8_t terminal[16]; char name[48]; bool builtin; bool usersr; };
+struct GrB_Semiring_opaque { uint64_t magic; GrB_Monoid_opaque* add; GrB_BinaryOp_opaque* mul; char name[56]; bool builtin; bool usersr; };
 struct GrB_Descriptor_opaque { uint64_t magic; int outp, mask, inp0, inp1, axb, nthreads, sort; double chunk; bool builtin; char name[16]; };
 // a user-defined select operator (GxB_SelectOp_new, grb_userop.cpp; opcode >= SEL_USER) has its value and thunk types and owns a copy of its C definition; built-ins: nullptr
 struct GxB_SelectOp_opaque { uint64_t magic; int opcode; char name[40]; void* fn; GrB_Type_opaque* xtype; GrB_Type_opaque* ttype; char* defn; };

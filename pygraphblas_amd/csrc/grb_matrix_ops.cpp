@@ -104,8 +104,50 @@ namespace {
 void check_mat(GrB_Matrix A, const char* what) { if (!check_obj(A)) fail(GrB_UNINITIALIZED_OBJECT, std::string(what) + ": uninitialised matrix"); }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// A user-defined semiring (GrBX_Semiring_new_user, grb_usersr.cpp) in two steps.  The pattern of T is the pattern of the ANY_PAIR product of the operands'
+// patterns: the built-in routes with a BOOL ANY_PAIR semiring and no values — spgemm_masked under a plain mask (its rows are the mask's, in column order),
+// spgemm_hash otherwise (a segmented sort, or the dense path's ordered walk, leaves every row in column order).  The compiled kernel then fills the values,
+// every entry the left-to-right sum of its products in ascending k.  Refused naming the operator on containers without an HBM layout; the accumulator is looked at
+// before the dimensions; never queued; none of the batch / few-rows routes.  The write-back is the built-in semirings' own.
+void user_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
+  check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm");
+  const GrB_BinaryOp add = semiring->add->op, mul = semiring->mul;
+  user_needs_layout(usersr_name(add, mul), "dimension", is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B),
+                    C->type->code >= T_FC32 || A->type->code >= T_FC32 || B->type->code >= T_FC32 || (M && M->type->code >= T_FC32));
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc);
+  const Dims a = op_dims(A, dv.tran0), b = op_dims(B, dv.tran1);
+  if (a.c != b.r) fail(GrB_DIMENSION_MISMATCH, "mxm: dimensions do not conform");
+  conform(C, M, {a.r, b.c}, "mxm: dimensions do not conform");
+  lazy_flush();
+  g_last_plan.clear();
+  if (nothing_to_write(C, M, dv)) return;
+  const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);
+  SemiringDesc pd{}; pd.zcode = T_BOOL; pd.addop = B_ANY; pd.mulop = B_PAIR;      // (identity false, no terminal value, no flip)
+  SpgemmCall call{}; call.A = &Ad; call.B = &Bd;
+  DevCSR T; bool t_masked = false;
+  if (M && !dv.mask_comp) {
+    mat_to_device(M);
+    call.M = &M->csr; call.mcode = M->type->code; call.mstruct = dv.mask_struct;
+    spgemm_masked(call, pd, T); t_masked = true;
+  } else spgemm_hash(call, pd, T);
+  const int zc = add->ztype->code;
+  const std::string pattern_plan = g_last_plan;
+  g_last_plan = usersr_plan(USK_MXM, add, mul);
+  T.val.alloc(T.nnz * type_size(zc) + 16);
+  DevBuf acast, bcast;
+  const void* av = cast_values(zc, A->type->code, Ad.val.p, Ad.nnz, acast);
+  const void* bv = cast_values(zc, B->type->code, Bd.val.p, Bd.nnz, bcast);
+  usersr_product_values(add, mul, Ad, av, Bd, bv, T);
+  g_last_plan += "pattern: " + pattern_plan;
+  matrix_write_back(C, T, zc, M, dv, accum, t_masked);
+}
+
 void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
+  const bool user = check_obj(semiring) && check_obj(semiring->add) && is_user_semiring(semiring);
+  if (user) usersr_check(semiring->add->op, semiring->mul);      // (operators the compiled route cannot run are refused before a device is asked for)
   need_device();
+  if (user) { user_mxm(C, M, accum, semiring, A, B, desc); return; }
   if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mxm(C, M, accum, semiring, A, B, desc); return; }   // dimensions beyond the device layouts
   check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm");
   const DescView dv(desc);
@@ -280,9 +322,29 @@ void do_select(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GxB_SelectOp op, 
 }
 
 void do_reduce_vector(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Monoid monoid, GrB_Matrix A, GrB_Descriptor desc) {
+  if (check_obj(monoid) && check_obj(monoid->op) && is_user_monoid(monoid)) usersr_check(monoid->op, nullptr);      // (refused before a device is asked for)
   need_device(); check_mat(A, "reduce");
-  if (!check_obj(monoid)) fail(GrB_UNINITIALIZED_OBJECT, "reduce: monoid"); check_binop(monoid->op, "monoid");
+  if (!check_obj(monoid)) fail(GrB_UNINITIALIZED_OBJECT, "reduce: monoid");
   if (mask && !check_obj(mask)) fail(GrB_UNINITIALIZED_OBJECT, "reduce: mask");
+  if (check_obj(monoid->op) && is_user_monoid(monoid)) {
+    // a user-defined monoid (GrBX_Monoid_new_user): the row kernel of grb_usersr.cpp with the matrix value as the product; refused on containers without an HBM
+    // layout, the accumulator looked at before the dimensions, never queued
+    user_needs_layout(monoid->op->name, "dimension or size", is_hyper(A) || is_hyper(w) || is_hyper(mask), A->type->code >= T_FC32 || w->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
+    if (accum) check_binop(accum, "accum");
+    const DescView udv(desc);
+    const uint64_t ur = op_dims(A, udv.tran0).r;
+    DevBuf uallow_buf; const uint8_t* uallow;
+    if (vector_prelude(w, mask, udv, ur, {}, "reduce: dimensions do not conform", true, uallow_buf, uallow)) return;
+    vec_gate(w);
+    const int uc = monoid->op->ztype->code;
+    const DevCSR& S = operand(A, udv.tran0);
+    DevBuf ac, tval(ur * type_size(uc) + 16), tpres(ur + 16);
+    const void* av = cast_values(uc, A->type->code, S.val.p, S.nnz, ac);
+    usersr_rows(USK_REDUCE_ROWS, monoid->op, nullptr, S, av, nullptr, nullptr, nullptr, tval.p, tpres.as<uint8_t>());
+    vector_write_back(w, uc, tval, tpres, uallow, accum, udv.replace, false);
+    return;
+  }
+  check_binop(monoid->op, "monoid");
   const DescView dv(desc);
   const uint64_t r = op_dims(A, dv.tran0).r;
   DevBuf allow_buf; const uint8_t* allow;

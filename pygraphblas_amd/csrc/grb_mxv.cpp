@@ -21,11 +21,42 @@ static int g_force_method = SPMV_AUTO;   // test hook: GRB_MI355X_SPMV=adaptive|
 // ns x (n values + n bytes) copies per product of the first bitmap version (3.8 of 14 ms of the BC driver at R-MAT-22) are gone.  One-shot: cleared by the call.
 namespace grb { thread_local void* g_mxv_dest_val = nullptr; thread_local uint8_t* g_mxv_dest_pres = nullptr; }
 
+// A user-defined semiring (GrBX_Semiring_new_user, grb_usersr.cpp): containers without an HBM layout are refused naming its operator, the accumulator is looked at
+// before the dimensions, the call is never queued and completes deferred work first.  T — unmasked, or under the allow bytes — comes from the compiled row kernel
+// over the CSR of the orientation the built-in product pulls over; the argument order of the multiplier is the kernel's kind, not a flag.  The write-back is the
+// built-in semirings' own.
+static void user_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u, GrB_Descriptor desc, bool is_vxm) {
+  const GrB_BinaryOp add = semiring->add->op, mul = semiring->mul;
+  user_needs_layout(usersr_name(add, mul), "dimension or size", is_hyper(A) || is_hyper(w) || is_hyper(u) || is_hyper(mask),
+                    A->type->code >= T_FC32 || w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc);
+  const bool useT = is_vxm ? !dv.tran1 : dv.tran0;           // M = useT ? A^T : A
+  const uint64_t mr = useT ? A->ncols : A->nrows, mc = useT ? A->nrows : A->ncols;
+  if (u->n != mc || w->n != mr || (mask && mask->n != mr)) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: dimensions do not conform");
+  lazy_flush(); vec_gate(w);
+  g_last_plan.clear();
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, mr, allow_buf, &nothing);
+  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  mat_to_device(A); vec_to_device(u);
+  const DevCSR& R = useT ? mat_csc(A) : A->csr;
+  const int zc = add->ztype->code; const size_t zs = type_size(zc);
+  DevBuf tval(mr * zs + 16), tpres(mr + 16), ucast, acast;
+  const void* av = cast_values(zc, A->type->code, R.val.p, R.nnz, acast);
+  const void* uv = cast_values(zc, u->type->code, u->dval.p, u->n, ucast);
+  usersr_rows(is_vxm ? USK_VXM : USK_MXV, add, mul, R, av, uv, u->dpres.as<uint8_t>(), allow, tval.p, tpres.as<uint8_t>());
+  vector_write_back(w, zc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/true);
+}
+
 static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u,
                      GrB_Descriptor desc, bool is_vxm) {
+  const bool user = check_obj(semiring) && check_obj(semiring->add) && is_user_semiring(semiring);
+  if (user) usersr_check(semiring->add->op, semiring->mul);      // (operators the compiled route cannot run are refused before a device is asked for)
   need_device();
   if (!check_obj(w) || !check_obj(A) || !check_obj(u) || (mask && !check_obj(mask)))
     fail(GrB_UNINITIALIZED_OBJECT, "mxv/vxm: uninitialised operand");
+  if (user) { user_mxv_like(w, mask, accum, semiring, A, u, desc, is_vxm); return; }
   if (is_hyper(A) || is_hyper(w) || is_hyper(u) || is_hyper(mask)) { hyper_mxv_like(w, mask, accum, semiring, A, u, desc, is_vxm); return; }   // dimensions beyond the device layouts
   if (w->q_reads || w->lazy == 2) vec_gate(w);                // deferred element-wise work on the output completes first (a pending fill, lazy == 1, is dealt with below)
   const DescView dv(desc);

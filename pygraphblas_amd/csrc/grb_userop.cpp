@@ -27,6 +27,9 @@
 // GxB_Vector_select (do_select, vec_select: the built-in select operators' drivers, whose keep bytes it makes) run it through userselect_run: one text per (definition, name, xtype, ttype, matrix | vector) with the kernel grb_userselect, which writes
 // one keep byte per stored entry (matrix: per CSR position; vector: per bitmap position, i the position and j 0); the drivers compact / write back as for the
 // built-in select operators.
+//
+// The table of compiled texts, the prelude and the launch counter are shared with the kernels of user-defined monoids and semirings (grb_usersr.cpp:
+// userop_kernel_of, userop_prelude, userop_count_launch), the one way a user-defined operator reaches mxm / mxv / vxm and the matrix-to-vector reduction.
 #include "grb_api.hpp"
 #include "grb_device.hpp"
 #include "grb_jit.hpp"
@@ -193,9 +196,15 @@ void launch(hipFunction_t fn, uint64_t n, void** args) {
 
 }  // namespace
 
+hipFunction_t userop_kernel_of(const std::string& src, const char* name, const char* entry, const char* prefix) { return kernel_of(src, name, entry, prefix); }
+const char* userop_c_type(int code) { return c_type(code); }
+const char* userop_prelude() { return PRELUDE; }
+void userop_count_launch() { g_stat_launched++; }
+
 void userop_refuse(const char* opname, const char* where) {
   fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + opname + " cannot be used as " + where +
-                            ": user-defined operators run in apply, apply with a bound scalar, eWiseAdd and eWiseMult only");
+                            ": user-defined operators run in apply, apply with a bound scalar, eWiseAdd, eWiseMult and select, and as the operators of a "
+                            "GrBX_Monoid_new_user / GrBX_Semiring_new_user object in mxm, mxv, vxm and the matrix-to-vector reduction only");
 }
 
 void user_needs_layout(const char* opname, const char* extent, bool hyper, bool cplx) {

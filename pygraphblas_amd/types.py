@@ -131,6 +131,20 @@ class Type(metaclass=MetaType):
     default_one = 1
 
     @classmethod
+    def new_monoid(cls, op, identity):
+        """A monoid of this type over `op`, a `@binary_op` operator or one of the built-ins the compiled kernels express (FIRST, SECOND, PAIR, PLUS, MINUS,
+        TIMES, MIN, MAX; LOR / LAND / LXOR on BOOL) (reference: pygraphblas/types.py:113-120).  The identity is stored, never combined into a result."""
+        from .userop import UserMonoid
+        return UserMonoid(cls, op, identity)
+
+    @classmethod
+    def new_semiring(cls, monoid, op):
+        """A semiring of this type: `monoid` from `new_monoid` (or a built-in monoid of the operators above) and the multiplier `op` (reference:
+        pygraphblas/types.py:122-129).  Runs in mxm / mxv / vxm through kernels compiled for the device."""
+        from .userop import UserSemiring
+        return UserSemiring(cls, monoid, op)
+
+    @classmethod
     def _default_semiring(cls):
         return cls.PLUS_TIMES
 

@@ -42,7 +42,7 @@ import textwrap
 
 from . import types
 from ._capi import lib
-from .base import check, _error_codes, GraphBLASException
+from .base import check, _error_codes, GraphBLASException, DomainMismatch
 
 __all__ = ["unary_op", "binary_op", "select_op", "UserUnaryOp", "UserBinaryOp", "UserSelectOp", "translate", "translate_select"]
 
@@ -526,6 +526,62 @@ class UserSelectOp(_UserOp, types.SelectOp):
             _raise(info, "GxB_SelectOp_new")
         self._setup("SelectOp", func, typ, h, defn)
         self.thunk_type = thunk_type or typ
+
+
+class UserMonoid(types.Monoid):
+    """`T.new_monoid(op, identity)`: a monoid over a user-defined or (expressible) built-in binary operator (GrBX_Monoid_new_user).  Holds a reference to its
+    operator — the C object keeps a pointer to it — and frees its handle on collection."""
+
+    def __init__(self, typ, op, identity):
+        if not isinstance(op, types.BinaryOp):
+            raise TypeError(f"new_monoid takes a binary operator, not {type(op).__name__}")
+        if op.type._h != typ._h:      # (the identity is packed as this class's C type: the operator's type must be the class's)
+            raise DomainMismatch(f"{typ.__name__}.new_monoid: operator {op.name} is of type {op.type.__name__}")
+        h = C.c_void_p()
+        info = lib.GrBX_Monoid_new_user(C.byref(h), C.c_void_p(op.get_op()), C.byref(typ._c(identity)))
+        if info:
+            _raise(info, "GrBX_Monoid_new_user")
+        self.kind, self.cname, self.name, self.type = "Monoid", f"user_{op.name}", f"{op.name}_MONOID", typ
+        self._h, self._token = h.value, None
+        self.op, self.identity = op, identity
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and lib is not None:
+            self._h = None
+            lib.GrB_Monoid_free(C.byref(C.c_void_p(h)))
+
+    def __repr__(self):
+        return f"<UserMonoid {self.type.__name__}.{self.name}>"
+
+
+class UserSemiring(types.Semiring):
+    """`T.new_semiring(monoid, op)`: a semiring at least one of whose operators is user-defined (GrBX_Semiring_new_user); a `semiring=` argument, a context
+    manager (`with sr: A @ B`) and a callable (`sr(A, B)`) like the built-in ones.  Holds references to its monoid and multiplier."""
+
+    def __init__(self, typ, monoid, op):
+        if not isinstance(monoid, types.Monoid) or not isinstance(op, types.BinaryOp):
+            raise TypeError("new_semiring takes a monoid and a binary operator")
+        for what in (monoid, op):
+            if what.type._h != typ._h:
+                raise DomainMismatch(f"{typ.__name__}.new_semiring: {what.kind} {what.name} is of type {what.type.__name__}")
+        h = C.c_void_p()
+        info = lib.GrBX_Semiring_new_user(C.byref(h), C.c_void_p(monoid.get_op()), C.c_void_p(op.get_op()))
+        if info:
+            _raise(info, "GrBX_Semiring_new_user")
+        self.kind, self.cname, self.type = "Semiring", f"user_{monoid.name}_{op.name}", typ
+        self.name = f"{monoid.name[:-7] if monoid.name.endswith('_MONOID') else monoid.name}_{op.name}"
+        self._h, self._token = h.value, None
+        self.monoid, self.op = monoid, op
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and lib is not None:
+            self._h = None
+            lib.GrB_Semiring_free(C.byref(C.c_void_p(h)))
+
+    def __repr__(self):
+        return f"<UserSemiring {self.type.__name__}.{self.name}>"
 
 
 def unary_op(arg_type):

@@ -380,6 +380,16 @@ GrB_Info GxB_SelectOp_free(GxB_SelectOp *selectop);  /* releases a user-defined 
 GrB_Info GrBX_userop_stats(uint64_t *compiled, uint64_t *loaded_from_disk, uint64_t *launched); /* user-operator kernels compiled with hipRTC, loaded from the code-object cache on disk instead, and launches through them */
 GrB_Info GrBX_userop_source(const char *name, const char *defn, GrB_Type type, int kind, char *buf, size_t len); /* the kernel text compiled for such an operator in an operation of `kind` (0 apply, 1 bind1st, 2 bind2nd, 3 eadd, 4 emult) */
 GrB_Info GrBX_selectop_source(const char *name, const char *defn, GrB_Type xtype, GrB_Type ttype, int on_vector, char *buf, size_t len); /* the kernel text compiled for a select operator used on a matrix (on_vector 0) or a vector (1) */
+/* User-defined monoids and semirings.  GrB_Monoid_new_<T> / GrB_Semiring_new refuse a user-defined operator; these two make the objects that GrB_mxm, GrB_mxv,
+ * GrB_vxm and GrB_Matrix_reduce_Monoid run through compiled kernels.  `op` / `mul`: a user-defined binary operator or one of the built-ins FIRST, SECOND, PAIR, PLUS,
+ * MINUS, TIMES, MIN, MAX (LOR / LAND / LXOR on BOOL); `add`: a monoid made here or a built-in monoid of one of those operators; `identity`: one value of op's type.
+ * All types are ONE of the 11 real built-in types.  The identity is never combined into a result; mxv and mxm call mul(A(i,k), B(k,j)), vxm calls mul(u(i), A(i,j)).
+ * The objects keep pointers to their operators, have no terminal value and are released by GrB_Monoid_free / GrB_Semiring_free (DESIGN.md section 8). */
+GrB_Info GrBX_Monoid_new_user(GrB_Monoid *monoid, GrB_BinaryOp op, const void *identity);
+GrB_Info GrBX_Semiring_new_user(GrB_Semiring *semiring, GrB_Monoid add, GrB_BinaryOp mul);
+GrB_Info GrBX_usersr_source(GrB_Monoid add, GrB_BinaryOp mul, int kind, char *buf, size_t len); /* the kernel text compiled for them in an operation of `kind` (0 mxv, 1 vxm, 2 mxm, 3 reduce_rows: mul may be NULL) */
+GrB_Info GxB_Monoid_identity(void *identity, GrB_Monoid monoid);
+GrB_Info GxB_Monoid_terminal(bool *has_terminal, void *terminal, GrB_Monoid monoid);
 GrB_Info GrBX_Matrix_residency(const GrB_Matrix A, int *where);   /* which images of the container are valid: bit 0 the host mirror, bit 1 the HBM image (a look: nothing is moved, no deferred work completed) */
 GrB_Info GrBX_Vector_residency(const GrB_Vector v, int *where);
 GrB_Info GrBX_last_error(char *buf, int len);        /* the message of the calling thread's most recent failure (for calls that have no container to ask: GxB_*Op_new, GrB_Monoid_new_*, GrB_Semiring_new) */
