@@ -365,6 +365,7 @@ static void build_tuples(GrB_Type type, const GrB_Index* I, const GrB_Index* J, 
                          std::vector<GrB_Index>* hj, std::vector<uint8_t>& hx) {
   const size_t ts = type->size; const size_t xs = type_size(xcode);
   if (dup && check_obj(dup) && is_user(dup)) userop_refuse(dup->name, "the dup operator of build");
+  if (dup && check_obj(dup) && binop_is_positional(dup->opcode)) fail(GrB_DOMAIN_MISMATCH, std::string("positional operator ") + dup->name + " cannot be used as the dup operator of build: it is the multiplier of the positional semirings, which run in mxm, mxv and vxm only");
   for (GrB_Index k = 0; k < n; k++) {
     if (I[k] >= nrows || (J && J[k] >= ncols)) fail(GrB_INDEX_OUT_OF_BOUNDS, "build: index out of bounds");
   }

@@ -689,6 +689,7 @@ GrB_Info GrB_Matrix_kronecker_Monoid(GrB_Matrix C, const GrB_Matrix Mask, const 
 }
 GrB_Info GrB_Matrix_kronecker_Semiring(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
   if (!op) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
+  if (C && check_obj(C) && check_obj(op->mul) && is_positional_semiring(op)) return guarded(C, [&] { possr_refuse_elementwise(op, "kronecker"); });
   return GrB_Matrix_kronecker_BinaryOp(C, Mask, accum, op->mul, A, B, desc);
 }
 GrB_Info GxB_kron(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {

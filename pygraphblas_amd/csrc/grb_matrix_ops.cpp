@@ -13,6 +13,7 @@
 #include "grb_matops.hpp"
 #include "grb_assign_scalar.hpp"
 #include "grb_lazy.hpp"
+#include "grb_possr.hpp"
 
 using namespace grb;
 
@@ -143,10 +144,48 @@ void user_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semir
   matrix_write_back(C, T, zc, M, dv, accum, t_masked);
 }
 
+// A positional semiring (grb_possr.hpp) in the two steps of user_mxm: T's pattern from the built-in routes with the BOOL ANY_PAIR descriptor and no values, then
+// k_possr_product (or, where the value is i or j of T's own pattern, k_possr_fill) writes the coordinates' monoid into it.  No operand value is read or cast.
+// Hypersparse and complex containers were refused by the caller, before a device was asked for; the dimensions are checked as for every built-in semiring; never
+// queued; none of the batch / few-rows routes.  The write-back is the built-in semirings' own.
+void positional_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc);
+  const Dims a = op_dims(A, dv.tran0), b = op_dims(B, dv.tran1);
+  if (a.c != b.r) fail(GrB_DIMENSION_MISMATCH, "mxm: dimensions do not conform");
+  conform(C, M, {a.r, b.c}, "mxm: dimensions do not conform");
+  lazy_flush();
+  g_last_plan.clear();
+  if (nothing_to_write(C, M, dv)) return;
+  const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);
+  SemiringDesc pd{}; pd.zcode = T_BOOL; pd.addop = B_ANY; pd.mulop = B_PAIR;      // (identity false, no terminal value, no flip)
+  SpgemmCall call{}; call.A = &Ad; call.B = &Bd;
+  DevCSR T; bool t_masked = false;
+  if (M && !dv.mask_comp) {
+    mat_to_device(M);
+    call.M = &M->csr; call.mcode = M->type->code; call.mstruct = dv.mask_struct;
+    spgemm_masked(call, pd, T); t_masked = true;
+  } else spgemm_hash(call, pd, T);
+  const int zc = semiring->add->op->ztype->code;
+  const std::string pattern_plan = g_last_plan;
+  g_last_plan = possr_plan(PK_MXM, semiring);
+  T.val.alloc(T.nnz * type_size(zc) + 16);
+  possr_product_values(semiring->add->op->opcode, zc, pos_coord(semiring->mul->opcode, PK_MXM), Ad, Bd, T);
+  g_last_plan += "pattern: " + pattern_plan;
+  matrix_write_back(C, T, zc, M, dv, accum, t_masked);
+}
+
 void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
-  const bool user = check_obj(semiring) && check_obj(semiring->add) && is_user_semiring(semiring);
+  const bool positional = check_obj(semiring) && check_obj(semiring->add) && check_obj(semiring->mul) && is_positional_semiring(semiring);
+  if (positional) {      // (refused before a device is asked for)
+    check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm");
+    possr_needs_layout(semiring, is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B),
+                       C->type->code >= T_FC32 || A->type->code >= T_FC32 || B->type->code >= T_FC32 || (M && M->type->code >= T_FC32));
+  }
+  const bool user = !positional && check_obj(semiring) && check_obj(semiring->add) && is_user_semiring(semiring);
   if (user) usersr_check(semiring->add->op, semiring->mul);      // (operators the compiled route cannot run are refused before a device is asked for)
   need_device();
+  if (positional) { positional_mxm(C, M, accum, semiring, A, B, desc); return; }
   if (user) { user_mxm(C, M, accum, semiring, A, B, desc); return; }
   if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mxm(C, M, accum, semiring, A, B, desc); return; }   // dimensions beyond the device layouts
   check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm");
@@ -481,13 +520,13 @@ GrB_Info GrB_Matrix_eWiseAdd_BinaryOp(GrB_Matrix C, const GrB_Matrix M, const Gr
 GrB_Info GrB_Matrix_eWiseAdd_Monoid(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->op, A, B, desc, true); }); }
 GrB_Info GrB_Matrix_eWiseAdd_Semiring(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
-  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->add->op, A, B, desc, true); }); }
+  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { possr_refuse_elementwise(op, "eWiseAdd"); do_ewise(C, M, accum, op->add->op, A, B, desc, true); }); }
 GrB_Info GrB_Matrix_eWiseMult_BinaryOp(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; return guarded(C, [&] { do_ewise(C, M, accum, op, A, B, desc, false); }); }
 GrB_Info GrB_Matrix_eWiseMult_Monoid(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->op, A, B, desc, false); }); }
 GrB_Info GrB_Matrix_eWiseMult_Semiring(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
-  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->mul, A, B, desc, false); }); }
+  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { possr_refuse_elementwise(op, "eWiseMult"); do_ewise(C, M, accum, op->mul, A, B, desc, false); }); }
 GrB_Info GrB_Matrix_apply(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_UnaryOp op, const GrB_Matrix A, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
   return guarded(C, [&] { do_apply(C, M, accum, elem_op(op), nullptr, 0, A, desc); });

@@ -10,6 +10,7 @@
 #include "grb_opcommon.hpp"
 #include "grb_spmv.hpp"
 #include "grb_lazy.hpp"
+#include "grb_possr.hpp"
 #include <cmath>
 #include <algorithm>
 
@@ -49,13 +50,42 @@ static void user_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB
   vector_write_back(w, zc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/true);
 }
 
+// A positional semiring (grb_possr.hpp): a route of its own beside the user-defined one.  Hypersparse and complex containers were refused by the caller, before a
+// device was asked for; the dimensions are checked as for every built-in semiring; the call is never queued and completes deferred work first.  T — unmasked, or
+// under the allow bytes of any mask form — comes from k_possr_rows over the CSR of the orientation the built-in product pulls over (the cached transpose for vxm /
+// GrB_INP0), which reads the operand's presence bytes and no values at all.  The write-back is the built-in semirings' own.
+static void positional_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u, GrB_Descriptor desc, bool is_vxm) {
+  if (accum) check_binop(accum, "accum");
+  const DescView dv(desc);
+  const bool useT = is_vxm ? !dv.tran1 : dv.tran0;           // M = useT ? A^T : A
+  const uint64_t mr = useT ? A->ncols : A->nrows, mc = useT ? A->nrows : A->ncols;
+  if (u->n != mc || w->n != mr || (mask && mask->n != mr)) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: dimensions do not conform");
+  lazy_flush(); vec_gate(w);
+  const int kind = is_vxm ? PK_VXM : PK_MXV;
+  g_last_plan = possr_plan(kind, semiring);
+  DevBuf allow_buf; bool nothing = false;
+  const uint8_t* allow = vector_allow(mask, dv, mr, allow_buf, &nothing);
+  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  mat_to_device(A); vec_to_device(u);
+  const DevCSR& R = useT ? mat_csc(A) : A->csr;
+  const int zc = semiring->add->op->ztype->code;
+  DevBuf tval(mr * type_size(zc) + 16), tpres(mr + 16);
+  possr_rows(semiring->add->op->opcode, zc, pos_coord(semiring->mul->opcode, kind), R, u->dpres.as<uint8_t>(), allow, tval.p, tpres.as<uint8_t>());
+  vector_write_back(w, zc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/true);
+}
+
 static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u,
                      GrB_Descriptor desc, bool is_vxm) {
-  const bool user = check_obj(semiring) && check_obj(semiring->add) && is_user_semiring(semiring);
+  const bool positional = check_obj(semiring) && check_obj(semiring->add) && check_obj(semiring->mul) && is_positional_semiring(semiring);
+  if (positional && check_obj(w) && check_obj(A) && check_obj(u) && (!mask || check_obj(mask)))      // (refused before a device is asked for)
+    possr_needs_layout(semiring, is_hyper(A) || is_hyper(w) || is_hyper(u) || is_hyper(mask),
+                       A->type->code >= T_FC32 || w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
+  const bool user = !positional && check_obj(semiring) && check_obj(semiring->add) && is_user_semiring(semiring);
   if (user) usersr_check(semiring->add->op, semiring->mul);      // (operators the compiled route cannot run are refused before a device is asked for)
   need_device();
   if (!check_obj(w) || !check_obj(A) || !check_obj(u) || (mask && !check_obj(mask)))
     fail(GrB_UNINITIALIZED_OBJECT, "mxv/vxm: uninitialised operand");
+  if (positional) { positional_mxv_like(w, mask, accum, semiring, A, u, desc, is_vxm); return; }
   if (user) { user_mxv_like(w, mask, accum, semiring, A, u, desc, is_vxm); return; }
   if (is_hyper(A) || is_hyper(w) || is_hyper(u) || is_hyper(mask)) { hyper_mxv_like(w, mask, accum, semiring, A, u, desc, is_vxm); return; }   // dimensions beyond the device layouts
   if (w->q_reads || w->lazy == 2) vec_gate(w);                // deferred element-wise work on the output completes first (a pending fill, lazy == 1, is dealt with below)

@@ -6,6 +6,7 @@
 #include "grb_device.hpp"
 #include "grb_semiring.hpp"
 #include "grb_userop.hpp"
+#include "grb_possr.hpp"
 #include "grb_lazy.hpp"
 #include <initializer_list>
 #include <vector>
@@ -19,6 +20,8 @@ inline void not_implemented(const std::string& what) { fail(GrB_INVALID_VALUE, "
 inline void check_binop(GrB_BinaryOp op, const char* what) {
   if (!check_obj(op)) fail(GrB_UNINITIALIZED_OBJECT, std::string(what) + " operator is not initialised");
   if (is_user(op)) userop_refuse(op->name, what);
+  // the multiplier of a positional semiring (an internal object, reached through GxB_Semiring_multiply): it runs inside its semiring in mxm / mxv / vxm only
+  if (binop_is_positional(op->opcode)) fail(GrB_DOMAIN_MISMATCH, std::string("positional operator ") + op->name + " cannot be used as " + what + ": it is the multiplier of the positional semirings, which run in mxm, mxv and vxm only");
   if (op->opcode >= B_FIRSTI) not_implemented(std::string("positional / user-defined operator ") + op->name);
   if (op->xtype != op->ytype) not_implemented(std::string("mixed-type operator ") + op->name);
 }

@@ -320,6 +320,7 @@ GrB_Info GrB_Descriptor_free(GrB_Descriptor* d) {
 GrB_Info GrB_Semiring_new(GrB_Semiring* s, GrB_Monoid add, GrB_BinaryOp mul) {
   if (!s) return GrB_NULL_POINTER; if (!check_obj(add) || !check_obj(mul)) return GrB_UNINITIALIZED_OBJECT;
   if (is_user(mul)) { g_last_error = std::string("GrB_Semiring_new: user-defined operator ") + mul->name + " cannot be a semiring's multiplier (it runs in apply and eWise only)"; return GrB_DOMAIN_MISMATCH; }
+  if (binop_is_positional(mul->opcode)) { g_last_error = std::string("GrB_Semiring_new: positional operator ") + mul->name + " is the multiplier of the built-in positional semirings only"; return GrB_DOMAIN_MISMATCH; }
   if (mul->ztype != add->op->ztype) return GrB_DOMAIN_MISMATCH;
   auto* r = new GrB_Semiring_opaque{GRB_MAGIC, add, mul, "", false};
   snprintf(r->name, sizeof r->name, "user_%s_%s", add->op->name, mul->name); *s = r; return GrB_SUCCESS;
@@ -330,6 +331,7 @@ GrB_Info GrB_Monoid_free(GrB_Monoid* m) { if (m && *m && check_obj(*m) && !(*m)-
 static GrB_Info monoid_new(GrB_Monoid* m, GrB_BinaryOp op, int code, const void* identity) {
   if (!m) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
   if (is_user(op)) { g_last_error = std::string("GrB_Monoid_new: user-defined operator ") + op->name + " cannot be a monoid's operator (it runs in apply and eWise only)"; return GrB_DOMAIN_MISMATCH; }
+  if (binop_is_positional(op->opcode)) { g_last_error = std::string("GrB_Monoid_new: positional operator ") + op->name + " cannot be a monoid's operator"; return GrB_DOMAIN_MISMATCH; }
   if (op->xtype != op->ztype || op->ytype != op->ztype) return GrB_DOMAIN_MISMATCH;
   auto* r = new GrB_Monoid_opaque{GRB_MAGIC, op, {0}, false, {0}, "", false};
   cast_scalar(op->ztype->code, r->identity, code, identity);

@@ -311,13 +311,13 @@ GrB_Info GrB_Vector_eWiseAdd_BinaryOp(GrB_Vector w, const GrB_Vector mask, const
 GrB_Info GrB_Vector_eWiseAdd_Monoid(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
   VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op->op, u, v, desc, true); }); }
 GrB_Info GrB_Vector_eWiseAdd_Semiring(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
-  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op->add->op, u, v, desc, true); }); }
+  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { possr_refuse_elementwise(op, "eWiseAdd"); vec_ewise_op(w, mask, accum, op->add->op, u, v, desc, true); }); }
 GrB_Info GrB_Vector_eWiseMult_BinaryOp(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
   VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op, u, v, desc, false); }); }
 GrB_Info GrB_Vector_eWiseMult_Monoid(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
   VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op->op, u, v, desc, false); }); }
 GrB_Info GrB_Vector_eWiseMult_Semiring(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
-  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op->mul, u, v, desc, false); }); }
+  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { possr_refuse_elementwise(op, "eWiseMult"); vec_ewise_op(w, mask, accum, op->mul, u, v, desc, false); }); }
 
 // "Same size, same pattern, equal values" of two vectors of ONE built-in real type as a single pass (what pygraphblas/vector.py:188-235 `Vector.iseq` composes from
 // five calls).  GrB_NO_VALUE: not this function's case (types differ, complex, a size beyond the device layout, no device) — the caller composes it as before.

@@ -129,6 +129,17 @@ for add in ["LOR", "LAND", "LXOR", "EQ", "ANY"]:
 for add, mul in [("LOR", "LAND"), ("LAND", "LOR"), ("LXOR", "LAND")]:
     semirings.append((f"GrB_{add}_{mul}_SEMIRING_BOOL", mon_of(add, "BOOL"), bin_of(mul, "BOOL")))
 semirings.append(("GrB_LXNOR_LOR_SEMIRING_BOOL", "GrB_LXNOR_MONOID_BOOL", "GrB_LOR"))
+# positional semirings (pygraphblas/semiring.py:87-93 names their multipliers): the product term's coordinate in INT32 / INT64, whatever the operands hold.  Their
+# multipliers are INTERNAL binary operators — objects that GxB_Semiring_multiply returns and the printers name, with no exported handle: nothing but mxm / mxv /
+# vxm runs them, and the exported binary-operator set is the one tests/operator_model.py mirrors
+POSITIONAL = ["FIRSTI", "FIRSTI1", "FIRSTJ", "FIRSTJ1", "SECONDI", "SECONDI1", "SECONDJ", "SECONDJ1"]
+posops = []  # (cname, opcode, type): defined in the registry, absent from the header
+for t in ["INT32", "INT64"]:
+    for mul in POSITIONAL:
+        posops.append((f"GxB_{mul}_{t}", "B_" + mul, t))
+    for add in ["MIN", "MAX", "ANY", "PLUS", "TIMES"]:
+        for mul in POSITIONAL:
+            semirings.append((f"GxB_{add}_{mul}_{t}", mon_of(add, t), f"GxB_{mul}_{t}"))
 
 # ---- descriptors ---------------------------------------------------------------------------
 descs = []
@@ -163,6 +174,8 @@ for cname, op, x, z in unops:
 for cname, op, x, y, z in binops:
     inc.append(f'static GrB_BinaryOp_opaque bo_{cname} = {{GRB_MAGIC, grb::{op}, {ty(x)}, {ty(y)}, {ty(z)}, "{cname}", nullptr}};\n'
                f'extern "C" GrB_BinaryOp {cname} = &bo_{cname};\n')
+for cname, op, t in posops:      # (no extern "C" handle)
+    inc.append(f'static GrB_BinaryOp_opaque bo_{cname} = {{GRB_MAGIC, grb::{op}, {ty(t)}, {ty(t)}, {ty(t)}, "{cname}", nullptr}};\n')
 for cname, b in monoids:
     inc.append(f'static GrB_Monoid_opaque mo_{cname} = {{GRB_MAGIC, &bo_{b}, {{0}}, false, {{0}}, "{cname}", true}};\n'
                f'extern "C" GrB_Monoid {cname} = &mo_{cname};\n')
