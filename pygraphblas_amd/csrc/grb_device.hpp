@@ -154,6 +154,13 @@ __device__ __forceinline__ bool mask_truth_at(const void* mval, int mcode, uint6
   }
 }
 
+// ---- the grid of a kernel that gives every row a wave and strides over the rows: 256 threads (four rows) per workgroup, at most 16 workgroups per compute
+// unit, at least 1 (the row kernels of the positional and the user-defined semirings: grb_possr.hip, grb_usersr.cpp)
+inline unsigned row_launch_blocks(uint64_t nrows) {
+  uint64_t blocks = (nrows + 3) / 4, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap; if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+
 // ---- a device word the host can read back (count results, flags) ------------------------------------------
 // 16 KiB of page-locked host memory per thread: the landing place of the small device-to-host readbacks (counts, reduced scalars, the
 // result summary of a BOOL product: 8.1 KiB)

@@ -13,7 +13,6 @@
 #include "grb_matops.hpp"
 #include "grb_assign_scalar.hpp"
 #include "grb_lazy.hpp"
-#include "grb_possr.hpp"
 
 using namespace grb;
 
@@ -104,17 +103,19 @@ namespace {
 
 void check_mat(GrB_Matrix A, const char* what) { if (!check_obj(A)) fail(GrB_UNINITIALIZED_OBJECT, std::string(what) + ": uninitialised matrix"); }
 
+void check_mxm_operands(GrB_Matrix M, GrB_Matrix A, GrB_Matrix B) { check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm"); }
+
 // ---------------------------------------------------------------------------------------------------------------------
-// A user-defined semiring (GrBX_Semiring_new_user, grb_usersr.cpp) in two steps.  The pattern of T is the pattern of the ANY_PAIR product of the operands'
-// patterns: the built-in routes with a BOOL ANY_PAIR semiring and no values — spgemm_masked under a plain mask (its rows are the mask's, in column order),
-// spgemm_hash otherwise (a segmented sort, or the dense path's ordered walk, leaves every row in column order).  The compiled kernel then fills the values,
-// every entry the left-to-right sum of its products in ascending k.  Refused naming the operator on containers without an HBM layout; the accumulator is looked at
-// before the dimensions; never queued; none of the batch / few-rows routes.  The write-back is the built-in semirings' own.
-void user_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
-  check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm");
-  const GrB_BinaryOp add = semiring->add->op, mul = semiring->mul;
-  user_needs_layout(usersr_name(add, mul), "dimension", is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B),
-                    C->type->code >= T_FC32 || A->type->code >= T_FC32 || B->type->code >= T_FC32 || (M && M->type->code >= T_FC32));
+// A semiring that does not run through SemiringDesc — user-defined or positional (SemiringRoute, grb_opcommon.hpp) — in two steps, one driver for both.  The
+// pattern of T is the pattern of the ANY_PAIR product of the operands' patterns: the built-in routes with a BOOL ANY_PAIR semiring and no values — spgemm_masked
+// under a plain mask (its rows are the mask's, in column order), spgemm_hash otherwise (a segmented sort, or the dense path's ordered walk, leaves every row in
+// column order).  The route's kernel then fills the values (a user-defined semiring: every entry the left-to-right sum of its products in ascending k, over operand
+// values cast into T's type; a positional one: the coordinates' monoid, no operand value read or cast).  What is refused before a device is asked for was refused by
+// the caller; a user-defined semiring's layout refusal comes here, then the accumulator is looked at BEFORE the dimensions; never queued; none of the batch /
+// few-rows routes.  The write-back is the built-in semirings' own.  A call that may write nothing (no mask + the complement flag) leaves the plan string empty.
+void off_table_mxm(const SemiringRoute& route, GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
+  check_mxm_operands(M, A, B);
+  route.refuse_after_device(no_layout(C, M, A, B), "dimension");
   if (accum) check_binop(accum, "accum");
   const DescView dv(desc);
   const Dims a = op_dims(A, dv.tran0), b = op_dims(B, dv.tran1);
@@ -132,63 +133,29 @@ void user_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semir
     call.M = &M->csr; call.mcode = M->type->code; call.mstruct = dv.mask_struct;
     spgemm_masked(call, pd, T); t_masked = true;
   } else spgemm_hash(call, pd, T);
-  const int zc = add->ztype->code;
+  const int zc = route.zcode();
   const std::string pattern_plan = g_last_plan;
-  g_last_plan = usersr_plan(USK_MXM, add, mul);
+  g_last_plan = route.plan(PK_MXM);
   T.val.alloc(T.nnz * type_size(zc) + 16);
   DevBuf acast, bcast;
-  const void* av = cast_values(zc, A->type->code, Ad.val.p, Ad.nnz, acast);
-  const void* bv = cast_values(zc, B->type->code, Bd.val.p, Bd.nnz, bcast);
-  usersr_product_values(add, mul, Ad, av, Bd, bv, T);
-  g_last_plan += "pattern: " + pattern_plan;
-  matrix_write_back(C, T, zc, M, dv, accum, t_masked);
-}
-
-// A positional semiring (grb_possr.hpp) in the two steps of user_mxm: T's pattern from the built-in routes with the BOOL ANY_PAIR descriptor and no values, then
-// k_possr_product (or, where the value is i or j of T's own pattern, k_possr_fill) writes the coordinates' monoid into it.  No operand value is read or cast.
-// Hypersparse and complex containers were refused by the caller, before a device was asked for; the dimensions are checked as for every built-in semiring; never
-// queued; none of the batch / few-rows routes.  The write-back is the built-in semirings' own.
-void positional_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
-  if (accum) check_binop(accum, "accum");
-  const DescView dv(desc);
-  const Dims a = op_dims(A, dv.tran0), b = op_dims(B, dv.tran1);
-  if (a.c != b.r) fail(GrB_DIMENSION_MISMATCH, "mxm: dimensions do not conform");
-  conform(C, M, {a.r, b.c}, "mxm: dimensions do not conform");
-  lazy_flush();
-  g_last_plan.clear();
-  if (nothing_to_write(C, M, dv)) return;
-  const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);
-  SemiringDesc pd{}; pd.zcode = T_BOOL; pd.addop = B_ANY; pd.mulop = B_PAIR;      // (identity false, no terminal value, no flip)
-  SpgemmCall call{}; call.A = &Ad; call.B = &Bd;
-  DevCSR T; bool t_masked = false;
-  if (M && !dv.mask_comp) {
-    mat_to_device(M);
-    call.M = &M->csr; call.mcode = M->type->code; call.mstruct = dv.mask_struct;
-    spgemm_masked(call, pd, T); t_masked = true;
-  } else spgemm_hash(call, pd, T);
-  const int zc = semiring->add->op->ztype->code;
-  const std::string pattern_plan = g_last_plan;
-  g_last_plan = possr_plan(PK_MXM, semiring);
-  T.val.alloc(T.nnz * type_size(zc) + 16);
-  possr_product_values(semiring->add->op->opcode, zc, pos_coord(semiring->mul->opcode, PK_MXM), Ad, Bd, T);
+  const void* av = route.operand_values(A->type->code, Ad.val.p, Ad.nnz, acast);
+  const void* bv = route.operand_values(B->type->code, Bd.val.p, Bd.nnz, bcast);
+  route.product_values(Ad, av, Bd, bv, T);
   g_last_plan += "pattern: " + pattern_plan;
   matrix_write_back(C, T, zc, M, dv, accum, t_masked);
 }
 
 void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
-  const bool positional = check_obj(semiring) && check_obj(semiring->add) && check_obj(semiring->mul) && is_positional_semiring(semiring);
-  if (positional) {      // (refused before a device is asked for)
-    check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm");
-    possr_needs_layout(semiring, is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B),
-                       C->type->code >= T_FC32 || A->type->code >= T_FC32 || B->type->code >= T_FC32 || (M && M->type->code >= T_FC32));
-  }
-  const bool user = !positional && check_obj(semiring) && check_obj(semiring->add) && is_user_semiring(semiring);
-  if (user) usersr_check(semiring->add->op, semiring->mul);      // (operators the compiled route cannot run are refused before a device is asked for)
+  const SemiringRoute route = semiring_route(semiring);
+  if (route.kind == SR_POSITIONAL) {      // (its layout refusal needs initialised operands, and comes before a device is asked for)
+    check_mxm_operands(M, A, B);
+    const NoLayout nl = no_layout(C, M, A, B);
+    route.refuse_before_device(&nl);
+  } else route.refuse_before_device(nullptr);
   need_device();
-  if (positional) { positional_mxm(C, M, accum, semiring, A, B, desc); return; }
-  if (user) { user_mxm(C, M, accum, semiring, A, B, desc); return; }
+  if (route.off_table()) { off_table_mxm(route, C, M, accum, A, B, desc); return; }
   if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mxm(C, M, accum, semiring, A, B, desc); return; }   // dimensions beyond the device layouts
-  check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm");
+  check_mxm_operands(M, A, B);
   const DescView dv(desc);
   const Dims a = op_dims(A, dv.tran0), b = op_dims(B, dv.tran1);
   if (a.c != b.r) fail(GrB_DIMENSION_MISMATCH, "mxm: dimensions do not conform");
@@ -258,8 +225,8 @@ void do_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, G
   need_device(); check_mat(A, "eWise"); check_mat(B, "eWise"); if (M) check_mat(M, "eWise");
   const bool user = check_obj(op) && is_user(op);
   if (user) {
-    user_needs_layout(op->name, "dimension", is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B),
-                      C->type->code >= T_FC32 || A->type->code >= T_FC32 || B->type->code >= T_FC32 || (M && M->type->code >= T_FC32));
+    const NoLayout nl = no_layout(C, M, A, B);
+    user_needs_layout(op->name, "dimension", nl.hyper, nl.cplx);
     if (accum) check_binop(accum, "accum");
   } else {
     check_binop(op, "eWise");
@@ -299,8 +266,8 @@ void do_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, G
 void do_apply(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const ElemOp& op, const void* scalar, int scode, GrB_Matrix A, GrB_Descriptor desc) {
   need_device(); check_mat(A, "apply"); if (M) check_mat(M, "apply");
   if (op.user()) {
-    user_needs_layout(op.name, "dimension", is_hyper(C) || is_hyper(M) || is_hyper(A),
-                      C->type->code >= T_FC32 || A->type->code >= T_FC32 || (M && M->type->code >= T_FC32) || scode >= T_FC32);
+    const NoLayout nl = no_layout(C, M, A);
+    user_needs_layout(op.name, "dimension", nl.hyper, nl.cplx || scode >= T_FC32);
     if (accum) check_binop(accum, "accum");
   }
   const DescView dv(desc);
@@ -333,8 +300,8 @@ void do_select(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GxB_SelectOp op, 
   if (!check_obj(op)) fail(GrB_UNINITIALIZED_OBJECT, "select: operator");
   const bool user = is_user(op), has_thunk = thunk && check_obj(thunk) && thunk->has;
   if (user) {
-    user_needs_layout(op->name, "dimension", is_hyper(C) || is_hyper(M) || is_hyper(A),
-                      C->type->code >= T_FC32 || A->type->code >= T_FC32 || (M && M->type->code >= T_FC32) || (has_thunk && thunk->type->code >= T_FC32));
+    const NoLayout nl = no_layout(C, M, A);
+    user_needs_layout(op->name, "dimension", nl.hyper, nl.cplx || (has_thunk && thunk->type->code >= T_FC32));
     if (accum) check_binop(accum, "accum");
   }
   const DescView dv(desc);
@@ -368,7 +335,8 @@ void do_reduce_vector(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Mon
   if (check_obj(monoid->op) && is_user_monoid(monoid)) {
     // a user-defined monoid (GrBX_Monoid_new_user): the row kernel of grb_usersr.cpp with the matrix value as the product; refused on containers without an HBM
     // layout, the accumulator looked at before the dimensions, never queued
-    user_needs_layout(monoid->op->name, "dimension or size", is_hyper(A) || is_hyper(w) || is_hyper(mask), A->type->code >= T_FC32 || w->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
+    const NoLayout nl = no_layout(A, w, mask);
+    user_needs_layout(monoid->op->name, "dimension or size", nl.hyper, nl.cplx);
     if (accum) check_binop(accum, "accum");
     const DescView udv(desc);
     const uint64_t ur = op_dims(A, udv.tran0).r;
@@ -481,7 +449,6 @@ void do_assign_scalar(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const void
   std::vector<uint32_t> rows(rows64.begin(), rows64.end()), cols(cols64.begin(), cols64.end());
   std::sort(cols.begin(), cols.end()); cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
   std::vector<uint8_t> inrow(C->nrows ? C->nrows : 1, 0); for (auto r : rows) inrow[r] = 1;
-  const uint64_t total = 0; (void)total;
   uint64_t nsel = 0; for (uint64_t i = 0; i < C->nrows; i++) nsel += inrow[i];
   if (nsel * cols.size() > 0xFFFFFFF0ull) fail(GrB_OUT_OF_MEMORY, "assign: region too large");
   // the scalar block T (host-built CSR, uploaded)

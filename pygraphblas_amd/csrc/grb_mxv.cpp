@@ -10,11 +10,12 @@
 #include "grb_opcommon.hpp"
 #include "grb_spmv.hpp"
 #include "grb_lazy.hpp"
-#include "grb_possr.hpp"
+#include "grb_bigholes.hpp"
 #include <cmath>
 #include <algorithm>
 
 using namespace grb;
+static_assert(BH_INT32 == T_INT32 && BH_INT64 == T_INT64 && BH_FP32 == T_FP32 && BH_FP64 == T_FP64, "grb_bigholes.hpp names the type codes by number");
 
 static int g_force_method = SPMV_AUTO;   // test hook: GRB_MI355X_SPMV=adaptive|rowgroup|push
 // Where the next product on this thread writes T (round 6, grb_mxm_rows.cpp): a row of a batch matrix's bitmap.  The kernels write the row sums and presence
@@ -22,71 +23,116 @@ static int g_force_method = SPMV_AUTO;   // test hook: GRB_MI355X_SPMV=adaptive|
 // ns x (n values + n bytes) copies per product of the first bitmap version (3.8 of 14 ms of the BC driver at R-MAT-22) are gone.  One-shot: cleared by the call.
 namespace grb { thread_local void* g_mxv_dest_val = nullptr; thread_local uint8_t* g_mxv_dest_pres = nullptr; }
 
-// A user-defined semiring (GrBX_Semiring_new_user, grb_usersr.cpp): containers without an HBM layout are refused naming its operator, the accumulator is looked at
-// before the dimensions, the call is never queued and completes deferred work first.  T — unmasked, or under the allow bytes — comes from the compiled row kernel
-// over the CSR of the orientation the built-in product pulls over; the argument order of the multiplier is the kernel's kind, not a flag.  The write-back is the
-// built-in semirings' own.
-static void user_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u, GrB_Descriptor desc, bool is_vxm) {
-  const GrB_BinaryOp add = semiring->add->op, mul = semiring->mul;
-  user_needs_layout(usersr_name(add, mul), "dimension or size", is_hyper(A) || is_hyper(w) || is_hyper(u) || is_hyper(mask),
-                    A->type->code >= T_FC32 || w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
+// A semiring that does not run through SemiringDesc — user-defined or positional (SemiringRoute, grb_opcommon.hpp): one driver for both.  What is refused before
+// a device is asked for was refused by the caller; a user-defined semiring's layout refusal comes here, then the accumulator is looked at BEFORE the dimensions;
+// the call is never queued and completes deferred work first.  T — unmasked, or under the allow bytes of any mask form — comes from the route's row kernel over
+// the CSR of the orientation the built-in product pulls over (the cached transpose for vxm / GrB_INP0); operand values are cast into T's type where the route
+// reads them at all, and the argument order of the multiplier is the kernel's kind, not a flag.  The write-back is the built-in semirings' own.  A call that may
+// write nothing (no mask + the complement flag) leaves the plan string empty.
+static void off_table_mxv_like(const SemiringRoute& route, GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Matrix A, GrB_Vector u, GrB_Descriptor desc, bool is_vxm) {
+  route.refuse_after_device(no_layout(A, w, u, mask), "dimension or size");
   if (accum) check_binop(accum, "accum");
   const DescView dv(desc);
   const bool useT = is_vxm ? !dv.tran1 : dv.tran0;           // M = useT ? A^T : A
   const uint64_t mr = useT ? A->ncols : A->nrows, mc = useT ? A->nrows : A->ncols;
   if (u->n != mc || w->n != mr || (mask && mask->n != mr)) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: dimensions do not conform");
   lazy_flush(); vec_gate(w);
-  g_last_plan.clear();
+  const int product = is_vxm ? PK_VXM : PK_MXV;
+  g_last_plan = route.plan(product);
   DevBuf allow_buf; bool nothing = false;
   const uint8_t* allow = vector_allow(mask, dv, mr, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
+  if (nothing) { g_last_plan.clear(); if (dv.replace) GrB_Vector_clear(w); return; }
   mat_to_device(A); vec_to_device(u);
   const DevCSR& R = useT ? mat_csc(A) : A->csr;
-  const int zc = add->ztype->code; const size_t zs = type_size(zc);
-  DevBuf tval(mr * zs + 16), tpres(mr + 16), ucast, acast;
-  const void* av = cast_values(zc, A->type->code, R.val.p, R.nnz, acast);
-  const void* uv = cast_values(zc, u->type->code, u->dval.p, u->n, ucast);
-  usersr_rows(is_vxm ? USK_VXM : USK_MXV, add, mul, R, av, uv, u->dpres.as<uint8_t>(), allow, tval.p, tpres.as<uint8_t>());
+  const int zc = route.zcode();
+  DevBuf tval(mr * type_size(zc) + 16), tpres(mr + 16), ucast, acast;
+  const void* av = route.operand_values(A->type->code, R.val.p, R.nnz, acast);
+  const void* uv = route.operand_values(u->type->code, u->dval.p, u->n, ucast);
+  route.rows(product, R, av, uv, u->dpres.as<uint8_t>(), allow, tval.p, tpres.as<uint8_t>());
   vector_write_back(w, zc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/true);
 }
 
-// A positional semiring (grb_possr.hpp): a route of its own beside the user-defined one.  Hypersparse and complex containers were refused by the caller, before a
-// device was asked for; the dimensions are checked as for every built-in semiring; the call is never queued and completes deferred work first.  T — unmasked, or
-// under the allow bytes of any mask form — comes from k_possr_rows over the CSR of the orientation the built-in product pulls over (the cached transpose for vxm /
-// GrB_INP0), which reads the operand's presence bytes and no values at all.  The write-back is the built-in semirings' own.
-static void positional_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u, GrB_Descriptor desc, bool is_vxm) {
-  if (accum) check_binop(accum, "accum");
-  const DescView dv(desc);
-  const bool useT = is_vxm ? !dv.tran1 : dv.tran0;           // M = useT ? A^T : A
-  const uint64_t mr = useT ? A->ncols : A->nrows, mc = useT ? A->nrows : A->ncols;
-  if (u->n != mc || w->n != mr || (mask && mask->n != mr)) fail(GrB_DIMENSION_MISMATCH, "mxv/vxm: dimensions do not conform");
-  lazy_flush(); vec_gate(w);
-  const int kind = is_vxm ? PK_VXM : PK_MXV;
-  g_last_plan = possr_plan(kind, semiring);
-  DevBuf allow_buf; bool nothing = false;
-  const uint8_t* allow = vector_allow(mask, dv, mr, allow_buf, &nothing);
-  if (nothing) { if (dv.replace) GrB_Vector_clear(w); return; }
-  mat_to_device(A); vec_to_device(u);
-  const DevCSR& R = useT ? mat_csc(A) : A->csr;
-  const int zc = semiring->add->op->ztype->code;
-  DevBuf tval(mr * type_size(zc) + 16), tpres(mr + 16);
-  possr_rows(semiring->add->op->opcode, zc, pos_coord(semiring->mul->opcode, kind), R, u->dpres.as<uint8_t>(), allow, tval.p, tpres.as<uint8_t>());
-  vector_write_back(w, zc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/true);
+// The direction of a product (Beamer-style): push walks the rows of the frontier, pull scans the rows of the output.  Push is considered only for a sparse operand
+// and a monoid with a native atomic; it is taken when the edges leaving the frontier (an exact count on the device) are < 1/16 of all entries.  Both operands are
+// resident.  Counts u where that is needed, and records the edge count in u->fe_lb / fe_lb_key.
+struct Direction { bool push, tiny; uint64_t u_nvals; bool u_full; };      // tiny: pushed from the host's list of <= 64 entries; u_nvals: n - 1 ("has holes") where u was not counted
+static Direction choose_direction(int method, const SemiringDesc& sd, GrB_Matrix A, GrB_Vector u, bool useT) {
+  // the entry count of u and (for the direction choice below) the edges leaving it come from one kernel and one round
+  // trip when the count is not known yet — the usual state inside a BFS loop, where u was just updated under a mask
+  uint64_t fe_cached = ~0ull;
+  bool stays_pull = false;            // the operand was too heavy for a push step when it was last counted and has only grown since
+  // (masked products — the frontier-like operands of a BFS — and, since round 4, unmasked ones whose operand has an unknown count: the
+  //  sweeps of the shortest-path loop, whose operand only gains entries; never build a transpose just for this)
+  if (method == SPMV_AUTO && spmspv_push_supported(sd) && u->n && (useT || A->csc.valid)) {
+    const DevCSR& P0 = useT ? A->csr : mat_csc(A);
+    if (u->fe_lb_key == P0.rowptr.serial && P0.rowptr.serial && u->fe_lb * 16 >= P0.nnz + 16) stays_pull = true;      // no kernel, no host round trip (whether or not the count is known: `w.iseq(v)` of the shortest-path loop counts v)
+    else if (!u->dnvals_known) {
+      uint64_t cnt = 0;
+      fe_cached = frontier_edges_and_count(u->dpres.as<uint8_t>(), P0.rowptr.as<uint32_t>(), u->n, &cnt);
+      u->dnvals = cnt; u->dnvals_known = true; u->fe_lb = fe_cached; u->fe_lb_key = P0.rowptr.serial; u->fe_lb_true = false;
+    }
+  }
+  const uint64_t u_nvals = stays_pull && !u->dnvals_known ? (u->n ? u->n - 1 : 0) : vec_dev_nvals(u);             // (not counted: treated as "has holes")
+  const bool u_full = u_nvals == u->n;
+  bool push = false;
+  // an operand of at most 64 entries known as a list on the host (the first level of a BFS): push without counting its edges — 64 rows,
+  // the long ones split over all workgroups, are never worth a pull over every row of a large matrix
+  const bool tiny = u->small_valid && u->small_idx.size() == u_nvals && u_nvals <= 64 && (uint64_t)A->csr.nnz >= (1u << 20) && (useT || A->csc.valid);
+  if (method == SPMV_PUSH) push = spmspv_push_supported(sd);
+  else if (method == SPMV_AUTO && !stays_pull && spmspv_push_supported(sd) && !u_full && u_nvals * 16 < (uint64_t)A->csr.nnz + 16) {
+    if (tiny) push = true;
+    else {
+      const DevCSR& P = useT ? A->csr : mat_csc(A);
+      const uint64_t fe = fe_cached != ~0ull ? fe_cached : frontier_edges(u->dpres.as<uint8_t>(), P.rowptr.as<uint32_t>(), u->n);
+      push = fe * 16 < P.nnz + 16;
+      u->fe_lb = fe; u->fe_lb_key = P.rowptr.serial; u->fe_lb_true = false;                       // (exact now, a lower bound while entries are only added)
+    }
+  }
+  return {push, tiny, u_nvals, u_full};
+}
+
+// "Big holes": a MIN_PLUS / MAX_PLUS product over an operand with holes and no mask (the sweeps of the reference's shortest-path
+// loop, `v<accum MIN> = v MIN_PLUS A`: v has no entry for the vertices not reached yet).  The full-operand pipeline kernels cannot
+// skip absent entries, and no value z makes a + z the monoid's identity for every a.  But when the values are small against the
+// type's range, a BIG fill does the same job exactly: every sum that touches a hole lands beyond a threshold no real sum can
+// reach, so "T(i) is an entry" is "T(i) is on the near side of the threshold" — one pass over the result.  Conditions (else the
+// bitmap variant of the row-block kernel runs, as before): |A's values| and |u's values| below a quarter of BIG (integers: BIG =
+// 2^(bits-2), so nothing wraps; floating point: BIG = infinity and every value finite, sums not overflowing), measured once per
+// matrix and once per call.  R-MAT-22 INT64: 1.0 -> 0.3 ms per sweep.
+// `eligible`: a pull over an operand with holes that the identity fill does not serve, no mask, no forced method.  The constants: grb_bigholes.hpp.
+struct BigHoles { bool on; uint8_t fill[16], thresh[16]; double uabs, aabs; };
+static BigHoles plan_big_holes(bool eligible, const SemiringDesc& sd, GrB_Matrix A, GrB_Vector u, bool useT, uint64_t u_nvals) {
+  BigHoles big{false, {0}, {0}, 0, 0};
+  if (!(eligible && !sd.flip && sd.mulop == B_PLUS && (sd.addop == B_MIN || sd.addop == B_MAX) &&
+        (sd.zcode == T_INT32 || sd.zcode == T_INT64 || sd.zcode == T_FP32 || sd.zcode == T_FP64) && A->type->code == sd.zcode && u->type->code == sd.zcode)) return big;
+  DevCSR& R = useT ? const_cast<DevCSR&>(mat_csc(A)) : A->csr;
+  if (!(R.nnz >= (1u << 20) && u_nvals * 64 >= u->n)) return big;                       // a product the pipeline kernels take, an operand that is not nearly empty
+  uint8_t mn[8], mx[8]; uint64_t bad = 0, cnt = 0;
+  if (R.range_state == 0) {                       // the matrix's range: measured once, cached with the CSR
+    R.range_state = 2;
+    if (value_range(sd.zcode, R.nnz, R.val.p, nullptr, mn, mx, &bad, &cnt) && bad == 0 && cnt) { R.range_abs = range_abs_of(sd.zcode, mn, mx); R.range_state = 1; }
+  }
+  if (R.range_state != 1) return big;
+  bad = 0; cnt = 0;
+  const bool bound_known = u->abs_bound >= 0 && u->lazy == 0 && u->dev_valid;          // left by the previous sweep: no kernel, no read-back
+  if (!bound_known && !(value_range(sd.zcode, u->n, u->dval.p, u->dpres.as<uint8_t>(), mn, mx, &bad, &cnt) && bad == 0 && cnt)) return big;
+  big.uabs = bound_known ? std::fabs(u->abs_bound) : range_abs_of(sd.zcode, mn, mx); big.aabs = R.range_abs;
+  const BigHolesConstants c = big_holes_constants(sd.zcode, sd.addop == B_MIN, big.aabs, big.uabs);
+  big.on = c.admitted; memcpy(big.fill, c.fill, 16); memcpy(big.thresh, c.thresh, 16);
+  return big;
 }
 
 static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u,
                      GrB_Descriptor desc, bool is_vxm) {
-  const bool positional = check_obj(semiring) && check_obj(semiring->add) && check_obj(semiring->mul) && is_positional_semiring(semiring);
-  if (positional && check_obj(w) && check_obj(A) && check_obj(u) && (!mask || check_obj(mask)))      // (refused before a device is asked for)
-    possr_needs_layout(semiring, is_hyper(A) || is_hyper(w) || is_hyper(u) || is_hyper(mask),
-                       A->type->code >= T_FC32 || w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
-  const bool user = !positional && check_obj(semiring) && check_obj(semiring->add) && is_user_semiring(semiring);
-  if (user) usersr_check(semiring->add->op, semiring->mul);      // (operators the compiled route cannot run are refused before a device is asked for)
+  const SemiringRoute route = semiring_route(semiring);
+  const bool initialised = check_obj(w) && check_obj(A) && check_obj(u) && (!mask || check_obj(mask));
+  if (route.off_table()) {
+    const NoLayout nl = initialised ? no_layout(A, w, u, mask) : NoLayout{};
+    route.refuse_before_device(initialised ? &nl : nullptr);
+  }
   need_device();
-  if (!check_obj(w) || !check_obj(A) || !check_obj(u) || (mask && !check_obj(mask)))
-    fail(GrB_UNINITIALIZED_OBJECT, "mxv/vxm: uninitialised operand");
-  if (positional) { positional_mxv_like(w, mask, accum, semiring, A, u, desc, is_vxm); return; }
-  if (user) { user_mxv_like(w, mask, accum, semiring, A, u, desc, is_vxm); return; }
+  if (!initialised) fail(GrB_UNINITIALIZED_OBJECT, "mxv/vxm: uninitialised operand");
+  if (route.off_table()) { off_table_mxv_like(route, w, mask, accum, A, u, desc, is_vxm); return; }
   if (is_hyper(A) || is_hyper(w) || is_hyper(u) || is_hyper(mask)) { hyper_mxv_like(w, mask, accum, semiring, A, u, desc, is_vxm); return; }   // dimensions beyond the device layouts
   if (w->q_reads || w->lazy == 2) vec_gate(w);                // deferred element-wise work on the output completes first (a pending fill, lazy == 1, is dealt with below)
   const DescView dv(desc);
@@ -112,45 +158,11 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     return;
   }
   mat_to_device(A); vec_to_device(u);
-  // the entry count of u and (for the direction choice below) the edges leaving it come from one kernel and one round
-  // trip when the count is not known yet — the usual state inside a BFS loop, where u was just updated under a mask
-  uint64_t fe_cached = ~0ull;
-  bool stays_pull = false;            // the operand was too heavy for a push step when it was last counted and has only grown since
-  // (masked products — the frontier-like operands of a BFS — and, since round 4, unmasked ones whose operand has an unknown count: the
-  //  sweeps of the shortest-path loop, whose operand only gains entries; never build a transpose just for this)
-  if (method == SPMV_AUTO && spmspv_push_supported(sd) && u->n && (useT || A->csc.valid)) {
-    const DevCSR& P0 = useT ? A->csr : mat_csc(A);
-    if (u->fe_lb_key == P0.rowptr.serial && P0.rowptr.serial && u->fe_lb * 16 >= P0.nnz + 16) stays_pull = true;      // no kernel, no host round trip (whether or not the count is known: `w.iseq(v)` of the shortest-path loop counts v)
-    else if (!u->dnvals_known) {
-      uint64_t cnt = 0;
-      fe_cached = frontier_edges_and_count(u->dpres.as<uint8_t>(), P0.rowptr.as<uint32_t>(), u->n, &cnt);
-      u->dnvals = cnt; u->dnvals_known = true; u->fe_lb = fe_cached; u->fe_lb_key = P0.rowptr.serial; u->fe_lb_true = false;
-    }
-  }
-  const uint64_t u_nvals = stays_pull && !u->dnvals_known ? (u->n ? u->n - 1 : 0) : vec_dev_nvals(u);             // (not counted: treated as "has holes")
-  const bool u_full = u_nvals == u->n;
+  const auto [push, tiny, u_nvals, u_full] = choose_direction(method, sd, A, u, useT);
 
   // does the multiply read the matrix / vector values at all?
   const bool uses_a = sd.flip ? binop_uses_y(sd.mulop) : binop_uses_x(sd.mulop);
   const bool uses_u = sd.flip ? binop_uses_x(sd.mulop) : binop_uses_y(sd.mulop);
-
-  // direction (Beamer-style): push walks the rows of the frontier, pull scans the rows of the output.  Push is
-  // considered only for a sparse operand and a monoid with a native atomic; it is taken when the edges leaving the
-  // frontier (an exact count on the device) are < 1/16 of all entries.
-  bool push = false;
-  // an operand of at most 64 entries known as a list on the host (the first level of a BFS): push without counting its edges — 64 rows,
-  // the long ones split over all workgroups, are never worth a pull over every row of a large matrix
-  const bool tiny = u->small_valid && u->small_idx.size() == u_nvals && u_nvals <= 64 && (uint64_t)A->csr.nnz >= (1u << 20) && (useT || A->csc.valid);
-  if (method == SPMV_PUSH) push = spmspv_push_supported(sd);
-  else if (method == SPMV_AUTO && !stays_pull && spmspv_push_supported(sd) && !u_full && u_nvals * 16 < (uint64_t)A->csr.nnz + 16) {
-    if (tiny) push = true;
-    else {
-      const DevCSR& P = useT ? A->csr : mat_csc(A);
-      const uint64_t fe = fe_cached != ~0ull ? fe_cached : frontier_edges(u->dpres.as<uint8_t>(), P.rowptr.as<uint32_t>(), u->n);
-      push = fe * 16 < P.nnz + 16;
-      u->fe_lb = fe; u->fe_lb_key = P.rowptr.serial; u->fe_lb_true = false;                       // (exact now, a lower bound while entries are only added)
-    }
-  }
 
   bool fused_mask = false, excl_small = false;
   if (mask_is_u) {
@@ -191,76 +203,25 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     const bool neutral = sd.addop == B_PLUS || sd.addop == B_TIMES || sd.addop == B_MIN || sd.addop == B_MAX || sd.addop == B_LOR || sd.addop == B_LAND || sd.addop == B_LXOR;
     fill_holes = neutral && (sd.mulop == B_SECOND || (sd.mulop == B_TIMES && sd.addop == B_PLUS && is_int) || (sd.mulop == B_LAND && sd.addop == B_LOR && sd.zcode == T_BOOL));
   }
-  // "Big holes": a MIN_PLUS / MAX_PLUS product over an operand with holes and no mask (the sweeps of the reference's shortest-path
-  // loop, `v<accum MIN> = v MIN_PLUS A`: v has no entry for the vertices not reached yet).  The full-operand pipeline kernels cannot
-  // skip absent entries, and no value z makes a + z the monoid's identity for every a.  But when the values are small against the
-  // type's range, a BIG fill does the same job exactly: every sum that touches a hole lands beyond a threshold no real sum can
-  // reach, so "T(i) is an entry" is "T(i) is on the near side of the threshold" — one pass over the result.  Conditions (else the
-  // bitmap variant of the row-block kernel runs, as before): |A's values| and |u's values| below a quarter of BIG (integers: BIG =
-  // 2^(bits-2), so nothing wraps; floating point: BIG = infinity and every value finite, sums not overflowing), measured once per
-  // matrix and once per call.  R-MAT-22 INT64: 1.0 -> 0.3 ms per sweep.
-  bool big_holes = false; uint8_t big_fill[16] = {0}, big_thresh[16] = {0}; double big_uabs = 0, big_aabs = 0;
-  if (!push && !u_full && !fill_holes && !allow && method == SPMV_AUTO && !sd.flip && sd.mulop == B_PLUS && (sd.addop == B_MIN || sd.addop == B_MAX) &&
-      (sd.zcode == T_INT32 || sd.zcode == T_INT64 || sd.zcode == T_FP32 || sd.zcode == T_FP64) && A->type->code == sd.zcode && u->type->code == sd.zcode) {
-    DevCSR& R = useT ? const_cast<DevCSR&>(mat_csc(A)) : A->csr;
-    if (R.nnz >= (1u << 20) && u_nvals * 64 >= u->n) {                       // a product the pipeline kernels take, an operand that is not nearly empty
-      if (R.range_state == 0) {
-        uint8_t mn[8], mx[8]; uint64_t bad = 0, cnt = 0;
-        R.range_state = 2;
-        if (value_range(sd.zcode, R.nnz, R.val.p, nullptr, mn, mx, &bad, &cnt) && bad == 0 && cnt) {
-          double a = 0, b = 0;
-          if (sd.zcode == T_INT32) { int32_t x, y; memcpy(&x, mn, 4); memcpy(&y, mx, 4); a = (double)x; b = (double)y; }
-          else if (sd.zcode == T_INT64) { int64_t x, y; memcpy(&x, mn, 8); memcpy(&y, mx, 8); a = (double)x; b = (double)y; }
-          else if (sd.zcode == T_FP32) { float x, y; memcpy(&x, mn, 4); memcpy(&y, mx, 4); a = x; b = y; }
-          else { memcpy(&a, mn, 8); memcpy(&b, mx, 8); }
-          R.range_abs = std::max(std::fabs(a), std::fabs(b)); R.range_state = 1;
-        }
-      }
-      if (R.range_state == 1) {
-        uint8_t mn[8], mx[8]; uint64_t bad = 0, cnt = 0;
-        const bool bound_known = u->abs_bound >= 0 && u->lazy == 0 && u->dev_valid;          // left by the previous sweep: no kernel, no read-back
-        if (bound_known || (value_range(sd.zcode, u->n, u->dval.p, u->dpres.as<uint8_t>(), mn, mx, &bad, &cnt) && bad == 0 && cnt)) {
-          double a = 0, b = 0; const bool is_min = sd.addop == B_MIN;
-          if (bound_known) a = b = u->abs_bound;
-          else if (sd.zcode == T_INT32) { int32_t x, y; memcpy(&x, mn, 4); memcpy(&y, mx, 4); a = (double)x; b = (double)y; }
-          else if (sd.zcode == T_INT64) { int64_t x, y; memcpy(&x, mn, 8); memcpy(&y, mx, 8); a = (double)x; b = (double)y; }
-          else if (sd.zcode == T_FP32) { float x, y; memcpy(&x, mn, 4); memcpy(&y, mx, 4); a = x; b = y; }
-          else { memcpy(&a, mn, 8); memcpy(&b, mx, 8); }
-          const double uabs = std::max(std::fabs(a), std::fabs(b));
-          big_uabs = uabs; big_aabs = R.range_abs;
-          if (sd.zcode == T_INT32 && R.range_abs < 268435456.0 && uabs < 268435456.0) {            // 2^28: real sums within +-2^29, hole sums beyond +-(2^30 - 2^28)
-            const int32_t f = is_min ? (1 << 30) : -(1 << 30), th = is_min ? (1 << 29) + (1 << 28) : -((1 << 29) + (1 << 28));
-            memcpy(big_fill, &f, 4); memcpy(big_thresh, &th, 4); big_holes = true;
-          } else if (sd.zcode == T_INT64 && R.range_abs < 1.15e18 && uabs < 1.15e18) {               // < 2^60
-            const int64_t f = is_min ? (1ll << 62) : -(1ll << 62), th = is_min ? (1ll << 61) + (1ll << 60) : -((1ll << 61) + (1ll << 60));
-            memcpy(big_fill, &f, 8); memcpy(big_thresh, &th, 8); big_holes = true;
-          } else if (sd.zcode == T_FP32 && R.range_abs < 8e37 && uabs < 8e37) {                       // sums stay finite
-            const float f = is_min ? INFINITY : -INFINITY; memcpy(big_fill, &f, 4); memcpy(big_thresh, &f, 4); big_holes = true;
-          } else if (sd.zcode == T_FP64 && R.range_abs < 4e307 && uabs < 4e307) {
-            const double f = is_min ? (double)INFINITY : -(double)INFINITY; memcpy(big_fill, &f, 8); memcpy(big_thresh, &f, 8); big_holes = true;
-          }
-        }
-      }
-    }
-  }
+  const BigHoles big = plan_big_holes(!push && !u_full && !fill_holes && !allow && method == SPMV_AUTO, sd, A, u, useT, u_nvals);
   const void* uval = nullptr;
   const bool zero_fill = [&] { for (size_t b = 0; b < zs; b++) if (sd.identity[b]) return false; return true; }();
   if (uses_u && fill_holes && u->holes_zero && u->type->code == sd.zcode && zero_fill) {
     uval = u->dval.p;                                     // written by the element-wise chain kernel with zeros in the holes: no pass at all
-  } else if (big_holes) {
+  } else if (big.on) {
     // the fill goes into u's OWN buffer (the values of absent positions are nobody's business: holes_zero is dropped) and is remembered: the
     // sweeps of the shortest-path loop only add entries — real values, written by the merge's store — so from the second sweep on the operand
     // is ready as it stands (a cast-and-fill pass over the vector per sweep before: 18 us of 357 at R-MAT-22)
     // (the operand is an INPUT: its stored entries never change, only the bytes behind its holes do — a write all the same.  Not while queued work
     //  still reads the vector, nor while an exchange writes into vector buffers on the second stream: then the fill goes into a copy, as before round 4)
-    if (u->holes_big && memcmp(u->holes_big_val, big_fill, zs) == 0) uval = u->dval.p;
+    if (u->holes_big && memcmp(u->holes_big_val, big.fill, zs) == 0) uval = u->dval.p;
     else if (u->q_reads || dist_exchange_pending()) {
       ucast.alloc(u->n * zs + 1);
-      vec_cast_fill_values(sd.zcode, ucast.p, u->type->code, u->dval.p, u->dpres.as<uint8_t>(), u->n, big_fill);
+      vec_cast_fill_values(sd.zcode, ucast.p, u->type->code, u->dval.p, u->dpres.as<uint8_t>(), u->n, big.fill);
       uval = ucast.p;
     } else {
-      vec_cast_fill_values(sd.zcode, u->dval.p, u->type->code, u->dval.p, u->dpres.as<uint8_t>(), u->n, big_fill);      // (same type: big_holes requires it; element-wise, in place)
-      u->holes_zero = false; u->holes_big = true; memcpy(u->holes_big_val, big_fill, 16);
+      vec_cast_fill_values(sd.zcode, u->dval.p, u->type->code, u->dval.p, u->dpres.as<uint8_t>(), u->n, big.fill);      // (same type: plan_big_holes requires it; element-wise, in place)
+      u->holes_zero = false; u->holes_big = true; memcpy(u->holes_big_val, big.fill, 16);
       uval = u->dval.p;
     }
   } else if (uses_u && fill_holes) {
@@ -295,7 +256,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     spmspv_push(call, sd, u_nvals);
   } else {
     DevCSR& R = useT ? const_cast<DevCSR&>(mat_csc(A)) : A->csr;
-    call.M = &R; call.upres = (u_full || fill_holes || big_holes) ? nullptr : u->dpres.as<uint8_t>();
+    call.M = &R; call.upres = (u_full || fill_holes || big.on) ? nullptr : u->dpres.as<uint8_t>();
     if (fused_mask) {
       call.upres = u->dpres.as<uint8_t>(); call.fm_val = u->dval.as<uint8_t>(); call.fm_flags = (uint8_t)((dv.mask_struct ? 1 : 0) | (dv.mask_comp ? 2 : 0));
       // the vector's code bytes (one gather per neighbour instead of two): left behind by the masked assign that wrote it (`v[q] = level`), else made by one pass
@@ -315,16 +276,16 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     // accumulator in the same store — and when w is a fill that was never written (`r[:] = teleport` before the product of
     // gap/prmark.py:21-23), the fill folds into that store too and w is never read
     bool epi_done = false;
-    if (accum_is_monoid && w_full && method == SPMV_AUTO && !big_holes) {       // (with big holes every row has a sum: the threshold must see it first — epi 3)
+    if (accum_is_monoid && w_full && method == SPMV_AUTO && !big.on) {       // (with big holes every row has a sum: the threshold must see it first — epi 3)
       call.epi = w_fill ? 2 : 1; call.epi_w = w_fill ? nullptr : w->dval.p; call.epi_done = &epi_done;
       if (w_fill) memcpy(call.epi_fill, w->lazy_fill, 16);
     }
     // big holes + `w<accum MIN> = ...` with the monoid's own operator (the sweeps of the shortest-path loop, `v.vxm(A, MIN_PLUS, accum=MIN, out=v)`):
     // the merge kernel applies the threshold and the accumulator in its store — no threshold pass over T, no accumulate epilogue, no T at all
-    const bool big_epi = big_holes && accum_is_monoid && method == SPMV_AUTO && w->lazy == 0 && !w->q_reads;
+    const bool big_epi = big.on && accum_is_monoid && method == SPMV_AUTO && w->lazy == 0 && !w->q_reads;
     if (big_epi) {
       vec_to_device(w);
-      call.epi = 3; call.epi_w = w->dval.p; call.epi_wpres = w->dpres.as<uint8_t>(); memcpy(call.epi_fill, big_thresh, 16); call.epi_done = &epi_done;
+      call.epi = 3; call.epi_w = w->dval.p; call.epi_wpres = w->dpres.as<uint8_t>(); memcpy(call.epi_fill, big.thresh, 16); call.epi_done = &epi_done;
     }
     spmv_pull(call, sd);
     if (epi_done && call.epi == 3) {
@@ -332,7 +293,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
       vec_invalidate_host(w);
       w->holes_big = keep_big;
       w->dnvals_known = false; w->dnvals = 0; w->holes_zero = false;      // (entries were only added: the lower bound fe_lb of the edges leaving them stays valid — the next sweep needs no count)
-      w->abs_bound = big_uabs + big_aabs;       // every sum that passed the threshold is within |u| + |A|; MIN / MAX select among such values and w's own (w is u, or held values of an earlier sweep)
+      w->abs_bound = big.uabs + big.aabs;       // every sum that passed the threshold is within |u| + |A|; MIN / MAX select among such values and w's own (w is u, or held values of an earlier sweep)
       if (w != u) w->abs_bound = -1;
       return;
     }
@@ -346,7 +307,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
       return;
     }
   }
-  if (big_holes) big_to_absent(sd.zcode, mr, tval.p, tpres.as<uint8_t>(), big_thresh, sd.addop == B_MIN);       // sums made of fill values only are no entries
+  if (big.on) big_to_absent(sd.zcode, mr, tval.p, tpres.as<uint8_t>(), big.thresh, sd.addop == B_MIN);       // sums made of fill values only are no entries
   const bool w_is_u = w == u; const bool w_was_empty = !w_is_u && w->lazy == 0 && w->dnvals_known && w->dnvals == 0 && !w->host_valid;
   vector_write_back(w, sd.zcode, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/true);
   // every sum that survived the threshold is within |u| + |A|: the bound of the result when w held nothing else (w was empty / is
@@ -354,7 +315,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
   // MAX, FIRST, SECOND, ANY).  An arithmetic accumulator (PLUS, TIMES ...) can leave |w| beyond it: then no bound is recorded and the
   // next sweep measures the range again.
   const bool accum_selects = accum && check_obj(accum) && (accum->opcode == B_MIN || accum->opcode == B_MAX || accum->opcode == B_FIRST || accum->opcode == B_SECOND || accum->opcode == B_ANY);
-  if (big_holes && w->type->code == sd.zcode && (!accum || w_was_empty || (w_is_u && accum_selects))) w->abs_bound = big_uabs + big_aabs;
+  if (big.on && w->type->code == sd.zcode && (!accum || w_was_empty || (w_is_u && accum_selects))) w->abs_bound = big.uabs + big.aabs;
   if (any_done) any_true_written(w->lazy == 0 && w->dev_valid && w->dval.p == tkey ? w : nullptr, tkey, call.any_true_tag, fe_done ? fe_key : 0, fe_nblocks);       // (adopted as they are: w is exactly T)
 }
 

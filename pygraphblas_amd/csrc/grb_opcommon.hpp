@@ -121,6 +121,58 @@ inline const void* cast_values(int dst_code, int src_code, const void* src, uint
   return tmp.p;
 }
 
+// Does any of these containers (nullptr: not given) lack an HBM layout?  `hyper`: a dimension or size beyond the device layout; `cplx`: complex entries.  The two
+// flags user_needs_layout / possr_needs_layout take; a scalar's or a thunk's type is the caller's own extra term.
+struct NoLayout { bool hyper = false, cplx = false; };
+inline void no_layout_of(NoLayout& f, const GrB_Matrix_opaque* A) { if (A) { f.hyper = f.hyper || is_hyper(A); f.cplx = f.cplx || A->type->code >= T_FC32; } }
+inline void no_layout_of(NoLayout& f, const GrB_Vector_opaque* v) { if (v) { f.hyper = f.hyper || is_hyper(v); f.cplx = f.cplx || v->type->code >= T_FC32; } }
+template <class... C> NoLayout no_layout(const C*... containers) { NoLayout f; (no_layout_of(f, containers), ...); return f; }
+
+// ---- a semiring that does not run through SemiringDesc ----------------------------------------------------------------------------------------------------
+// Made once at the top of a product call (semiring_route).  A built-in semiring goes through make_semiring_desc and the SpMV / SpGEMM kernels.  The two off-table
+// kinds — user-defined (GrBX_Semiring_new_user, grb_userop.hpp) and positional (grb_possr.hpp) — share ONE driver per product (off_table_mxv_like in grb_mxv.cpp,
+// off_table_mxm in grb_matrix_ops.cpp): T comes from a small row kernel (mxv / vxm) or "pattern first, values second" (mxm), then the built-in write-back runs;
+// such a call is never queued and completes deferred work first, and its accumulator is looked at before the dimensions.  Where the two differ is answered here.
+// `product`: 0 mxv, 1 vxm, 2 mxm — the numbers of USK_* and of PK_*.
+enum SemiringKind { SR_BUILTIN = 0, SR_USER, SR_POSITIONAL };
+static_assert((int)USK_MXV == (int)PK_MXV && (int)USK_VXM == (int)PK_VXM && (int)USK_MXM == (int)PK_MXM, "one numbering of the products");
+struct SemiringRoute {
+  int kind; GrB_Semiring s;
+  bool off_table() const { return kind != SR_BUILTIN; }
+  int zcode() const { return s->add->op->ztype->code; }      // the type of T
+  // operand values as the kernels take them: cast into T's type (user-defined), or none at all (a positional semiring reads no value)
+  const void* operand_values(int code, const void* val, uint64_t n, DevBuf& tmp) const { return kind == SR_USER ? cast_values(zcode(), code, val, n, tmp) : nullptr; }
+  // the head of the plan string: "usersr<add=...,mul=...,type=...,kind=...> " / "possr<...> "
+  std::string plan(int product) const { return kind == SR_USER ? usersr_plan(product, s->add->op, s->mul) : possr_plan(product, s); }
+  // Refused before a device is asked for: operators the compiled route cannot run (user-defined); containers without an HBM layout, naming the semiring
+  // (positional — `nl`: nullptr while an operand is not initialised, which is an error of its own).
+  void refuse_before_device(const NoLayout* nl) const {
+    if (kind == SR_USER) usersr_check(s->add->op, s->mul);
+    if (kind == SR_POSITIONAL && nl) possr_needs_layout(s, nl->hyper, nl->cplx);
+  }
+  // ... and after it, once the operands are known to be initialised: containers without an HBM layout, naming the operator (user-defined; `extent`: "dimension" of
+  // a matrix, "dimension or size" where vectors take part)
+  void refuse_after_device(const NoLayout& nl, const char* extent) const {
+    if (kind == SR_USER) user_needs_layout(usersr_name(s->add->op, s->mul), extent, nl.hyper, nl.cplx);
+  }
+  // mxv / vxm: t(r) for every allowed row of R (usersr_rows / possr_rows); the plan string ends up as plan(product) + the kernel's name
+  void rows(int product, const DevCSR& R, const void* aval, const void* uval, const uint8_t* upres, const uint8_t* allow, void* tval, uint8_t* tpres) const {
+    if (kind == SR_USER) usersr_rows(product, s->add->op, s->mul, R, aval, uval, upres, allow, tval, tpres);
+    else possr_rows(s->add->op->opcode, zcode(), pos_coord(s->mul->opcode, product), R, upres, allow, tval, tpres);
+  }
+  // mxm: the values of a T whose pattern exists (usersr_product_values / possr_product_values); appends the kernel's name to the plan string
+  void product_values(const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, DevCSR& T) const {
+    if (kind == SR_USER) usersr_product_values(s->add->op, s->mul, A, aval, B, bval, T);
+    else possr_product_values(s->add->op->opcode, zcode(), pos_coord(s->mul->opcode, PK_MXM), A, B, T);
+  }
+};
+// (a handle that is not initialised is nobody's: the built-in route reports it)
+inline SemiringRoute semiring_route(GrB_Semiring s) {
+  if (!check_obj(s) || !check_obj(s->add)) return {SR_BUILTIN, s};
+  if (check_obj(s->mul) && is_positional_semiring(s)) return {SR_POSITIONAL, s};
+  return {is_user_semiring(s) ? SR_USER : SR_BUILTIN, s};
+}
+
 // mask vector -> allow bytes.  Returns nullptr (= everything allowed) when there is no mask and no
 // complement; sets *nothing when there is no mask but the complement flag is set.
 inline const uint8_t* vector_allow(GrB_Vector mask, const DescView& dv, uint64_t n, DevBuf& tmp, bool* nothing) {

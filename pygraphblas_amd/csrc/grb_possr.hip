@@ -131,12 +131,6 @@ __global__ __launch_bounds__(256) void k_possr_fill(const uint32_t* __restrict__
     for (uint32_t p = crp[i] + lane; p < crp[i + 1]; p += 64u) cval[p] = coord_value<T>(c, (uint32_t)i, 0u, ccol[p]);
 }
 
-// a wave per row, 256 threads, at most 16 workgroups per compute unit (the kernels stride)
-unsigned row_blocks(uint64_t nrows) {
-  uint64_t blocks = (nrows + 3) / 4, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap;
-  return (unsigned)blocks;
-}
-
 // f.template operator()<ADD, T>() for the monoid and the type of the call
 template <class F> void with_monoid_and_type(int addop, int zcode, F&& f) {
   auto by_type = [&]<int ADD>() {
@@ -182,7 +176,7 @@ void possr_rows(int addop, int zcode, PosCoord c, const DevCSR& R, const uint8_t
   g_last_plan += "k_possr_rows ";
   if (!R.nrows) return;
   with_monoid_and_type(addop, zcode, [&]<int ADD, class T>() {
-    hipLaunchKernelGGL((k_possr_rows<ADD, T>), dim3(row_blocks(R.nrows)), dim3(256), 0, stream(), R.rowptr.as<uint32_t>(), R.col.as<uint32_t>(), upres, allow, (T*)tval, tpres,
+    hipLaunchKernelGGL((k_possr_rows<ADD, T>), dim3(row_launch_blocks(R.nrows)), dim3(256), 0, stream(), R.rowptr.as<uint32_t>(), R.col.as<uint32_t>(), upres, allow, (T*)tval, tpres,
                        R.nrows, c);
   });
   GRB_HIP(hipGetLastError());
@@ -193,15 +187,15 @@ void possr_product_values(int addop, int zcode, PosCoord c, const DevCSR& A, con
   g_last_plan += fill ? "k_possr_fill " : "k_possr_product ";
   if (!T.nnz || !T.nrows) return;
   if (fill) {
-    if (zcode == T_INT32) hipLaunchKernelGGL((k_possr_fill<int32_t>), dim3(row_blocks(T.nrows)), dim3(256), 0, stream(), T.rowptr.as<uint32_t>(), T.col.as<uint32_t>(), T.val.as<int32_t>(), T.nrows, c);
-    else hipLaunchKernelGGL((k_possr_fill<int64_t>), dim3(row_blocks(T.nrows)), dim3(256), 0, stream(), T.rowptr.as<uint32_t>(), T.col.as<uint32_t>(), T.val.as<int64_t>(), T.nrows, c);
+    if (zcode == T_INT32) hipLaunchKernelGGL((k_possr_fill<int32_t>), dim3(row_launch_blocks(T.nrows)), dim3(256), 0, stream(), T.rowptr.as<uint32_t>(), T.col.as<uint32_t>(), T.val.as<int32_t>(), T.nrows, c);
+    else hipLaunchKernelGGL((k_possr_fill<int64_t>), dim3(row_launch_blocks(T.nrows)), dim3(256), 0, stream(), T.rowptr.as<uint32_t>(), T.col.as<uint32_t>(), T.val.as<int64_t>(), T.nrows, c);
     GRB_HIP(hipGetLastError());
     return;
   }
   DevBuf seen(T.nnz + 16);
   GRB_HIP(hipMemsetAsync(seen.p, 0, T.nnz, stream()));
   with_monoid_and_type(addop, zcode, [&]<int ADD, class V>() {
-    hipLaunchKernelGGL((k_possr_product<ADD, V>), dim3(row_blocks(T.nrows)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), B.rowptr.as<uint32_t>(),
+    hipLaunchKernelGGL((k_possr_product<ADD, V>), dim3(row_launch_blocks(T.nrows)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), A.col.as<uint32_t>(), B.rowptr.as<uint32_t>(),
                        B.col.as<uint32_t>(), T.rowptr.as<uint32_t>(), T.col.as<uint32_t>(), T.val.as<V>(), seen.as<uint8_t>(), T.nrows, c);
   });
   GRB_HIP(hipGetLastError());

@@ -1,5 +1,6 @@
 // grb_possr.hpp — the positional semirings GxB_{MIN,MAX,ANY,PLUS,TIMES}_{FIRSTI,FIRSTI1,FIRSTJ,FIRSTJ1,SECONDI,SECONDI1,SECONDJ,SECONDJ1}_{INT32,INT64} in
-// mxm / mxv / vxm (kernels and launches: grb_possr.hip; the drivers' `positional` blocks: grb_matrix_ops.cpp / grb_mxv.cpp).
+// mxm / mxv / vxm (kernels and launches: grb_possr.hip; the drivers: off_table_mxm in grb_matrix_ops.cpp and off_table_mxv_like in grb_mxv.cpp, which a
+// positional semiring shares with the user-defined ones through a SemiringRoute, grb_opcommon.hpp).
 //
 // The multiplier ignores the operands' values and yields a coordinate of the product term, cast to the semiring's type (INT32 wraps), + 1 for the ...1 forms.
 // With the indices of the operands AFTER the descriptor's transposes:

@@ -48,8 +48,9 @@ void userop_count_launch();               // GrBX_userop_stats' `launched`
 
 // ---- user-defined monoids and semirings (GrBX_Monoid_new_user / GrBX_Semiring_new_user, grb_usersr.cpp) ----------------------------------------------------
 // A monoid or semiring made by those two entry points: its operators are user-defined or built-ins the generated text can express, its types ONE real built-in
-// type.  Every such object — also one made of built-ins only, and a semiring over such a monoid — takes this route.  It runs in mxm / mxv / vxm and the
-// matrix-to-vector reduction through two compiled kernels:
+// type.  Every such object — also one made of built-ins only, and a semiring over such a monoid — takes this route.  It runs in mxm / mxv / vxm (the off-table
+// drivers off_table_mxm / off_table_mxv_like, through a SemiringRoute: grb_opcommon.hpp) and the matrix-to-vector reduction (a block of do_reduce_vector)
+// through two compiled kernels:
 //   rows      t(r) = (+)_p mul(a(p), u(col(p))) over the CSR rows of one operand (mxv, vxm), or (+)_p a(p) (reduce_rows): a wave per row
 //   product   the values of T = A (+).(x) B on a pattern that is already there: a wave per row of T
 // The monoid's identity is never combined into a result (an entry starts from its first product), and the multiplier's argument order is a constant of the text.

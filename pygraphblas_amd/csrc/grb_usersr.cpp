@@ -8,7 +8,8 @@
 // The objects keep POINTERS to their operators (freeing one while the object lives is the caller's error, as in SuiteSparse), have no terminal value, and are
 // released by GrB_Monoid_free / GrB_Semiring_free.  Nothing up to here needs a device.
 //
-// Running one — GrB_mxm, GrB_mxv, GrB_vxm, GrB_Matrix_reduce_Monoid (the drivers' `user` blocks in grb_matrix_ops.cpp / grb_mxv.cpp) — goes through two kernels
+// Running one — GrB_mxm, GrB_mxv, GrB_vxm (the off-table drivers of grb_matrix_ops.cpp / grb_mxv.cpp, through a SemiringRoute: grb_opcommon.hpp) and
+// GrB_Matrix_reduce_Monoid (a block of do_reduce_vector) — goes through two kernels
 // generated around the definitions like grb_userop.cpp's (every function of a definition made a device function, each definition in a namespace of its own so that
 // two operators may share a function name) and compiled through the same table and code-object cache (`usersr-<hash>.co`):
 //   grb_usersr_rows      mxv / vxm / reduce_rows: a wave64 per row of the CSR the driver picked, rows in a grid-stride loop; lanes stride over the row's entries,
@@ -164,10 +165,9 @@ std::string both_names(const GrB_BinaryOp_opaque* add, const GrB_BinaryOp_opaque
   return s.empty() ? std::string(add->name) : s;
 }
 
-// a wave per row, 256 threads, at most 16 workgroups per compute unit (the kernels stride)
+// a wave per row (row_launch_blocks, grb_device.hpp: the kernels stride)
 void launch_rows(hipFunction_t fn, uint64_t nrows, void** args) {
-  uint64_t blocks = (nrows + 3) / 4, cap = (uint64_t)device_cus() * 16; if (cap < 1) cap = 1; if (blocks > cap) blocks = cap;
-  GRB_HIP(hipModuleLaunchKernel(fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream(), args, nullptr));
+  GRB_HIP(hipModuleLaunchKernel(fn, row_launch_blocks(nrows), 1, 1, 256, 1, 1, 0, stream(), args, nullptr));
   userop_count_launch();
 }
 

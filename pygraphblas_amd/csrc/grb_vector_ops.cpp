@@ -174,8 +174,8 @@ static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_
   if (!check_obj(u) || !check_obj(v) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "eWise: uninitialised operand");
   const bool user = check_obj(op) && is_user(op);
   if (user) {
-    user_needs_layout(op->name, "size", is_hyper(w) || is_hyper(u) || is_hyper(v) || (mask && is_hyper(mask)),
-                      w->type->code >= T_FC32 || u->type->code >= T_FC32 || v->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32));
+    const NoLayout nl = no_layout(w, u, v, mask);
+    user_needs_layout(op->name, "size", nl.hyper, nl.cplx);
     if (accum) check_binop(accum, "accum");
   } else {
     check_binop(op, "eWise");
@@ -231,8 +231,8 @@ static void vec_apply_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, cons
   need_device();
   if (!check_obj(u) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "apply: uninitialised operand");
   if (op.user()) {
-    user_needs_layout(op.name, "size", is_hyper(w) || is_hyper(u) || (mask && is_hyper(mask)),
-                      w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32) || scode >= T_FC32);
+    const NoLayout nl = no_layout(w, u, mask);
+    user_needs_layout(op.name, "size", nl.hyper, nl.cplx || scode >= T_FC32);
     if (accum) check_binop(accum, "accum");
   }
   const DescView dv(desc); const uint64_t n = w->n;
@@ -268,8 +268,8 @@ static void vec_select(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GxB_Se
   if (mask && !check_obj(mask)) fail(GrB_UNINITIALIZED_OBJECT, "select: uninitialised mask");
   const bool user = is_user(op), has_thunk = thunk && check_obj(thunk) && thunk->has;
   if (user) {
-    user_needs_layout(op->name, "size", is_hyper(w) || is_hyper(u) || (mask && is_hyper(mask)),
-                      w->type->code >= T_FC32 || u->type->code >= T_FC32 || (mask && mask->type->code >= T_FC32) || (has_thunk && thunk->type->code >= T_FC32));
+    const NoLayout nl = no_layout(w, u, mask);
+    user_needs_layout(op->name, "size", nl.hyper, nl.cplx || (has_thunk && thunk->type->code >= T_FC32));
     if (accum) check_binop(accum, "accum");
   }
   const DescView dv(desc); const uint64_t n = w->n;
