@@ -132,6 +132,8 @@ void build_allow(uint64_t n, int mcode, const void* mval, const uint8_t* mpres, 
 static inline bool unop_needs_math(int op) { return op >= U_SQRT && op <= U_ISFINITE; }
 
 // ---- count present ------------------------------------------------------------------------------------
+// A presence byte means "entry" when it is not zero, whatever its bits (GrBX_Vector_import_Bitmap keeps the caller's bytes); the library itself writes 0 and 1.
+__device__ __forceinline__ uint32_t nz_bytes(uint32_t x) { return ((x | ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu)) & 0x80808080u) >> 7; }      // 0x01 in every byte of x that is not zero
 // One atomic per workgroup and at most 512 workgroups: same-address atomics complete one after the other (~10-80 ns each on
 // this part), so a counter bumped by every wave of a 4096-block grid cost 40-80 us for a 4 MB bitmap.
 __device__ __forceinline__ void block_add_u64(unsigned long long c, unsigned long long* out) {
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(256) void k_count(const uint8_t* __restrict__ pres,
   // 16 bytes per lane per load
   const uint64_t n16 = n / 16, T = gridDim.x * 256ull;
   const uint4* p4 = (const uint4*)pres;
-  auto ones = [](const uint4& v) { return (unsigned)(__popc(v.x & 0x01010101u) + __popc(v.y & 0x01010101u) + __popc(v.z & 0x01010101u) + __popc(v.w & 0x01010101u)); };
+  auto ones = [](const uint4& v) { return (unsigned)(__popc(nz_bytes(v.x)) + __popc(nz_bytes(v.y)) + __popc(nz_bytes(v.z)) + __popc(nz_bytes(v.w))); };      // any non-zero byte is an entry
   uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   for (; i + 3 * T < n16; i += 4 * T) { const uint4 a = p4[i], b = p4[i + T], d = p4[i + 2 * T], e = p4[i + 3 * T]; c += ones(a) + ones(b) + ones(d) + ones(e); }
   for (; i < n16; i += T) c += ones(p4[i]);
@@ -560,7 +562,6 @@ template <class T, bool MATH> __global__ void k_vec_assign_scalar_masked(uint64_
 // the same with one-byte values on both sides and no accumulator (`v[q] = level`: UINT8 levels under a BOOL frontier, once per BFS level):
 // 16 positions per thread — 16-byte loads and stores, the mask test and the select done on four bytes at a time — instead of a byte per
 // thread and instruction (7-13 us for 4 M positions; the bytes alone are 6 streams of 4 MB)
-__device__ __forceinline__ uint32_t nz_bytes(uint32_t x) { return ((x | ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu)) & 0x80808080u) >> 7; }      // 0x01 in every byte of x that is not zero
 __global__ void k_assign_masked_bytes(uint64_t n, uint8_t* __restrict__ wval, uint8_t* __restrict__ wpres, const uint8_t* __restrict__ mval, const uint8_t* __restrict__ mpres,
                                       bool mstruct, bool mcomp, uint8_t s, bool replace, uint8_t* __restrict__ code) {
   const uint64_t nv = n / 16; const uint32_t s4 = (uint32_t)s * 0x01010101u;

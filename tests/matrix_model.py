@@ -96,6 +96,14 @@ def binop(op, typ, a, b):
         elif op == "LOR": r = (a != 0) | (b != 0)
         elif op == "LAND": r = (a != 0) & (b != 0)
         elif op == "LXOR": r = (a != 0) ^ (b != 0)
+        elif op in ("EQ", "LXNOR") and typ == "BOOL": r = a == b
+        elif op == "ISEQ": r = a == b                             # (the IS* comparisons answer 0 / 1 in the operands' type)
+        elif op == "ISGT": r = a > b
+        elif op == "ISLT": r = a < b
+        elif op == "BOR" and not fp: r = a | b
+        elif op == "BAND" and not fp: r = a & b
+        elif op == "BXOR" and not fp: r = a ^ b
+        elif op == "BXNOR" and not fp: r = ~(a ^ b)
         else: raise ValueError(op)
         return np.asarray(r).astype(NP[typ])
 
@@ -193,6 +201,11 @@ def reduce_rows(monoid, typ, m):
 
 
 # ---- the write-back ------------------------------------------------------------------------------------------------------------------------------------
+def mask_truth(vals):
+    """The truth of stored mask values: != 0 (-0.0 is false, NaN is true)."""
+    return np.asarray(vals) != 0
+
+
 def mask_allows(mask, struct, comp, keys):
     """For each key: does the mask (None: no mask) let the position be written?"""
     if mask is None:
@@ -203,7 +216,7 @@ def mask_allows(mask, struct, comp, keys):
     stored[inside] = mask.keys[pos[inside]] == keys[inside]
     truth = stored.copy()
     if not struct:
-        truth[stored] = mask.vals[pos[stored]] != 0            # (-0.0 != 0 is false, NaN != 0 is true)
+        truth[stored] = mask_truth(mask.vals[pos[stored]])
     return truth != comp
 
 

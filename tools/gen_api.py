@@ -501,6 +501,9 @@ GrB_Info GrBX_Matrix_import_CSR(GrB_Matrix *A, GrB_Type type, GrB_Index nrows, G
                  const uint32_t *rowptr, const uint32_t *colidx, const void *values, int location);
 GrB_Info GrBX_Matrix_export_CSR(const GrB_Matrix A, uint32_t *rowptr, uint32_t *colidx, void *values, int location);
 GrB_Info GrBX_Vector_import_Full(GrB_Vector *v, GrB_Type type, GrB_Index n, const void *values, int location);
+/* present[i] != 0 means "position i holds an entry": ANY non-zero byte, not only 1.  The bytes are copied as they are (NULL: every position
+   holds an entry); every operation, nvals included, reads them by that rule, and export_Bitmap hands back 1 for an entry the library wrote and
+   the caller's own byte for an entry it never touched. */
 GrB_Info GrBX_Vector_import_Bitmap(GrB_Vector *v, GrB_Type type, GrB_Index n, const void *values,
                  const uint8_t *present, int location);
 GrB_Info GrBX_Vector_export_Bitmap(const GrB_Vector v, void *values, uint8_t *present, int location);
