@@ -86,15 +86,13 @@ static bool mat_edit_route(GrB_Matrix A) {
 static bool vec_edit_route(GrB_Vector v) {
   return v->dev_valid && !v->host_valid && !v->iso_full && v->lazy == 0 && v->q_reads == 0 && v->type->code < T_FC32 && v->n <= GRB_DIM_DEVICE_MAX && device_ok() && !edit_env_off();
 }
+// what was derived from the VALUES of the device CSR: an overwrite in place drops it (mat_set, the values-only flush)
+static void mat_values_changed(GrB_Matrix A) { A->csc.clear(); A->csr.xcd.reset(); A->csr.range_state = 0; A->bm.clear(); A->csr.heads_valid = false; }      // (the row heads carry the BOOL value of a row's first four entries)
 // what was derived from the structure of the device CSR (the list of mat_invalidate_host, and the bitmap cache)
 static void mat_drop_derived(GrB_Matrix A) {
   A->csc.clear(); A->bm.clear(); A->csr.has_plan = false; A->csr.plan_blocks.reset(); A->csr.plan_aux.reset();
   A->csr.wp_rs.reset(); A->csr.wp_hot.reset(); A->csr.wp_pcol.reset(); A->csr.wp_tsize = 0; A->csr.xcd.reset();
   A->csr.heads_valid = false; A->csr.range_state = 0; A->csr.locality_pct = -1; A->csr.pipe_uses = 0;
-}
-// every cached fact about the device image of a vector (the list of vec_invalidate_device); the entry count is recounted when asked for
-static void vec_drop_facts(GrB_Vector v) {
-  v->holes_zero = false; v->holes_big = false; v->lor_state = 0; v->abs_bound = -1; v->small_valid = false; v->code_valid = false; v->dnvals_known = false; v->fe_lb = 0; v->fe_lb_key = 0;
 }
 void mat_edit_flush(GrB_Matrix A) {
   if (!mat_edits_queued(A)) return;
@@ -108,9 +106,7 @@ void mat_edit_flush(GrB_Matrix A) {
   const EditCounts n = csr_apply_edits(A->csr, ts, k, ei.data(), ej.data(), del.data(), x.data(), out, &structural);      // (neither csr_apply_edits nor anything it calls comes back here)
   P.clear(); P.shrink_to_fit();                              // only now: a flush that failed (allocation, launch, the entry-count limit) leaves the queue as it was, and the caller its error
   if (structural) { A->csr = std::move(out); mat_drop_derived(A); }
-  else if (n.set) {                                          // values only: what an overwrite in place drops (mat_set)
-    A->csc.clear(); A->csr.xcd.reset(); A->csr.range_state = 0; A->bm.clear(); A->csr.heads_valid = false;
-  }
+  else if (n.set) mat_values_changed(A);
   g_last_plan = "edit<on=matrix,set=" + std::to_string(n.set) + ",ins=" + std::to_string(n.ins) + ",del=" + std::to_string(n.del) + "> k_edit_locate " +
                 (structural ? "k_edit_rowptr k_edit_stream k_edit_place " : n.set ? "k_edit_values " : "") + g_last_plan;
 }
@@ -122,7 +118,7 @@ void vec_edit_flush(GrB_Vector v) {
   const uint32_t k = (uint32_t)ord.size(); uint32_t nset = 0;
   std::vector<uint32_t> idx(k); std::vector<uint8_t> del(k), x((size_t)k * ts);
   for (uint32_t e = 0; e < k; e++) { const auto& r = P[ord[e]]; idx[e] = (uint32_t)r.i; del[e] = r.del ? 1 : 0; nset += r.del ? 0 : 1; memcpy(&x[(size_t)e * ts], r.x, ts); }
-  vec_drop_facts(v);
+  v->facts.image_replaced(0, false);
   vec_apply_edits(ts, v->n, k, idx.data(), del.data(), x.data(), v->dval.p, v->dpres.as<uint8_t>());
   P.clear(); P.shrink_to_fit();                              // only now: a flush that failed leaves the queue as it was (the scatter stores the same bytes when it runs again)
   // (a bitmap store does not tell an overwrite from an insert: `set` counts both, `ins` is not known)
@@ -244,17 +240,17 @@ unsigned long long* fe_summary_host() { return t_any.host_dev; }      // (after 
 void any_true_written(GrB_Vector w, const void* key, uint32_t tag, uint64_t fe_key, uint32_t fe_nblocks) {
   AnyTrue& s = t_any;
   s.owner = w; s.fe_has = fe_key != 0 && w != nullptr && fe_nblocks > 0 && fe_nblocks <= FE_HOST_PAIRS; s.fe_key = fe_key; s.fe_nblocks = fe_nblocks;
-  if (w) { w->lor_state = 1; w->lor_key = key; w->lor_tag = tag; }
+  if (w) { w->facts.lor_state = 1; w->facts.lor_key = key; w->facts.lor_tag = tag; }
 }
 bool any_true_lookup(GrB_Vector u, bool* value) {
-  if (!u->lor_state || u->lazy || u->q_reads || !u->dev_valid || u->dval.p != u->lor_key) return false;
-  if (u->lor_state == 1) {
+  if (!u->facts.lor_state || u->lazy || u->q_reads || !u->dev_valid || u->dval.p != u->facts.lor_key) return false;
+  if (u->facts.lor_state == 1) {
     AnyTrue& s = t_any;
-    if (s.owner != u || s.tag != u->lor_tag) { u->lor_state = 0; return false; }
+    if (s.owner != u || s.tag != u->facts.lor_tag) { u->facts.lor_state = 0; return false; }
     if (s.fe_has) {
       // every workgroup stores  tag (24 bits) | true entries, saturating (8) | edge sum, saturating (32)  into its host word: wait for all of them,
       // and clear what was read (a word is never mistaken for a later product's with the same 24-bit tag)
-      volatile unsigned long long* h = s.host; const unsigned long long want = (unsigned long long)(u->lor_tag & 0xFFFFFFu);
+      volatile unsigned long long* h = s.host; const unsigned long long want = (unsigned long long)(u->facts.lor_tag & 0xFFFFFFu);
       unsigned long long fe = 0, cnt = 0; uint32_t i = 0; const uint32_t nb = s.fe_nblocks;
       for (int round = 0; round < 2 && i < nb; round++) {
         for (uint64_t spin = 0; spin < (1ull << 22) && i < nb;) {
@@ -264,24 +260,27 @@ bool any_true_lookup(GrB_Vector u, bool* value) {
         if (i < nb) GRB_HIP(hipStreamSynchronize(stream()));      // (far beyond any product's time: let a failed launch report itself, then look once more)
       }
       s.owner = nullptr; s.fe_has = false;
-      if (i < nb) { u->lor_state = 0; return false; }
-      u->lor_state = cnt ? 3 : 2;
-      u->fe_lb = fe; u->fe_lb_key = s.fe_key; u->fe_lb_true = true;      // the edges leaving u's true entries (exact when the kernel counted: a lower bound is all the direction choice asks for)
+      if (i < nb) { u->facts.lor_state = 0; return false; }
+      u->facts.lor_state = cnt ? 3 : 2;
+      u->facts.fe_lb = fe; u->facts.fe_lb_key = s.fe_key; u->facts.fe_lb_true = true;      // the edges leaving u's true entries (exact when the kernel counted: a lower bound is all the direction choice asks for)
     } else {
       uint32_t* pin = (uint32_t*)pinned_scratch();
       GRB_HIP(hipMemcpyAsync(pin, s.word.p, 4, hipMemcpyDeviceToHost, stream()));
       GRB_HIP(hipStreamSynchronize(stream()));
-      u->lor_state = pin[0] == u->lor_tag ? 3 : 2; s.owner = nullptr;
+      u->facts.lor_state = pin[0] == u->facts.lor_tag ? 3 : 2; s.owner = nullptr;
     }
   }
-  *value = u->lor_state == 3; return true;
+  *value = u->facts.lor_state == 3; return true;
 }
 
-void vec_invalidate_device(GrB_Vector v) { vec_overwritten(v); v->holes_zero = false; v->holes_big = false; v->lor_state = 0; v->abs_bound = -1; v->small_valid = false; v->code_valid = false; v->dev_valid = false; v->dval.reset(); v->dpres.reset(); v->dnvals = 0; v->dnvals_known = true; v->fe_lb = 0; v->fe_lb_key = 0; }
-void vec_invalidate_host(GrB_Vector v) {
-  vec_overwritten(v); v->holes_zero = false; v->holes_big = false; v->lor_state = 0; v->abs_bound = -1; v->small_valid = false; v->code_valid = false; v->dev_elem_ops = 0;
+void vec_invalidate_device(GrB_Vector v) { vec_overwritten(v); v->dev_valid = false; v->dval.reset(); v->dpres.reset(); v->facts.image_dropped(); }
+// the device image was written: deferred work on v is settled and the host mirror goes
+static void vec_host_dropped(GrB_Vector v) {
+  vec_overwritten(v); v->dev_elem_ops = 0;
   v->host_valid = false; v->hi.clear(); v->hx.clear(); v->pending.clear(); v->hi.shrink_to_fit(); v->hx.shrink_to_fit();
 }
+void vec_invalidate_host(GrB_Vector v, uint64_t nvals, bool known) { vec_host_dropped(v); v->facts.image_replaced(nvals, known); }
+void vec_device_extended(GrB_Vector v) { vec_host_dropped(v); v->facts.image_extended(); }
 void vec_to_host(GrB_Vector v) {
   vec_gate(v);
   if (v->iso_full) fail(GrB_INSUFFICIENT_SPACE, ISO_MSG);
@@ -321,11 +320,11 @@ void vec_to_device(GrB_Vector v) {
       scatter_entries(k, di.as<uint32_t>(), dx.p, ts, v->dval.p, v->dpres.as<uint8_t>());
       GRB_HIP(hipStreamSynchronize(stream()));                          // the host staging vectors go out of scope
     }
-    v->dnvals = k; v->dnvals_known = true; v->dev_valid = true;
+    v->facts.image_replaced(k, true); v->dev_valid = true;
     if (k <= 64) {                                                       // the entries as a list (see small_idx)
-      v->small_idx.assign(k, 0); bool truthy = true;
+      v->facts.small_idx.assign(k, 0); bool truthy = true;
       for (uint32_t e = 0; e < k; e++) {
-        v->small_idx[e] = (uint32_t)v->hi[e];
+        v->facts.small_idx[e] = (uint32_t)v->hi[e];
         // truth as the mask kernels test it — value != 0 in the vector's type: the bytes of an FP -0.0 are not all zero, the value is false
         bool nz = false;
         const uint8_t* px = &v->hx[(size_t)e * ts];
@@ -334,7 +333,7 @@ void vec_to_device(GrB_Vector v) {
         else for (size_t b = 0; b < ts; b++) nz = nz || px[b] != 0;
         truthy = truthy && nz;
       }
-      v->small_valid = true; v->small_truthy = truthy;
+      v->facts.small_valid = true; v->facts.small_truthy = truthy;
     }
     return;
   }
@@ -345,12 +344,12 @@ void vec_to_device(GrB_Vector v) {
     GRB_HIP(hipMemcpyAsync(v->dpres.p, pres.data(), n, hipMemcpyHostToDevice, stream()));
     GRB_HIP(hipStreamSynchronize(stream()));
   }
-  v->dnvals = v->hi.size(); v->dnvals_known = true; v->dev_valid = true;
+  v->facts.image_replaced(v->hi.size(), true); v->dev_valid = true;
 }
 uint64_t vec_dev_nvals(GrB_Vector v) {
   vec_gate(v);
-  if (!v->dnvals_known) { v->dnvals = count_present(v->dpres.as<uint8_t>(), v->n); v->dnvals_known = true; }
-  return v->dnvals;
+  if (!v->facts.dnvals_known) { v->facts.dnvals = count_present(v->dpres.as<uint8_t>(), v->n); v->facts.dnvals_known = true; }
+  return v->facts.dnvals;
 }
 uint64_t vec_nvals(GrB_Vector v) {
   vec_gate(v);
@@ -547,8 +546,7 @@ static GrB_Info mat_set(GrB_Matrix C, const void* x, int xcode, GrB_Index i, GrB
         uint8_t* pin = (uint8_t*)pinned_scratch() + 64; cast_scalar(C->type->code, pin, xcode, x);
         GRB_HIP(hipMemcpyAsync((uint8_t*)C->csr.val.p + pos * C->type->size, pin, C->type->size, hipMemcpyHostToDevice, stream()));
         GRB_HIP(hipStreamSynchronize(stream()));
- C->csc.clear(); C->csr.xcd.reset(); C->csr.range_state = 0; C->bm.clear();
-        C->csr.heads_valid = false;      // the row heads carry the BOOL value of a row's first four entries
+        mat_values_changed(C);
         return;
       }
     }
@@ -628,7 +626,7 @@ GrB_Info GrB_Vector_dup(GrB_Vector* w, const GrB_Vector u) {
       const size_t ts = u->type->size;
       r->dval.alloc(u->n * ts ? u->n * ts : 1); r->dpres.alloc(u->n ? u->n : 1);
       if (u->n) dev_copy2(r->dval.p, u->dval.p, u->n * ts, r->dpres.p, u->dpres.p, u->n);
-      r->dnvals = u->dnvals; r->dnvals_known = u->dnvals_known; r->dev_valid = true; r->host_valid = false;
+      r->facts.image_replaced(u->facts.dnvals, u->facts.dnvals_known); r->dev_valid = true; r->host_valid = false;
     }
   });
   if (info) { GrB_Vector_free(&r); return info; }
@@ -653,9 +651,8 @@ GrB_Info GrB_Vector_resize(GrB_Vector v, GrB_Index n) {
         DevBuf nval(n * ts ? n * ts : 1), npres(n ? n : 1);
         if (keep) dev_copy2(nval.p, v->dval.p, keep * ts, npres.p, v->dpres.p, keep);
         if (n > keep) { GRB_HIP(hipMemsetAsync((uint8_t*)nval.p + keep * ts, 0, (n - keep) * ts, stream())); GRB_HIP(hipMemsetAsync(npres.as<uint8_t>() + keep, 0, n - keep, stream())); }
-        const bool known = v->dnvals_known && n >= v->n; const uint64_t cnt = v->dnvals;      // (a longer vector holds what it held)
-        vec_drop_facts(v);
-        v->dval = std::move(nval); v->dpres = std::move(npres); v->dcode.reset(); v->n = n; v->dnvals = cnt; v->dnvals_known = known;
+        v->facts.image_replaced(v->facts.dnvals, v->facts.dnvals_known && n >= v->n);      // (a longer vector holds what it held)
+        v->dval = std::move(nval); v->dpres = std::move(npres); v->dcode.reset(); v->n = n;
       }
       g_last_plan = "resize<on=vector,rows=" + std::to_string(n) + ",cols=1> ";
       return;
@@ -668,7 +665,7 @@ GrB_Info GrB_Vector_removeElement(GrB_Vector v, GrB_Index i) {
   CHECK_VEC(v); if (i >= v->n) return GrB_INVALID_INDEX;
   return guarded(v, [&] {
     GrB_Vector_opaque::Pending p{i, true, {0}};
-    if (!v->host_valid && !v->iso_full) { if (v->lazy | v->q_reads) vec_resolve(v); if (vec_edit_route(v)) { v->pending.push_back(p); vec_drop_facts(v); return; } }      // it lives in HBM (a deferred chain completed first): queued for the device
+    if (!v->host_valid && !v->iso_full) { if (v->lazy | v->q_reads) vec_resolve(v); if (vec_edit_route(v)) { v->pending.push_back(p); v->facts.image_replaced(0, false); return; } }      // it lives in HBM (a deferred chain completed first): queued for the device
     vec_to_host(v); v->pending.push_back(p); vec_invalidate_device(v); });
 }
 GrB_Info GxB_Vector_Option_set(GrB_Vector v, int field, ...) {
@@ -703,7 +700,7 @@ static GrB_Info vec_set(GrB_Vector w, const void* x, int xcode, GrB_Index i) {
   CHECK_VEC(w); if (i >= w->n) return GrB_INVALID_INDEX;
   return guarded(w, [&] { if (w->iso_full) fail(GrB_INSUFFICIENT_SPACE, ISO_MSG);
     GrB_Vector_opaque::Pending p{i, false, {0}}; cast_scalar(w->type->code, p.x, xcode, x);
-    if (!w->host_valid) { if (w->lazy | w->q_reads) vec_resolve(w); if (vec_edit_route(w)) { w->pending.push_back(p); vec_drop_facts(w); return; } vec_to_host(w); }      // it lives in HBM (a deferred chain completed first): queued for the device
+    if (!w->host_valid) { if (w->lazy | w->q_reads) vec_resolve(w); if (vec_edit_route(w)) { w->pending.push_back(p); w->facts.image_replaced(0, false); return; } vec_to_host(w); }      // it lives in HBM (a deferred chain completed first): queued for the device
     w->pending.push_back(p); vec_invalidate_device(w); });
 }
 static GrB_Info vec_get(void* x, int xcode, GrB_Vector v, GrB_Index i) {
@@ -841,7 +838,7 @@ GrB_Info GrBX_Vector_import_Bitmap(GrB_Vector* v, GrB_Type type, GrB_Index n, co
       else GRB_HIP(hipMemsetAsync(w->dpres.p, 1, n, stream()));
     }
     w->dev_valid = true; w->host_valid = false;
-    w->dnvals = n; w->dnvals_known = !present;
+    w->facts.image_replaced(n, !present);
     GRB_HIP(hipStreamSynchronize(stream()));
   });
   if (info) { GrB_Vector_free(&w); return info; }
@@ -866,7 +863,7 @@ GrB_Info GrBX_Vector_device_view(GrB_Vector v, void** values, uint8_t** present,
 GrB_Info GrBX_Vector_device_touch(GrB_Vector v) {
   CHECK_VEC(v);
   return guarded(v, [&] { if (!v->dev_valid) fail(GrB_INVALID_VALUE, "device_touch: vector has no device view");
-    vec_invalidate_host(v); v->dnvals_known = false; });
+    vec_device_extended(v); });      // (the caller wrote through the view: the count is void, the edge bound stays — a stale one can only cost speed)
 }
 
 }  // extern "C"

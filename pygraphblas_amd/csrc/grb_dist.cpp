@@ -177,12 +177,12 @@ GrB_Info GrBX_Vector_allgatherv_start(GrB_Vector full, const GrB_Vector local, c
         if (presence) GRB_HIP(hipMemcpyAsync(full->dpres.as<uint8_t>() + r0, local->dpres.p, r1 - r0, hipMemcpyDeviceToDevice, stream()));
       }
     }
-    vec_invalidate_host(full);
+    vec_device_extended(full);      // (values rewritten in place over the callers' unchanging pattern: the edge bound stays — a stale one can only cost speed)
     // entry count of the gathered vector: all-present without presence bytes.  With them the true count is the sum of the ranks'
     // counts, which nobody needs on the hot path; the vector is marked "not full" (n - 1) instead of "unknown", so that the
     // products that follow neither recount it (a kernel and a host round trip, over slices that may still be in flight) nor skip
     // the presence bytes.  GrBX_Vector_device_touch re-establishes the exact count when a caller wants it.
-    if (presence) { full->dnvals = full->n ? full->n - 1 : 0; full->dnvals_known = true; } else { full->dnvals = full->n; full->dnvals_known = true; }
+    full->facts.dnvals = presence && full->n ? full->n - 1 : full->n; full->facts.dnvals_known = true;
     if (g_world == 1) return;
     if (!g_comm) fail(GrB_INVALID_VALUE, "allgatherv: GrBX_dist_init has not been called");
     ensure_streams();
@@ -255,7 +255,7 @@ GrB_Info GrBX_Vector_allgatherv_bits(GrB_Vector full, const GrB_Vector local, co
                                   full->dpres.as<uint8_t>() + bounds[p]);
     }
     GRB_HIP(hipGetLastError());
-    vec_invalidate_host(full); full->dnvals_known = false; full->fe_lb = 0; full->fe_lb_key = 0;
+    vec_invalidate_host(full);
   });
 }
 

@@ -387,7 +387,7 @@ constexpr uint64_t ASSIGN_DEVICE_MIN_ENTRIES = 30000;            // GrB_Matrix_a
 constexpr uint64_t ASSIGN_ROW_DEVICE_MIN_ENTRIES = 3000000;      // GrB_Row_assign: the host replaces the row's run of tuples in place, cheap up to ~1e6 entries
 constexpr uint64_t ASSIGN_COL_DEVICE_MIN_ENTRIES = 100000;       // GrB_Col_assign: the host's one merge pass
 constexpr uint64_t ASSIGN_VEC_DEVICE_MIN_ENTRIES = 500;          // GrB_Vector_assign: the host route is map-based for every shape (the smallest size measured; the device route won all)
-uint64_t entries_known(GrB_Vector u) { return u->host_valid ? vec_nvals(u) : (u->dnvals_known ? u->dnvals : 0); }      // (no device work for a count)
+uint64_t entries_known(GrB_Vector u) { return u->host_valid ? vec_nvals(u) : (u->facts.dnvals_known ? u->facts.dnvals : 0); }      // (no device work for a count)
 // `operand_entries`: asked only after the variable, the device and the residency of C have not decided
 template <class F> bool assign_on_device(GrB_Matrix C, bool others_capable, uint64_t min_entries, F&& operand_entries) {
   const int env = route_env("GRB_MI355X_ASSIGN");
@@ -466,7 +466,6 @@ bool assign_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB
   vec_to_device(u); vec_to_device(w);
   line_assign(w->type->code, w->n, w->dval.p, w->dpres.as<uint8_t>(), allow, idx, inv, u, accum, dv.replace);
   vec_invalidate_host(w);
-  w->fe_lb = 0; w->fe_lb_key = 0; w->dnvals_known = false; w->dnvals = 0;
   g_last_plan = std::string("assign_vector<index=") + kind_name(idx) + ",accum=" + accum_name(accum) + "> k_assign_vector ";
   return true;
 }
@@ -849,7 +848,7 @@ GrB_Info GxB_Matrix_diag(GrB_Matrix C, const GrB_Vector v, int64_t k, const GrB_
     if (diag_matrix_on_device(C, v)) {
       vec_to_device(v);                                                  // (completes deferred work on v: a lazily filled `v[:] = s` arrives as its bitmap)
       DevCSR T;
-      const bool full = diag_to_csr(v->type->code, v->n, v->dval.p, v->dpres.as<uint8_t>(), k, T, v->dnvals_known && v->dnvals == v->n);
+      const bool full = diag_to_csr(v->type->code, v->n, v->dval.p, v->dpres.as<uint8_t>(), k, T, v->facts.dnvals_known && v->facts.dnvals == v->n);
       g_last_plan = std::string("diag_matrix<k=") + std::to_string(k) + ",full=" + (full ? "1" : "0") + "> k_diag_fill ";
       const DescView dv(nullptr);
       matrix_write_back(C, T, v->type->code, nullptr, dv, nullptr, false);      // C becomes exactly T in C's type: its entries and pending edits are gone, as below

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <memory>
 #include "grb_ops.hpp"
+#include "grb_vecfacts.hpp"
 
 typedef uint64_t GrB_Index;
 
@@ -85,7 +86,7 @@ struct GrbError { int info; std::string msg; };
 uint64_t dev_alloc_serial();      // a number no other allocation of this process gets (the pool hands the same addresses out again)
 struct DevBuf {
   void* p = nullptr; size_t bytes = 0;
-  uint64_t serial = 0;              // identifies this allocation where a raw address could be a recycled one (Vector::fe_lb_key)
+  uint64_t serial = 0;              // identifies this allocation where a raw address could be a recycled one (VecFacts::fe_lb_key)
   bool borrowed = false;            // a view of memory another DevBuf owns (a row of a batch matrix's bitmap handed to a vector kernel, grb_mxm_rows.cpp): never freed here
   DevBuf() {}
   explicit DevBuf(size_t n) { alloc(n); }
@@ -169,11 +170,9 @@ struct GrB_Vector_opaque {
   bool iso_full = false; uint8_t iso_val[16] = {0};   // as for matrices: `Vector.iso(x)` of the default size
   bool dev_valid = false;
   grb::DevBuf dval, dpres;   // T[n], u8[n]
-  uint64_t dnvals = 0; bool dnvals_known = true;   // entry count of the device bitmap, recounted lazily
-  // a lower bound of the edges that leave the vector's entries in one matrix (keyed by its row-pointer buffer), valid while entries are
-  // only added (scalar assign under a mask without replace — the `v[q] = level` of a BFS loop): a masked product whose operand was
-  // already too heavy for a push step needs no recount to stay a pull step.  A stale value can only cost speed, never correctness.
-  uint64_t fe_lb = 0; uint64_t fe_lb_key = 0; bool fe_lb_true = false;   // fe_lb_true: the bound counts the edges of the TRUE entries only (the product's summary), not of every present one      // (key: the serial of the matrix's row-pointer allocation, 0 = none)
+  // everything remembered about the device image beyond its bytes.  The rule (grb_vecfacts.hpp): a fact is valid only for the image it was recorded for, and
+  // every writer of the image passes one of facts.image_dropped() / image_replaced(nvals, known) / image_extended() before it states what it knows of the new one
+  grb::VecFacts facts;
   // ---- non-blocking state (grb_lazy.cpp; the library is initialised GrB_NONBLOCKING by the reference, pygraphblas/__init__.py:251-256) ----
   // lazy == 1: `w(:) = lazy_fill` over every index was requested and nothing has been written yet (no buffers): a product that
   //            accumulates into w with its monoid's operator folds the fill into its own store; anything else materialises it.
@@ -181,23 +180,7 @@ struct GrB_Vector_opaque {
   // q_reads:   queued operations that read this vector's stored value — it must not change before they ran.
   // Every access goes through vec_gate() (vec_to_device / vec_to_host / vec_nvals / the entry points of grb_container.cpp).
   int lazy = 0; uint8_t lazy_fill[16] = {0}; int q_reads = 0;
-  bool holes_zero = false;     // the device values of absent positions are all-zero bits (written so by the element-wise chain kernel)
-  bool holes_big = false; uint8_t holes_big_val[16] = {0};      // ... or all hold this value of the vector's type (the BIG fill of a MIN_PLUS / MAX_PLUS sweep, grb_mxv.cpp; round 4).  Reset wherever holes_zero is.
-  // BOOL vectors: "is any stored value true", recorded by the product kernel that wrote the device buffers `lor_key`
-  // (0 unknown, 1 in the device word of grb_container.cpp's any_true_*, 2 false, 3 true) — `while q.reduce_bool()` of a BFS loop
-  uint8_t lor_state = 0; uint32_t lor_tag = 0; const void* lor_key = nullptr;
-  // an upper bound of |value| over the stored entries, left behind by the "big holes" product that wrote them (grb_mxv.cpp: the next
-  // sweep of a shortest-path loop needs no range kernel and no read-back); < 0 = unknown.  Reset wherever lor_state is.
-  double abs_bound = -1;
-  // the device image's entries as a list, when it has at most 64 of them and the list is known for free (uploaded from a small host mirror;
-  // `v(q) = s` over the entries of such a q): the first level of a BFS then pushes from the list — no frontier compaction (a flag pass,
-  // a scan and a scatter over all n positions), no counting kernel, no read-back.  small_truthy: every listed value is non-zero.
-  // Reset wherever lor_state is.
-  std::vector<uint32_t> small_idx; bool small_valid = false, small_truthy = false;
-  // one CODE byte per position of a one-byte-typed vector (round 6): bit 0 = present, bit 1 = present and its value is not zero — what the masked pull of a BFS
-  // level gathers per neighbour as ONE byte instead of a presence byte and a value byte (grb_spmv_kernels.hpp: k_spmv_rowlane_k<..., CODE>).  Written for free by
-  // the masked scalar assign that precedes the product (`v[q] = level`), else by one pass before the pull.  Reset wherever lor_state is.
-  grb::DevBuf dcode; bool code_valid = false;
+  grb::DevBuf dcode;   // the buffer of the code bytes (facts.code_valid): a buffer, not a fact — kept across the transitions and reused
   uint32_t dev_elem_ops = 0;   // element reads served on the device in a row (grb_container.cpp: after a few dozen the host mirror takes over)
   int sparsity_control = 15;
   std::string err;
@@ -246,7 +229,7 @@ void mat_edit_flush(GrB_Matrix A);
 void vec_edit_flush(GrB_Vector v);
 inline void vec_gate(GrB_Vector v) { if (v->lazy | v->q_reads) vec_resolve(v); if (vec_edits_queued(v)) vec_edit_flush(v); }
 void vec_overwritten(GrB_Vector v);       // v's value is about to be replaced as a whole: deferred work that only produced it is dropped
-uint32_t* any_true_acquire(uint32_t* tag);        // a device word a BOOL product kernel sets to the (fresh, non-zero) tag when it writes a true value (see lor_state)
+uint32_t* any_true_acquire(uint32_t* tag);        // a device word a BOOL product kernel sets to the (fresh, non-zero) tag when it writes a true value (see VecFacts::lor_state)
 void any_true_written(GrB_Vector w_or_null, const void* key, uint32_t tag, uint64_t fe_key = 0, uint32_t fe_nblocks = 0);    // a kernel honoured it; w's device buffers `key` are the result it describes (nullptr: nobody's); fe_key != 0: the kernel also filled the edge summary (counted in the row pointers with that serial)
 bool dist_exchange_pending();                   // grb_dist.cpp: GrBX_Vector_allgatherv_start without its GrBX_dist_wait yet
 // GRB_MI355X_DETERMINISTIC=1: floating-point PLUS results are the same bits in every run (mxm: grb_matrix_ops.cpp; vxm / mxv: no push step, whose atomics land in any order)
@@ -257,8 +240,9 @@ bool nonblocking();                       // GrB_init(GrB_NONBLOCKING) and not G
 void vec_host_assemble(GrB_Vector v);
 void vec_to_host(GrB_Vector v);
 void vec_to_device(GrB_Vector v);
-void vec_invalidate_host(GrB_Vector v);
-void vec_invalidate_device(GrB_Vector v);
+void vec_invalidate_host(GrB_Vector v, uint64_t nvals = 0, bool known = false);   // a kernel replaced the device image (facts.image_replaced): the host mirror goes
+void vec_device_extended(GrB_Vector v);   // ... or only added entries to it (facts.image_extended)
+void vec_invalidate_device(GrB_Vector v); // host was written: the device image goes (facts.image_dropped)
 uint64_t vec_nvals(GrB_Vector v);
 uint64_t vec_dev_nvals(GrB_Vector v);   // entry count of the (valid) device bitmap
 const DevCSR& mat_csc(GrB_Matrix A);      // cached CSR of A^T (device)

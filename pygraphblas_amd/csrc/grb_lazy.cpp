@@ -53,7 +53,7 @@ bool g_q_kept = false;          // the queue as it stands was already run once f
 std::recursive_mutex g_mu;
 uint64_t g_stat_chains = 0, g_stat_nodes = 0, g_stat_fills_folded = 0, g_stat_reduces_fused = 0;
 
-bool is_full(GrB_Vector v) { return v->dnvals_known && v->dnvals == v->n; }
+bool is_full(GrB_Vector v) { return v->facts.dnvals_known && v->facts.dnvals == v->n; }
 
 void release_reads() { for (auto& nd : g_q) for (int k = 0; k < 2; k++) if (nd.in[k]) nd.in[k]->q_reads = 0; }
 
@@ -130,8 +130,8 @@ void run_queue(const ChainReduce* red, void* red_result, bool keep = false) {
     GrB_Vector w = outs[o];
     if (nval[o].p) { w->dval = std::move(nval[o]); w->dpres = std::move(npres[o]); }
     w->lazy = 0; w->dev_valid = true; w->host_valid = false; w->hi.clear(); w->hx.clear(); w->pending.clear();
-    w->dnvals_known = out_full[o]; w->dnvals = out_full[o] ? w->n : 0;
-    w->holes_zero = true; w->holes_big = false; w->fe_lb = 0; w->fe_lb_key = 0; w->lor_state = 0; w->abs_bound = -1; w->small_valid = false; w->code_valid = false;
+    w->facts.image_replaced(w->n, out_full[o]);
+    w->facts.holes_zero = true;      // the chain kernel stores zeros where it stores no entry
   }
   g_q.clear(); g_q_type = -1; g_q_n = 0;
 }
@@ -141,7 +141,7 @@ void materialise_fill(GrB_Vector w) {
   w->lazy = 0;
   w->dval.alloc(n * ts ? n * ts : 1); w->dpres.alloc(n ? n : 1);
   vec_assign_scalar(w->type->code, n, w->dval.p, w->dpres.as<uint8_t>(), nullptr, nullptr, w->lazy_fill, -1, false);
-  w->dev_valid = true; w->host_valid = false; w->dnvals = n; w->dnvals_known = true; w->holes_zero = false; w->holes_big = false; w->lor_state = 0; w->abs_bound = -1; w->small_valid = false; w->code_valid = false;
+  w->dev_valid = true; w->host_valid = false; w->facts.image_replaced(n, true);
 }
 
 }  // namespace
@@ -193,8 +193,8 @@ bool lazy_fill(GrB_Vector w, const void* s_in_w_type) {
   vec_overwritten(w);
   // the buffers go back to the pool: whoever consumes the fill allocates the result
   w->hi.clear(); w->hx.clear(); w->pending.clear(); w->host_valid = false; w->iso_full = false;
-  w->dev_valid = false; w->dval.reset(); w->dpres.reset(); w->dnvals = 0; w->dnvals_known = false; w->fe_lb = 0; w->fe_lb_key = 0; w->holes_zero = false; w->holes_big = false;
-  w->lazy = 1; memcpy(w->lazy_fill, s_in_w_type, 16); w->lor_state = 0; w->abs_bound = -1; w->small_valid = false; w->code_valid = false;
+  w->dev_valid = false; w->dval.reset(); w->dpres.reset(); w->facts.image_replaced(0, false);
+  w->lazy = 1; memcpy(w->lazy_fill, s_in_w_type, 16);
   return true;
 }
 void lazy_fill_consumed(GrB_Vector w) { w->lazy = 0; g_stat_fills_folded++; }
@@ -233,11 +233,11 @@ static bool enqueue(Node nd, GrB_Vector w, int tcode) {
   // the output: what it held is replaced as a whole — unless it is also a stored operand of the queue, its buffers are not needed
   if (w->lazy == 1) w->lazy = 0;
   else if (w->lazy == 2) { for (auto& q : g_q) if (q.out == w) q.out = nullptr; }
-  // (while lazy == 2, dnvals / holes_zero keep describing the STORED value — the queue reads it; nobody else can without passing vec_gate)
+  // (while lazy == 2 and the queue reads w, the count keeps describing the STORED value — run_queue asks whether that operand is full; nobody else can look
+  //  without passing vec_gate, which runs the queue and records the new image's facts)
   if (!w->q_reads) { w->hi.clear(); w->hx.clear(); w->pending.clear(); w->host_valid = false; w->iso_full = false; w->dev_valid = false; w->dval.reset(); w->dpres.reset();
-                     w->dnvals = 0; w->dnvals_known = false; w->holes_zero = false; w->holes_big = false; }
-  else { w->host_valid = false; w->hi.clear(); w->hx.clear(); w->pending.clear(); }
-  w->fe_lb = 0; w->fe_lb_key = 0; w->lor_state = 0; w->abs_bound = -1; w->small_valid = false; w->code_valid = false;
+                     w->facts.image_replaced(0, false); }
+  else { w->host_valid = false; w->hi.clear(); w->hx.clear(); w->pending.clear(); w->facts.image_replaced(w->facts.dnvals, w->facts.dnvals_known); }
   w->lazy = 2;
   nd.out = w;
   g_q.push_back(nd); g_q_type = tcode; g_q_n = n; g_q_kept = false;

@@ -57,7 +57,7 @@ GrB_Vector row_vector(const DevCSR& S, GrB_Type type, uint32_t r, const std::vec
     hipLaunchKernelGGL((k_row_to_bitmap<decltype(TS)::value>), dim3(grid_of(cnt)), dim3(256), 0, stream(), S.col.as<uint32_t>() + b, (const uint8_t*)S.val.p + (size_t)b * ts, cnt,
                        (uint8_t*)v->dval.p, v->dpres.as<uint8_t>());
   });
-  v->dev_valid = true; v->host_valid = false; v->dnvals = cnt; v->dnvals_known = true;
+  v->dev_valid = true; v->host_valid = false; v->facts.image_replaced(cnt, true);
   return v;
 }
 struct VecGuard { std::vector<GrB_Vector> v; ~VecGuard() { for (auto& x : v) if (x) GrB_Vector_free(&x); } };
@@ -212,7 +212,7 @@ template <int TS> __global__ void k_bm_compact(const uint8_t* __restrict__ pres,
 GrB_Vector view_vector(GrB_Type type, uint64_t n, void* val, void* pres, bool known, uint64_t nvals) {
   GrB_Vector v = nullptr; if (GrB_Vector_new(&v, type, n) != GrB_SUCCESS) fail(GrB_OUT_OF_MEMORY, "batch: vector view");
   v->dval.borrow(val, n * type->size); v->dpres.borrow(pres, n);
-  v->dev_valid = true; v->host_valid = false; v->dnvals = nvals; v->dnvals_known = known;
+  v->dev_valid = true; v->host_valid = false; v->facts.image_replaced(nvals, known);
   return v;
 }
 }  // namespace
@@ -276,7 +276,7 @@ void ewise_batch(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryO
   VecGuard g;
   // the output owns C's buffers for the call (the vector write-back may swap them for the result's); the inputs borrow theirs
   GrB_Vector vc = nullptr; if (GrB_Vector_new(&vc, C->type, np) != GrB_SUCCESS) fail(GrB_OUT_OF_MEMORY, "batch: output view"); g.v.push_back(vc);
-  vc->dval = std::move(cb.val); vc->dpres = std::move(cb.pres); vc->dev_valid = true; vc->host_valid = false; vc->dnvals = cb.nvals; vc->dnvals_known = cb.nvals_known;
+  vc->dval = std::move(cb.val); vc->dpres = std::move(cb.pres); vc->dev_valid = true; vc->host_valid = false; vc->facts.image_replaced(cb.nvals, cb.nvals_known);
   cb.valid = false;
   auto view = [&](GrB_Matrix X) -> GrB_Vector {
     if (X == C) return vc;
@@ -292,7 +292,7 @@ void ewise_batch(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryO
   catch (...) { c_left_empty(); throw; }
   if (info != GrB_SUCCESS) { std::string e = vc->err; c_left_empty(); fail(info, "eWise (batch): " + e); }
   if (vc->dval.borrowed || vc->dpres.borrowed || vc->dval.bytes < np * C->type->size || vc->dpres.bytes < np) { c_left_empty(); fail(GrB_PANIC, "eWise (batch): the result does not own its buffers"); }
-  adopt_bitmap(C, std::move(vc->dval), std::move(vc->dpres), vc->dnvals_known, vc->dnvals);
+  adopt_bitmap(C, std::move(vc->dval), std::move(vc->dpres), vc->facts.dnvals_known, vc->facts.dnvals);
   g_last_plan = "ewise_batch<" + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + " as one vector> ";
 }
 
@@ -603,7 +603,7 @@ bool mxm_batch(GrB_Matrix C, GrB_Matrix A, GrB_Matrix Mmask, const DescView& dv,
     vec_to_device(w);
     if (w->dval.p != row_val) GRB_HIP(hipMemcpyAsync(row_val, w->dval.p, nout * zs, hipMemcpyDeviceToDevice, stream()));        // (the write-back did more than adopt T: e.g. an empty product)
     if (w->dpres.p != row_pres) GRB_HIP(hipMemcpyAsync(row_pres, w->dpres.p, nout, hipMemcpyDeviceToDevice, stream()));
-    if (w->dnvals_known) total += w->dnvals; else known = false;
+    if (w->facts.dnvals_known) total += w->facts.dnvals; else known = false;
   }
   g_last_plan = "mxm_batch<" + std::to_string(nr) + " x vxm on bitmap rows> first row: " + plans;
   const bool c_becomes_t = !accum && (!Mmask || dv.replace || mat_nvals(C) == 0) && mat_batch_shape(C->nrows, C->ncols, C->type->code);

@@ -54,7 +54,7 @@ static void off_table_mxv_like(const SemiringRoute& route, GrB_Vector w, GrB_Vec
 
 // The direction of a product (Beamer-style): push walks the rows of the frontier, pull scans the rows of the output.  Push is considered only for a sparse operand
 // and a monoid with a native atomic; it is taken when the edges leaving the frontier (an exact count on the device) are < 1/16 of all entries.  Both operands are
-// resident.  Counts u where that is needed, and records the edge count in u->fe_lb / fe_lb_key.
+// resident.  Counts u where that is needed, and records the edge count in u->facts.fe_lb / fe_lb_key.
 struct Direction { bool push, tiny; uint64_t u_nvals; bool u_full; };      // tiny: pushed from the host's list of <= 64 entries; u_nvals: n - 1 ("has holes") where u was not counted
 static Direction choose_direction(int method, const SemiringDesc& sd, GrB_Matrix A, GrB_Vector u, bool useT) {
   // the entry count of u and (for the direction choice below) the edges leaving it come from one kernel and one round
@@ -65,19 +65,19 @@ static Direction choose_direction(int method, const SemiringDesc& sd, GrB_Matrix
   //  sweeps of the shortest-path loop, whose operand only gains entries; never build a transpose just for this)
   if (method == SPMV_AUTO && spmspv_push_supported(sd) && u->n && (useT || A->csc.valid)) {
     const DevCSR& P0 = useT ? A->csr : mat_csc(A);
-    if (u->fe_lb_key == P0.rowptr.serial && P0.rowptr.serial && u->fe_lb * 16 >= P0.nnz + 16) stays_pull = true;      // no kernel, no host round trip (whether or not the count is known: `w.iseq(v)` of the shortest-path loop counts v)
-    else if (!u->dnvals_known) {
+    if (u->facts.fe_lb_key == P0.rowptr.serial && P0.rowptr.serial && u->facts.fe_lb * 16 >= P0.nnz + 16) stays_pull = true;      // no kernel, no host round trip (whether or not the count is known: `w.iseq(v)` of the shortest-path loop counts v)
+    else if (!u->facts.dnvals_known) {
       uint64_t cnt = 0;
       fe_cached = frontier_edges_and_count(u->dpres.as<uint8_t>(), P0.rowptr.as<uint32_t>(), u->n, &cnt);
-      u->dnvals = cnt; u->dnvals_known = true; u->fe_lb = fe_cached; u->fe_lb_key = P0.rowptr.serial; u->fe_lb_true = false;
+      u->facts.dnvals = cnt; u->facts.dnvals_known = true; u->facts.fe_lb = fe_cached; u->facts.fe_lb_key = P0.rowptr.serial; u->facts.fe_lb_true = false;
     }
   }
-  const uint64_t u_nvals = stays_pull && !u->dnvals_known ? (u->n ? u->n - 1 : 0) : vec_dev_nvals(u);             // (not counted: treated as "has holes")
+  const uint64_t u_nvals = stays_pull && !u->facts.dnvals_known ? (u->n ? u->n - 1 : 0) : vec_dev_nvals(u);             // (not counted: treated as "has holes")
   const bool u_full = u_nvals == u->n;
   bool push = false;
   // an operand of at most 64 entries known as a list on the host (the first level of a BFS): push without counting its edges — 64 rows,
   // the long ones split over all workgroups, are never worth a pull over every row of a large matrix
-  const bool tiny = u->small_valid && u->small_idx.size() == u_nvals && u_nvals <= 64 && (uint64_t)A->csr.nnz >= (1u << 20) && (useT || A->csc.valid);
+  const bool tiny = u->facts.small_valid && u->facts.small_idx.size() == u_nvals && u_nvals <= 64 && (uint64_t)A->csr.nnz >= (1u << 20) && (useT || A->csc.valid);
   if (method == SPMV_PUSH) push = spmspv_push_supported(sd);
   else if (method == SPMV_AUTO && !stays_pull && spmspv_push_supported(sd) && !u_full && u_nvals * 16 < (uint64_t)A->csr.nnz + 16) {
     if (tiny) push = true;
@@ -85,7 +85,7 @@ static Direction choose_direction(int method, const SemiringDesc& sd, GrB_Matrix
       const DevCSR& P = useT ? A->csr : mat_csc(A);
       const uint64_t fe = fe_cached != ~0ull ? fe_cached : frontier_edges(u->dpres.as<uint8_t>(), P.rowptr.as<uint32_t>(), u->n);
       push = fe * 16 < P.nnz + 16;
-      u->fe_lb = fe; u->fe_lb_key = P.rowptr.serial; u->fe_lb_true = false;                       // (exact now, a lower bound while entries are only added)
+      u->facts.fe_lb = fe; u->facts.fe_lb_key = P.rowptr.serial; u->facts.fe_lb_true = false;                       // (exact now, a lower bound while entries are only added)
     }
   }
   return {push, tiny, u_nvals, u_full};
@@ -114,9 +114,9 @@ static BigHoles plan_big_holes(bool eligible, const SemiringDesc& sd, GrB_Matrix
   }
   if (R.range_state != 1) return big;
   bad = 0; cnt = 0;
-  const bool bound_known = u->abs_bound >= 0 && u->lazy == 0 && u->dev_valid;          // left by the previous sweep: no kernel, no read-back
+  const bool bound_known = u->facts.abs_bound >= 0 && u->lazy == 0 && u->dev_valid;          // left by the previous sweep: no kernel, no read-back
   if (!bound_known && !(value_range(sd.zcode, u->n, u->dval.p, u->dpres.as<uint8_t>(), mn, mx, &bad, &cnt) && bad == 0 && cnt)) return big;
-  big.uabs = bound_known ? std::fabs(u->abs_bound) : range_abs_of(sd.zcode, mn, mx); big.aabs = R.range_abs;
+  big.uabs = bound_known ? std::fabs(u->facts.abs_bound) : range_abs_of(sd.zcode, mn, mx); big.aabs = R.range_abs;
   const BigHolesConstants c = big_holes_constants(sd.zcode, sd.addop == B_MIN, big.aabs, big.uabs);
   big.on = c.admitted; memcpy(big.fill, c.fill, 16); memcpy(big.thresh, c.thresh, 16);
   return big;
@@ -173,7 +173,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     // push kernels skip the listed positions themselves and multiply by `true`: no allow bytes, no BOOL copy of the operand (a pass over all positions)
     // (only for `w<!u, replace> = ...` without an accumulator, like the fused pull: with `allow == nullptr` the write-back makes w exactly T, which is
     //  right only when the listed positions are to be deleted anyway and nothing of w's old content survives — ADVICE round 5)
-    excl_small = !fused_mask && push && tiny && !accum && dv.replace && dv.mask_comp && u->small_truthy;
+    excl_small = !fused_mask && push && tiny && !accum && dv.replace && dv.mask_comp && u->facts.small_truthy;
     if (!fused_mask && !excl_small) {
       allow_buf.alloc(mr); ubool.alloc(mr + 1);
       build_allow_and_bool(mr, u->type->code, u->dval.p, u->dpres.as<uint8_t>(), dv.mask_struct, dv.mask_comp, allow_buf.as<uint8_t>(), ubool.as<uint8_t>());
@@ -193,7 +193,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
   // bitmap variant of the row-block kernel: 0.60 -> 0.17 ms at R-MAT-22).
   // w is full: resident in HBM with every position present, or `w(:) = s` was requested and not written yet (non-blocking mode, grb_lazy.cpp)
   const bool w_fill = w->lazy == 1 && w != u && w != mask;
-  const bool w_full = w_fill || (w->lazy == 0 && w->dev_valid && !w->host_valid && w->dnvals_known && w->dnvals == w->n && w != u);
+  const bool w_full = w_fill || (w->lazy == 0 && w->dev_valid && !w->host_valid && w->facts.dnvals_known && w->facts.dnvals == w->n && w != u);
   const bool accum_is_monoid = !mask && accum && check_obj(accum) && accum->opcode == sd.addop && accum->xtype->code == sd.zcode && accum->ytype->code == sd.zcode &&
                                accum->ztype->code == sd.zcode && w->type->code == sd.zcode;
   bool fill_holes = false;
@@ -206,7 +206,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
   const BigHoles big = plan_big_holes(!push && !u_full && !fill_holes && !allow && method == SPMV_AUTO, sd, A, u, useT, u_nvals);
   const void* uval = nullptr;
   const bool zero_fill = [&] { for (size_t b = 0; b < zs; b++) if (sd.identity[b]) return false; return true; }();
-  if (uses_u && fill_holes && u->holes_zero && u->type->code == sd.zcode && zero_fill) {
+  if (uses_u && fill_holes && u->facts.holes_zero && u->type->code == sd.zcode && zero_fill) {
     uval = u->dval.p;                                     // written by the element-wise chain kernel with zeros in the holes: no pass at all
   } else if (big.on) {
     // the fill goes into u's OWN buffer (the values of absent positions are nobody's business: holes_zero is dropped) and is remembered: the
@@ -214,14 +214,14 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     // is ready as it stands (a cast-and-fill pass over the vector per sweep before: 18 us of 357 at R-MAT-22)
     // (the operand is an INPUT: its stored entries never change, only the bytes behind its holes do — a write all the same.  Not while queued work
     //  still reads the vector, nor while an exchange writes into vector buffers on the second stream: then the fill goes into a copy, as before round 4)
-    if (u->holes_big && memcmp(u->holes_big_val, big.fill, zs) == 0) uval = u->dval.p;
+    if (u->facts.holes_big && memcmp(u->facts.holes_big_val, big.fill, zs) == 0) uval = u->dval.p;
     else if (u->q_reads || dist_exchange_pending()) {
       ucast.alloc(u->n * zs + 1);
       vec_cast_fill_values(sd.zcode, ucast.p, u->type->code, u->dval.p, u->dpres.as<uint8_t>(), u->n, big.fill);
       uval = ucast.p;
     } else {
       vec_cast_fill_values(sd.zcode, u->dval.p, u->type->code, u->dval.p, u->dpres.as<uint8_t>(), u->n, big.fill);      // (same type: plan_big_holes requires it; element-wise, in place)
-      u->holes_zero = false; u->holes_big = true; memcpy(u->holes_big_val, big.fill, 16);
+      u->facts.holes_hold(big.fill);
       uval = u->dval.p;
     }
   } else if (uses_u && fill_holes) {
@@ -251,7 +251,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     // push walks rows of M^T:  M^T = useT ? A : A^T
     DevCSR& P = useT ? A->csr : const_cast<DevCSR&>(mat_csc(A));
     call.M = &P; call.upres = u->dpres.as<uint8_t>();
-    if (u->small_valid && u->small_idx.size() == u_nvals) { call.small_idx = u->small_idx.data(); call.small_n = (uint32_t)u_nvals; call.excl_small = excl_small; }
+    if (u->facts.small_valid && u->facts.small_idx.size() == u_nvals) { call.small_idx = u->facts.small_idx.data(); call.small_n = (uint32_t)u_nvals; call.excl_small = excl_small; }
     call.aval = uses_a ? cast_values(sd.zcode, A->type->code, P.val.p, P.nnz, acast) : nullptr;
     spmspv_push(call, sd, u_nvals);
   } else {
@@ -263,10 +263,10 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
       // over the vector when the matrix is large enough for the pull to repay it (GRB_MI355X_CODE_BYTES=0: never)
       const char* ce = getenv("GRB_MI355X_CODE_BYTES"); const bool code_off = ce && atoi(ce) == 0;      // (read per call: a test hook)
       if (!code_off && u->n >= (1u << 16) && R.nnz >= (1u << 20)) {
-        if (!u->code_valid) {
+        if (!u->facts.code_valid) {
           if (!u->dcode.p || u->dcode.bytes < u->n + 16) u->dcode.alloc(u->n + 16);
           vec_code_bytes(u->n, u->dval.as<uint8_t>(), u->dpres.as<uint8_t>(), u->dcode.as<uint8_t>());
-          u->code_valid = true;
+          u->facts.code_valid = true;
         }
         call.fm_code = u->dcode.as<uint8_t>();
       }
@@ -289,12 +289,10 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     }
     spmv_pull(call, sd);
     if (epi_done && call.epi == 3) {
-      const bool keep_big = w == u && u->holes_big;                       // (the store wrote real values into former holes, nothing else: the others still hold the fill)
-      vec_invalidate_host(w);
-      w->holes_big = keep_big;
-      w->dnvals_known = false; w->dnvals = 0; w->holes_zero = false;      // (entries were only added: the lower bound fe_lb of the edges leaving them stays valid — the next sweep needs no count)
-      w->abs_bound = big.uabs + big.aabs;       // every sum that passed the threshold is within |u| + |A|; MIN / MAX select among such values and w's own (w is u, or held values of an earlier sweep)
-      if (w != u) w->abs_bound = -1;
+      const bool keep_big = w == u && u->facts.holes_big; uint8_t held[16]; memcpy(held, u->facts.holes_big_val, 16);
+      vec_device_extended(w);                       // (entries were only added: the lower bound fe_lb of the edges leaving them stays valid — the next sweep needs no count)
+      if (keep_big) w->facts.holes_hold(held);      // (the store wrote real values into former holes, nothing else: the others still hold the fill)
+      if (w == u) w->facts.abs_bound = big.uabs + big.aabs;       // every sum that passed the threshold is within |u| + |A|; MIN / MAX select among such values and w's own
       return;
     }
     if (epi_done) {
@@ -302,20 +300,20 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
         lazy_fill_consumed(w);
         w->dval = std::move(tval); w->dpres = std::move(tpres);
         w->dev_valid = true; w->host_valid = false; w->hi.clear(); w->hx.clear(); w->pending.clear();
-      } else vec_invalidate_host(w);
-      w->dnvals = w->n; w->dnvals_known = true; w->fe_lb = 0; w->fe_lb_key = 0; w->holes_zero = false; w->holes_big = false;
+        w->facts.image_replaced(w->n, true);
+      } else vec_invalidate_host(w, w->n, true);
       return;
     }
   }
   if (big.on) big_to_absent(sd.zcode, mr, tval.p, tpres.as<uint8_t>(), big.thresh, sd.addop == B_MIN);       // sums made of fill values only are no entries
-  const bool w_is_u = w == u; const bool w_was_empty = !w_is_u && w->lazy == 0 && w->dnvals_known && w->dnvals == 0 && !w->host_valid;
+  const bool w_is_u = w == u; const bool w_was_empty = !w_is_u && w->lazy == 0 && w->facts.dnvals_known && w->facts.dnvals == 0 && !w->host_valid;
   vector_write_back(w, sd.zcode, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/true);
   // every sum that survived the threshold is within |u| + |A|: the bound of the result when w held nothing else (w was empty / is
   // replaced as a whole), or when w is u itself and the accumulator SELECTS one of its arguments (`v<accum MIN> = v MIN_PLUS A`: MIN,
   // MAX, FIRST, SECOND, ANY).  An arithmetic accumulator (PLUS, TIMES ...) can leave |w| beyond it: then no bound is recorded and the
   // next sweep measures the range again.
   const bool accum_selects = accum && check_obj(accum) && (accum->opcode == B_MIN || accum->opcode == B_MAX || accum->opcode == B_FIRST || accum->opcode == B_SECOND || accum->opcode == B_ANY);
-  if (big.on && w->type->code == sd.zcode && (!accum || w_was_empty || (w_is_u && accum_selects))) w->abs_bound = big.uabs + big.aabs;
+  if (big.on && w->type->code == sd.zcode && (!accum || w_was_empty || (w_is_u && accum_selects))) w->facts.abs_bound = big.uabs + big.aabs;
   if (any_done) any_true_written(w->lazy == 0 && w->dev_valid && w->dval.p == tkey ? w : nullptr, tkey, call.any_true_tag, fe_done ? fe_key : 0, fe_nblocks);       // (adopted as they are: w is exactly T)
 }
 

@@ -206,20 +206,18 @@ inline bool vector_prelude(GrB_Vector w, GrB_Vector mask, const DescView& dv, ui
 inline void vector_write_back(GrB_Vector w, int tcode, DevBuf& tval, DevBuf& tpres, const uint8_t* allow, GrB_BinaryOp accum,
                               bool replace, bool t_only_allowed, uint64_t t_nvals = ~0ull) {
   const uint64_t n = w->n; const int wcode = w->type->code;
-  w->fe_lb = 0; w->fe_lb_key = 0;                       // entries may disappear: the bound of grb_mxv.cpp's direction choice is void
-  const bool w_empty = w->lazy ? false : (w->host_valid ? (vec_nvals(w) == 0) : (w->dnvals_known && w->dnvals == 0));   // (deferred work pending on w: not known, and not worth completing for this)
+  const bool w_empty = w->lazy ? false : (w->host_valid ? (vec_nvals(w) == 0) : (w->facts.dnvals_known && w->facts.dnvals == 0));   // (deferred work pending on w: not known, and not worth completing for this)
   if (accum) check_binop(accum, "accum");
   if (!accum && (!allow || (t_only_allowed && (replace || w_empty)))) {
     // w becomes exactly T: adopt the buffers (typecast the values if the output type differs)
     if (tcode != wcode) { DevBuf c(n * w->type->size + 1); vec_cast_values(wcode, c.p, tcode, tval.p, n); tval = std::move(c); }
-    vec_invalidate_host(w);
+    vec_invalidate_host(w, t_nvals, t_nvals != ~0ull);
     w->dval = std::move(tval); w->dpres = std::move(tpres); w->dev_valid = true;
-    w->dnvals_known = t_nvals != ~0ull; w->dnvals = w->dnvals_known ? t_nvals : 0;
     return;
   }
   vec_to_device(w);
   // no mask + accum: the result is the union of w and T — still full when w or T was
-  const bool stays_full = !allow && accum && ((w->dnvals_known && w->dnvals == n) || t_nvals == n);
+  const bool stays_full = !allow && accum && ((w->facts.dnvals_known && w->facts.dnvals == n) || t_nvals == n);
   // the epilogue runs in the accumulator's domain (or w's type without one)
   const int ecode = accum ? accum->xtype->code : wcode;
   DevBuf tc, wc;
@@ -228,8 +226,7 @@ inline void vector_write_back(GrB_Vector w, int tcode, DevBuf& tval, DevBuf& tpr
   if (ecode != wcode) { wc.alloc(n * type_size(ecode) + 1); vec_cast_values(ecode, wc.p, wcode, w->dval.p, n); wv = wc.p; }
   vec_epilogue(ecode, n, wv, w->dpres.as<uint8_t>(), tv, tpres.as<uint8_t>(), allow, accum ? accum->opcode : -1, replace);
   if (ecode != wcode) vec_cast_values(wcode, w->dval.p, ecode, wv, n);
-  vec_invalidate_host(w);
-  w->dnvals_known = stays_full; w->dnvals = stays_full ? n : 0;   // (temporaries return to the pool; reuse is stream-ordered)
+  vec_invalidate_host(w, n, stays_full);   // (entries may disappear: the edge bound goes too; temporaries return to the pool, reuse is stream-ordered)
 }
 
 }  // namespace grb

@@ -71,7 +71,7 @@ static GrB_Info vec_reduce(void* c, int ccode, GrB_BinaryOp accum, GrB_Monoid mo
         scalar_accum(c, ccode, r, mc, accum); return;
       }
     }
-    if (u->lor_state && u->type->code == T_BOOL && check_obj(monoid) && check_obj(monoid->op) && monoid->op->opcode == B_LOR && monoid->op->ztype->code == T_BOOL) {
+    if (u->facts.lor_state && u->type->code == T_BOOL && check_obj(monoid) && check_obj(monoid->op) && monoid->op->opcode == B_LOR && monoid->op->ztype->code == T_BOOL) {
       bool any = false;                                  // the kernel that produced u already noted it (grb_mxv.cpp)
       if (any_true_lookup(u, &any)) { const uint8_t r = any ? 1 : 0; scalar_accum(c, ccode, &r, T_BOOL, accum); return; }
     }
@@ -109,11 +109,11 @@ static void vec_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const 
       // when both the mask's and w's entries are known as short lists (the first level of a BFS: `v[q] = 1` with q = {start}), so are
       // the result's: w's entries and the positions the mask allows
       std::vector<uint32_t> merged; bool keep_list = false, truthy = false;
-      if (!accum && !dv.replace && !dv.mask_comp && w->small_valid && mask->small_valid && (dv.mask_struct || mask->small_truthy)) {
-        merged.resize(w->small_idx.size() + mask->small_idx.size());
-        merged.resize(std::set_union(w->small_idx.begin(), w->small_idx.end(), mask->small_idx.begin(), mask->small_idx.end(), merged.begin()) - merged.begin());
+      if (!accum && !dv.replace && !dv.mask_comp && w->facts.small_valid && mask->facts.small_valid && (dv.mask_struct || mask->facts.small_truthy)) {
+        merged.resize(w->facts.small_idx.size() + mask->facts.small_idx.size());
+        merged.resize(std::set_union(w->facts.small_idx.begin(), w->facts.small_idx.end(), mask->facts.small_idx.begin(), mask->facts.small_idx.end(), merged.begin()) - merged.begin());
         bool snz = false; for (size_t b = 0; b < type_size(wcode0); b++) snz = snz || s0[b] != 0;
-        keep_list = merged.size() <= 64; truthy = snz && (w->small_truthy || w->small_idx.empty());
+        keep_list = merged.size() <= 64; truthy = snz && (w->facts.small_truthy || w->facts.small_idx.empty());
       }
       // (Round 5, measured and dropped: recording this assign and letting the masked pull that follows apply it on its way over the rows — one launch and
       //  one dependent kernel less per BFS level.  The pull then looks at q beside v wherever it gathers an operand entry: +2 byte gathers per entry
@@ -123,15 +123,13 @@ static void vec_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const 
       if (type_size(wcode0) == 1 && n >= (1u << 16)) { if (!w->dcode.p || w->dcode.bytes < n + 16) w->dcode.alloc(n + 16); code_out = w->dcode.as<uint8_t>(); }
       const bool coded = vec_assign_scalar_masked(wcode0, n, w->dval.p, w->dpres.as<uint8_t>(), mask->type->code, mask->dval.p, mask->dpres.as<uint8_t>(), dv.mask_struct, dv.mask_comp, s0,
                                accum ? accum->opcode : -1, dv.replace, code_out);
-      vec_invalidate_host(w);
-      w->code_valid = coded;
-      if (dv.replace) { w->fe_lb = 0; w->fe_lb_key = 0; }
+      if (dv.replace) vec_invalidate_host(w); else vec_device_extended(w);      // (without replace a scalar assign only adds entries: the edge bound stays)
+      w->facts.code_valid = coded;
       // the positions the mask allows are entries of w now: when the mask carries a bound of the edges leaving its TRUE entries (left by the
       // product that made it, any_true_lookup), w's entries include them — `v[q] = level`: the next product's direction choice needs no count
       // (a bound that counts every PRESENT entry of the mask says nothing about the positions a valued mask allows: ADVICE round 5)
-      if (!dv.mask_comp && !dv.replace && (dv.mask_struct || mask->fe_lb_true) && mask->fe_lb_key && mask->fe_lb && mask->lazy == 0 && (w->fe_lb_key != mask->fe_lb_key || w->fe_lb < mask->fe_lb)) { w->fe_lb = mask->fe_lb; w->fe_lb_key = mask->fe_lb_key; w->fe_lb_true = false; }
-      w->dnvals_known = false; w->dnvals = 0;
-      if (keep_list) { w->small_idx.swap(merged); w->small_valid = true; w->small_truthy = truthy; w->dnvals = w->small_idx.size(); w->dnvals_known = true; }
+      if (!dv.mask_comp && !dv.replace && (dv.mask_struct || mask->facts.fe_lb_true) && mask->facts.fe_lb_key && mask->facts.fe_lb && mask->lazy == 0 && (w->facts.fe_lb_key != mask->facts.fe_lb_key || w->facts.fe_lb < mask->facts.fe_lb)) { w->facts.fe_lb = mask->facts.fe_lb; w->facts.fe_lb_key = mask->facts.fe_lb_key; w->facts.fe_lb_true = false; }
+      if (keep_list) { w->facts.small_idx.swap(merged); w->facts.small_valid = true; w->facts.small_truthy = truthy; w->facts.dnvals = w->facts.small_idx.size(); w->facts.dnvals_known = true; }
       return;
     }
   }
@@ -161,9 +159,9 @@ static void vec_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const 
     vec_assign_scalar(ecode, n, wc.p, w->dpres.as<uint8_t>(), allow, reg, s, accum->opcode, dv.replace);
     vec_cast_values(wcode, w->dval.p, ecode, wc.p, n);
   }
-  vec_invalidate_host(w);
-  if (dv.replace) { w->fe_lb = 0; w->fe_lb_key = 0; }                      // (without replace a scalar assign only adds entries: the bound stays)
-  w->dnvals_known = !allow && !reg; w->dnvals = w->dnvals_known ? n : 0;       // every index, no mask: the vector is full now
+  const bool full = !allow && !reg;                                       // every index, no mask: the vector is full now
+  if (dv.replace) vec_invalidate_host(w, n, full);
+  else { vec_device_extended(w); w->facts.dnvals = full ? n : 0; w->facts.dnvals_known = full; }      // (without replace a scalar assign only adds entries: the edge bound stays)
 }
 
 // eWiseAdd / eWiseMult.  A user-defined operator (grb_userop.cpp) runs on bitmap vectors in HBM only and is never queued: deferred work is completed first, then
@@ -199,15 +197,13 @@ static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_
     if (!off && same && (mask || accum) && n) {
       if (accum) check_binop(accum, "accum");
       vec_to_device(u); vec_to_device(v); if (mask) vec_to_device(mask); vec_to_device(w);
-      const bool uf = u->dnvals_known && u->dnvals == n, vf = v->dnvals_known && v->dnvals == n, wf = w->dnvals_known && w->dnvals == n;
+      const bool uf = u->facts.dnvals_known && u->facts.dnvals == n, vf = v->facts.dnvals_known && v->facts.dnvals == n, wf = w->facts.dnvals_known && w->facts.dnvals == n;
       const bool t_full = is_union ? (uf || vf) : (uf && vf);
       const bool stays_full = !mask && accum && (wf || t_full);
       vec_ewise_fused(wc, n, u->dval.p, u->dpres.as<uint8_t>(), v->dval.p, v->dpres.as<uint8_t>(), op->opcode, is_union,
                       mask ? mask->type->code : 0, mask ? mask->dval.p : nullptr, mask ? mask->dpres.as<uint8_t>() : nullptr, dv.mask_struct, dv.mask_comp,
                       accum ? accum->opcode : -1, dv.replace, w->dval.p, w->dpres.as<uint8_t>());
-      vec_invalidate_host(w);
-      w->fe_lb = 0; w->fe_lb_key = 0;
-      w->dnvals_known = stays_full; w->dnvals = stays_full ? n : 0;
+      vec_invalidate_host(w, n, stays_full);
       return;
     }
   }
@@ -220,7 +216,7 @@ static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_
   if (user) userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), nullptr, nullptr, tval.p, tpres.as<uint8_t>());
   else vec_ewise(xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), op->opcode, is_union, tval.p, tpres.as<uint8_t>());
   // a comparison yields 0/1 in the operand type: identical to BOOL after the typecast into w
-  const bool uf = u->dnvals_known && u->dnvals == n, vf = v->dnvals_known && v->dnvals == n;
+  const bool uf = u->facts.dnvals_known && u->facts.dnvals == n, vf = v->facts.dnvals_known && v->facts.dnvals == n;
   const uint64_t tn = (is_union ? (uf || vf) : (uf && vf)) ? n : ~0ull;          // a full operand makes the union full, two make the intersection full
   vector_write_back(w, xc, tval, tpres, allow, accum, dv.replace, /*t_only_allowed=*/false, tn);
 }
@@ -244,7 +240,7 @@ static void vec_apply_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, cons
   DevBuf uc, tval(n * type_size(op.xcode) + 16), tpres(n + 16);
   const void* uv = cast_values(op.xcode, u->type->code, u->dval.p, n, uc);
   elem_eval(op, n, uv, u->dpres.as<uint8_t>(), s, tval.p, tpres.as<uint8_t>());
-  vector_write_back(w, op.xcode, tval, tpres, allow, accum, dv.replace, false, u->dnvals_known ? u->dnvals : ~0ull);     // apply keeps the pattern
+  vector_write_back(w, op.xcode, tval, tpres, allow, accum, dv.replace, false, u->facts.dnvals_known ? u->facts.dnvals : ~0ull);     // apply keeps the pattern
 }
 
 // positional unary operators on a vector (an n x 1 column): the pattern of u, the values are the index (which 0 / 1: + 1) or the column 0 (2 / 3: + 1)
@@ -258,7 +254,7 @@ static void vec_position_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, i
   DevBuf tval(n * type_size(zcode) + 1), tpres(n + 1);
   vec_position_values(zcode, n, which, tval.p);
   if (n) GRB_HIP(hipMemcpyAsync(tpres.p, u->dpres.p, n, hipMemcpyDeviceToDevice, stream()));
-  vector_write_back(w, zcode, tval, tpres, allow, accum, dv.replace, false, u->dnvals_known ? u->dnvals : ~0ull);
+  vector_write_back(w, zcode, tval, tpres, allow, accum, dv.replace, false, u->facts.dnvals_known ? u->facts.dnvals : ~0ull);
 }
 
 // select: T is u with the presence bytes the operator keeps.  A built-in operator makes them from the positions (an n x 1 column: entry (i, 0)) or from the
@@ -328,7 +324,7 @@ GrB_Info GrBX_Vector_iseq(bool* equal, const GrB_Vector u, const GrB_Vector v) {
   if (u == v) { *equal = true; return GrB_SUCCESS; }
   return guarded(const_cast<GrB_Vector>(u), [&] {
     vec_to_device(const_cast<GrB_Vector>(u)); vec_to_device(const_cast<GrB_Vector>(v));
-    if (u->dnvals_known && v->dnvals_known && u->dnvals != v->dnvals) { *equal = false; return; }
+    if (u->facts.dnvals_known && v->facts.dnvals_known && u->facts.dnvals != v->facts.dnvals) { *equal = false; return; }
     *equal = vec_iseq_mismatches(u->type->code, u->n, u->dval.p, u->dpres.as<uint8_t>(), v->dval.p, v->dpres.as<uint8_t>()) == 0;
   });
 }
