@@ -106,11 +106,12 @@ void check_mat(GrB_Matrix A, const char* what) { if (!check_obj(A)) fail(GrB_UNI
 void check_mxm_operands(GrB_Matrix M, GrB_Matrix A, GrB_Matrix B) { check_mat(A, "mxm"); check_mat(B, "mxm"); if (M) check_mat(M, "mxm"); }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// A semiring that does not run through SemiringDesc — user-defined or positional (SemiringRoute, grb_opcommon.hpp) — in two steps, one driver for both.  The
+// A semiring that does not run through SemiringDesc — user-defined, positional or comparison (SemiringRoute, grb_opcommon.hpp) — in two steps, one driver for all three.  The
 // pattern of T is the pattern of the ANY_PAIR product of the operands' patterns: the built-in routes with a BOOL ANY_PAIR semiring and no values — spgemm_masked
 // under a plain mask (its rows are the mask's, in column order), spgemm_hash otherwise (a segmented sort, or the dense path's ordered walk, leaves every row in
 // column order).  The route's kernel then fills the values (a user-defined semiring: every entry the left-to-right sum of its products in ascending k, over operand
-// values cast into T's type; a positional one: the coordinates' monoid, no operand value read or cast).  What is refused before a device is asked for was refused by
+// values cast into T's type; a positional one: the coordinates' monoid, no operand value read or cast; a comparison one: the BOOL monoid over the comparisons of
+// operand values cast into the multiplier's argument type, one byte per entry).  What is refused before a device is asked for was refused by
 // the caller; a user-defined semiring's layout refusal comes here, then the accumulator is looked at BEFORE the dimensions; never queued; none of the batch /
 // few-rows routes.  The write-back is the built-in semirings' own.  A call that may write nothing (no mask + the complement flag) leaves the plan string empty.
 void off_table_mxm(const SemiringRoute& route, GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
@@ -147,10 +148,10 @@ void off_table_mxm(const SemiringRoute& route, GrB_Matrix C, GrB_Matrix M, GrB_B
 
 void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
   const SemiringRoute route = semiring_route(semiring);
-  if (route.kind == SR_POSITIONAL) {      // (its layout refusal needs initialised operands, and comes before a device is asked for)
+  if (route.refuses_layout_by_name()) {      // (its layout refusal needs initialised operands, and comes before a device is asked for)
     check_mxm_operands(M, A, B);
     const NoLayout nl = no_layout(C, M, A, B);
-    route.refuse_before_device(&nl);
+    route.refuse_before_device(&nl, accum);
   } else route.refuse_before_device(nullptr);
   need_device();
   if (route.off_table()) { off_table_mxm(route, C, M, accum, A, B, desc); return; }

@@ -23,11 +23,11 @@ static int g_force_method = SPMV_AUTO;   // test hook: GRB_MI355X_SPMV=adaptive|
 // ns x (n values + n bytes) copies per product of the first bitmap version (3.8 of 14 ms of the BC driver at R-MAT-22) are gone.  One-shot: cleared by the call.
 namespace grb { thread_local void* g_mxv_dest_val = nullptr; thread_local uint8_t* g_mxv_dest_pres = nullptr; }
 
-// A semiring that does not run through SemiringDesc — user-defined or positional (SemiringRoute, grb_opcommon.hpp): one driver for both.  What is refused before
+// A semiring that does not run through SemiringDesc — user-defined, positional or comparison (SemiringRoute, grb_opcommon.hpp): one driver for all three.  What is refused before
 // a device is asked for was refused by the caller; a user-defined semiring's layout refusal comes here, then the accumulator is looked at BEFORE the dimensions;
 // the call is never queued and completes deferred work first.  T — unmasked, or under the allow bytes of any mask form — comes from the route's row kernel over
-// the CSR of the orientation the built-in product pulls over (the cached transpose for vxm / GrB_INP0); operand values are cast into T's type where the route
-// reads them at all, and the argument order of the multiplier is the kernel's kind, not a flag.  The write-back is the built-in semirings' own.  A call that may
+// the CSR of the orientation the built-in product pulls over (the cached transpose for vxm / GrB_INP0); operand values are cast into T's type (a comparison semiring: its multiplier's argument
+// type) where the route reads them at all, and the argument order of the multiplier is the kernel's kind, not a flag.  The write-back is the built-in semirings' own.  A call that may
 // write nothing (no mask + the complement flag) leaves the plan string empty.
 static void off_table_mxv_like(const SemiringRoute& route, GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Matrix A, GrB_Vector u, GrB_Descriptor desc, bool is_vxm) {
   route.refuse_after_device(no_layout(A, w, u, mask), "dimension or size");
@@ -128,7 +128,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
   const bool initialised = check_obj(w) && check_obj(A) && check_obj(u) && (!mask || check_obj(mask));
   if (route.off_table()) {
     const NoLayout nl = initialised ? no_layout(A, w, u, mask) : NoLayout{};
-    route.refuse_before_device(initialised ? &nl : nullptr);
+    route.refuse_before_device(initialised ? &nl : nullptr, accum);
   }
   need_device();
   if (!initialised) fail(GrB_UNINITIALIZED_OBJECT, "mxv/vxm: uninitialised operand");

@@ -7,6 +7,7 @@
 #include "grb_semiring.hpp"
 #include "grb_userop.hpp"
 #include "grb_possr.hpp"
+#include "grb_cmpsr.hpp"
 #include "grb_lazy.hpp"
 #include <initializer_list>
 #include <vector>
@@ -129,26 +130,37 @@ inline void no_layout_of(NoLayout& f, const GrB_Vector_opaque* v) { if (v) { f.h
 template <class... C> NoLayout no_layout(const C*... containers) { NoLayout f; (no_layout_of(f, containers), ...); return f; }
 
 // ---- a semiring that does not run through SemiringDesc ----------------------------------------------------------------------------------------------------
-// Made once at the top of a product call (semiring_route).  A built-in semiring goes through make_semiring_desc and the SpMV / SpGEMM kernels.  The two off-table
-// kinds — user-defined (GrBX_Semiring_new_user, grb_userop.hpp) and positional (grb_possr.hpp) — share ONE driver per product (off_table_mxv_like in grb_mxv.cpp,
+// Made once at the top of a product call (semiring_route).  A built-in semiring goes through make_semiring_desc and the SpMV / SpGEMM kernels.  The three off-table
+// kinds — user-defined (GrBX_Semiring_new_user, grb_userop.hpp), positional (grb_possr.hpp) and comparison (a built-in semiring whose multiplier is GrB_<cmp>_<T>
+// over a non-Boolean T, grb_cmpsr.hpp) — share ONE driver per product (off_table_mxv_like in grb_mxv.cpp,
 // off_table_mxm in grb_matrix_ops.cpp): T comes from a small row kernel (mxv / vxm) or "pattern first, values second" (mxm), then the built-in write-back runs;
-// such a call is never queued and completes deferred work first, and its accumulator is looked at before the dimensions.  Where the two differ is answered here.
-// `product`: 0 mxv, 1 vxm, 2 mxm — the numbers of USK_* and of PK_*.
-enum SemiringKind { SR_BUILTIN = 0, SR_USER, SR_POSITIONAL };
+// such a call is never queued and completes deferred work first, and its accumulator is looked at before the dimensions.  Where the three differ is answered here.
+// `product`: 0 mxv, 1 vxm, 2 mxm — the numbers of USK_*, of PK_* and of CK_*.
+enum SemiringKind { SR_BUILTIN = 0, SR_USER, SR_POSITIONAL, SR_COMPARE };
 static_assert((int)USK_MXV == (int)PK_MXV && (int)USK_VXM == (int)PK_VXM && (int)USK_MXM == (int)PK_MXM, "one numbering of the products");
+static_assert((int)CK_MXV == (int)PK_MXV && (int)CK_VXM == (int)PK_VXM && (int)CK_MXM == (int)PK_MXM, "one numbering of the products");
 struct SemiringRoute {
   int kind; GrB_Semiring s;
   bool off_table() const { return kind != SR_BUILTIN; }
-  int zcode() const { return s->add->op->ztype->code; }      // the type of T
-  // operand values as the kernels take them: cast into T's type (user-defined), or none at all (a positional semiring reads no value)
-  const void* operand_values(int code, const void* val, uint64_t n, DevBuf& tmp) const { return kind == SR_USER ? cast_values(zcode(), code, val, n, tmp) : nullptr; }
-  // the head of the plan string: "usersr<add=...,mul=...,type=...,kind=...> " / "possr<...> "
-  std::string plan(int product) const { return kind == SR_USER ? usersr_plan(product, s->add->op, s->mul) : possr_plan(product, s); }
+  int zcode() const { return s->add->op->ztype->code; }      // the type of T (a comparison semiring: BOOL, its monoid's)
+  int xcode() const { return s->mul->xtype->code; }          // the type a comparison semiring compares in
+  // operand values as the kernels take them: cast into T's type (user-defined) or into the multiplier's argument type (comparison), or none at all (a positional
+  // semiring reads no value)
+  const void* operand_values(int code, const void* val, uint64_t n, DevBuf& tmp) const {
+    return kind == SR_USER ? cast_values(zcode(), code, val, n, tmp) : kind == SR_COMPARE ? cast_values(xcode(), code, val, n, tmp) : nullptr;
+  }
+  // the head of the plan string: "usersr<add=...,mul=...,type=...,kind=...> " / "possr<...> " / "cmpsr<...> "
+  std::string plan(int product) const { return kind == SR_USER ? usersr_plan(product, s->add->op, s->mul) : kind == SR_COMPARE ? cmpsr_plan(product, s) : possr_plan(product, s); }
+  // its layout refusal names the semiring and needs initialised operands: the callers hand refuse_before_device their NoLayout
+  bool refuses_layout_by_name() const { return kind == SR_POSITIONAL || kind == SR_COMPARE; }
   // Refused before a device is asked for: operators the compiled route cannot run (user-defined); containers without an HBM layout, naming the semiring
-  // (positional — `nl`: nullptr while an operand is not initialised, which is an error of its own).
-  void refuse_before_device(const NoLayout* nl) const {
+  // (positional, comparison — `nl`: nullptr while an operand is not initialised, which is an error of its own) and, for a comparison semiring, a user-defined
+  // accumulator (refused by check_binop as everywhere else; `accum` may be nullptr).
+  void refuse_before_device(const NoLayout* nl, GrB_BinaryOp accum = nullptr) const {
     if (kind == SR_USER) usersr_check(s->add->op, s->mul);
     if (kind == SR_POSITIONAL && nl) possr_needs_layout(s, nl->hyper, nl->cplx);
+    if (kind == SR_COMPARE && nl) cmpsr_needs_layout(s, nl->hyper, nl->cplx);
+    if (kind == SR_COMPARE && accum && check_obj(accum) && is_user(accum)) check_binop(accum, "accum");
   }
   // ... and after it, once the operands are known to be initialised: containers without an HBM layout, naming the operator (user-defined; `extent`: "dimension" of
   // a matrix, "dimension or size" where vectors take part)
@@ -158,11 +170,13 @@ struct SemiringRoute {
   // mxv / vxm: t(r) for every allowed row of R (usersr_rows / possr_rows); the plan string ends up as plan(product) + the kernel's name
   void rows(int product, const DevCSR& R, const void* aval, const void* uval, const uint8_t* upres, const uint8_t* allow, void* tval, uint8_t* tpres) const {
     if (kind == SR_USER) usersr_rows(product, s->add->op, s->mul, R, aval, uval, upres, allow, tval, tpres);
+    else if (kind == SR_COMPARE) cmpsr_rows(s->add->op->opcode, xcode(), cmp_sel(s->mul->opcode, product), R, aval, uval, upres, allow, (uint8_t*)tval, tpres);
     else possr_rows(s->add->op->opcode, zcode(), pos_coord(s->mul->opcode, product), R, upres, allow, tval, tpres);
   }
   // mxm: the values of a T whose pattern exists (usersr_product_values / possr_product_values); appends the kernel's name to the plan string
   void product_values(const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, DevCSR& T) const {
     if (kind == SR_USER) usersr_product_values(s->add->op, s->mul, A, aval, B, bval, T);
+    else if (kind == SR_COMPARE) cmpsr_product_values(s->add->op->opcode, xcode(), cmp_sel(s->mul->opcode, CK_MXM), A, aval, B, bval, T);
     else possr_product_values(s->add->op->opcode, zcode(), pos_coord(s->mul->opcode, PK_MXM), A, B, T);
   }
 };
@@ -170,6 +184,8 @@ struct SemiringRoute {
 inline SemiringRoute semiring_route(GrB_Semiring s) {
   if (!check_obj(s) || !check_obj(s->add)) return {SR_BUILTIN, s};
   if (check_obj(s->mul) && is_positional_semiring(s)) return {SR_POSITIONAL, s};
+  // a BUILT-IN semiring over a comparison of a non-Boolean type; the same two objects composed with GrB_Semiring_new stay on the table route ("not implemented")
+  if (check_obj(s->mul) && check_obj(s->add->op) && is_compare_semiring(s)) return {SR_COMPARE, s};
   return {is_user_semiring(s) ? SR_USER : SR_BUILTIN, s};
 }
 

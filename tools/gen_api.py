@@ -111,7 +111,7 @@ def mon_of(op, t):
     return _mon_by_key[(op, t)]
 
 
-# ---- semirings (same-type multiply; comparison-multiply semirings are not declared) ---------
+# ---- semirings: same-type multiply first; the comparison-multiply ones (a BOOL monoid over GrB_<cmp>_<T>) follow the _BOOL column ---------
 MULS = ["FIRST", "SECOND", "PAIR", "MIN", "MAX", "PLUS", "MINUS", "RMINUS", "TIMES", "DIV", "RDIV",
         "ISEQ", "ISNE", "ISGT", "ISLT", "ISGE", "ISLE", "LOR", "LAND", "LXOR"]
 for t in NUM:
@@ -129,6 +129,12 @@ for add in ["LOR", "LAND", "LXOR", "EQ", "ANY"]:
 for add, mul in [("LOR", "LAND"), ("LAND", "LOR"), ("LXOR", "LAND")]:
     semirings.append((f"GrB_{add}_{mul}_SEMIRING_BOOL", mon_of(add, "BOOL"), bin_of(mul, "BOOL")))
 semirings.append(("GrB_LXNOR_LOR_SEMIRING_BOOL", "GrB_LXNOR_MONOID_BOOL", "GrB_LOR"))
+# comparison semirings (pygraphblas/semiring.py:87-121, `boolean_re`): a BOOL monoid over the comparison GrB_<cmp>_<T> of a non-Boolean type — T x T -> BOOL.  They run
+# in mxm / mxv / vxm through the kernels of grb_cmpsr.hip; the _BOOL column above stays on the operator table
+for t in NUM:
+    for add in ["LOR", "LAND", "LXOR", "EQ", "ANY"]:
+        for mul in ["EQ", "NE", "GT", "LT", "GE", "LE"]:
+            semirings.append((f"GxB_{add}_{mul}_{t}", mon_of(add, "BOOL"), bin_of(mul, t)))
 # positional semirings (pygraphblas/semiring.py:87-93 names their multipliers): the product term's coordinate in INT32 / INT64, whatever the operands hold.  Their
 # multipliers are INTERNAL binary operators — objects that GxB_Semiring_multiply returns and the printers name, with no exported handle: nothing but mxm / mxv /
 # vxm runs them, and the exported binary-operator set is the one tests/operator_model.py mirrors
