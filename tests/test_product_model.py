@@ -106,3 +106,64 @@ def test_absent_operand_positions_and_terminals():
     assert w.val.tolist() == w32([(5 - 2) + (lo - 3), (lo - 2) + (4 - 5), (7 - 2) + (9 - 3)])
     b = PM.product("EQ", "LOR", "BOOL", MM.from_coo(2, 3, [0, 0, 0, 1, 1], [0, 1, 2, 0, 1], [False, False, True, False, False], "BOOL"), dense_vec([False, False, False], [True, True, True], "BOOL"))
     assert b.val.tolist() == [True, True] and b.pres.all()                              # two false contributions: even
+
+
+# ---- the masked matrix product (product_model.masked_mxm / mxm) --------------------------------------------------------------------------------------------------
+from product_model import MXM_MASK_TYPES as MASK_TYPES, MXM_TYPES, mxm_semirings
+
+MXM_CASES_PER_TYPE = 60          # 420 cases in all
+MXM_MASK_VALUES = {"BOOL": [False, True], "INT8": [0, 1, -128], "UINT16": [0, 0, 256, 65535], "FP32": [0.0, -0.0, 1.5, np.nan], "INT64": [0, 1 << 32, -1],
+                   "FP64": [0.0, -0.0, np.nan, -2.0, 2.0 ** -300]}
+
+
+def rand_mat(rng, typ, nr, nc, dens, vals, empty_rows=True):
+    keys = np.flatnonzero(rng.random(nr * nc) < dens)
+    if empty_rows and nr > 1: keys = keys[keys // nc != rng.integers(0, nr)]                 # one row without entries
+    return MM.Mat(nr, nc, keys, rng.choice(vals, size=len(keys)).astype(MM.NP[typ]))
+
+
+def tuples_of_mat(m):
+    return O.Tuples(m.typ, m.nrows, m.ncols, m.rows, m.cols, m.vals)
+
+
+@pytest.mark.parametrize("typ", MXM_TYPES)
+def test_masked_mxm_agrees_with_the_oracle(typ):
+    """`C<M, replace> = accum(C, op(A) add.mul op(B))` of the model against O.mxm, exactly: every type and semiring of tests/test_spgemm_masked_at_size_gpu.py,
+    valued and structural masks of its six mask types with false values, -0.0 and NaN, complemented masks (the write-back alone), rows without entries in A, B
+    and M, transposed operands, accumulators and replace, values that wrap (the types' extremes)."""
+    rng = np.random.default_rng(MXM_TYPES.index(typ) + 1900); srs = mxm_semirings(typ); seen = set()
+    for case in range(MXM_CASES_PER_TYPE):
+        sr = srs[case % len(srs)]; add, mul = sr.split("_")
+        m, k, n = (int(rng.choice([1, 3, 7, 12])) for _ in range(3))
+        ta, tb = rng.random() < 0.3, rng.random() < 0.3
+        vals = pool(typ, sr, typ.startswith("FP"))                                  # (floating point: small values, so that every sum is exact in any order)
+        A = rand_mat(rng, typ, *((k, m) if ta else (m, k)), rng.choice([0.2, 0.6, 1.0]), vals)
+        B = rand_mat(rng, typ, *((n, k) if tb else (k, n)), rng.choice([0.2, 0.6, 1.0]), vals)
+        Cm = rand_mat(rng, typ, m, n, 0.3, vals, empty_rows=False)
+        mtyp = MASK_TYPES[case % len(MASK_TYPES)]
+        mkind = str(rng.choice(["valued", "valued", "structural", "complemented", "structural complemented"]))
+        M = rand_mat(rng, mtyp, m, n, rng.choice([0.3, 0.8]), np.array(MXM_MASK_VALUES[mtyp], MM.NP[mtyp]))
+        struct, comp = "structural" in mkind, "complemented" in mkind
+        replace = rng.random() < 0.4
+        accum = None if rng.random() < 0.5 else ("LOR" if typ == "BOOL" else str(rng.choice(["PLUS", "MIN"])))
+        seen |= {sr, mkind, mtyp, "ta" if ta else "a", "tb" if tb else "b", "accum" if accum else "no accum", "replace" if replace else "keep"}
+        got = PM.mxm(Cm, A, B, add, mul, typ, mask=M, struct=struct, comp=comp, replace=replace, accum=(accum, typ) if accum else None, tran_a=ta, tran_b=tb)
+        exp = O.mxm(tuples_of_mat(Cm), tuples_of_mat(A), tuples_of_mat(B), add, mul, typ, mask=tuples_of_mat(M), accum=accum, accum_type=typ, replace=replace, mask_comp=comp,
+                    mask_struct=struct, tran_a=ta, tran_b=tb).sorted()
+        what = (typ, case, sr, mkind, mtyp, ta, tb, replace, accum)
+        assert np.array_equal(got.rows, exp.I.astype(np.int64)) and np.array_equal(got.cols, exp.J.astype(np.int64)), (what, got.keys, exp.I, exp.J)
+        assert got.typ == typ and np.array_equal(got.vals, exp.X, equal_nan=typ.startswith("FP")), (what, got.vals, exp.X)
+    assert seen >= set(srs) | set(MASK_TYPES) | {"valued", "structural", "complemented", "structural complemented", "ta", "a", "tb", "b", "accum", "no accum", "replace", "keep"}
+
+
+def test_masked_mxm_by_hand():
+    """A false or absent mask entry prunes its products; an allowed entry without a product is absent; the fold runs in ascending k (ANY keeps the largest)."""
+    A = MM.from_coo(2, 3, [0, 0, 0, 1], [0, 1, 2, 1], [1, 2, 3, 4], "INT32")
+    B = MM.from_coo(3, 3, [0, 0, 1, 1, 2], [0, 1, 0, 2, 0], [10, 20, 30, 40, 50], "INT32")
+    M = MM.from_coo(2, 3, [0, 0, 0, 1, 1], [0, 1, 2, 0, 1], [-0.0, 1.0, np.nan, 2.0, 1.0], "FP64")
+    t = PM.masked_mxm("PLUS", "TIMES", "INT32", A, B, M)
+    assert t.keys.tolist() == [1, 2, 3] and t.vals.tolist() == [20, 80, 120]        # (0, 0) is false; (1, 1) receives nothing
+    t = PM.masked_mxm("PLUS", "TIMES", "INT32", A, B, M, struct=True)
+    assert t.keys.tolist() == [0, 1, 2, 3] and t.vals.tolist() == [10 + 60 + 150, 20, 80, 120]
+    t = PM.masked_mxm("ANY", "SECOND", "INT32", A, B, None)
+    assert t.keys.tolist() == [0, 1, 2, 3, 5] and t.vals.tolist() == [50, 20, 40, 30, 40]
