@@ -61,14 +61,19 @@ void mat_host_assemble(GrB_Matrix A) {
   A->hi.swap(ni); A->hj.swap(nj); A->hx.swap(nx); P.clear(); P.shrink_to_fit();
 }
 
+// ---- what happened to the device image: one function per event, each covers csr, csc and bm (the transitions: grb_devcsr.hpp) ----
+// no device image (the host mirror was written)
 void mat_invalidate_device(GrB_Matrix A) { A->dev_valid = false; A->csr.clear(); A->csc.clear(); A->bm.clear(); }
+// rows, columns or the entry set of the device CSR changed (the structural flush, resize)
+static void mat_structure_changed(GrB_Matrix A) { A->csc.clear(); A->bm.clear(); A->csr.derived.structure_changed(); }
+// the device image was replaced as a whole: the host mirror and the edit queue go, and whatever was derived from the old image.  The caller installs the new one.
 void mat_invalidate_host(GrB_Matrix A) {
   A->host_valid = false; A->hi.clear(); A->hj.clear(); A->hx.clear(); A->pending.clear(); A->dev_elem_ops = 0;
   A->hi.shrink_to_fit(); A->hj.shrink_to_fit(); A->hx.shrink_to_fit();
-  A->csc.clear(); A->csr.has_plan = false; A->csr.plan_blocks.reset(); A->csr.plan_aux.reset();
-  A->csr.wp_rs.reset(); A->csr.wp_hot.reset(); A->csr.wp_pcol.reset(); A->csr.wp_tsize = 0; A->csr.xcd.reset();
-  A->csr.heads_valid = false; A->csr.range_state = 0;      // (the device copy was rewritten: whatever was derived from its values goes with the plans)
+  mat_structure_changed(A);
 }
+// values of the device CSR were overwritten in place (mat_set, the values-only flush): the transpose and the bitmap hold copies of them
+static void mat_values_changed(GrB_Matrix A) { A->csc.clear(); A->bm.clear(); A->csr.derived.values_changed(); }
 
 // ---- the edit queue of a container that lives in HBM only ------------------------------------------------------------------------------
 // `A[i, j] = x`, `del A[i, j]`, `v[i] = x` on a container whose only valid image is the HBM one append today's Pending record and nothing else: no download, nothing
@@ -86,14 +91,6 @@ static bool mat_edit_route(GrB_Matrix A) {
 static bool vec_edit_route(GrB_Vector v) {
   return v->dev_valid && !v->host_valid && !v->iso_full && v->lazy == 0 && v->q_reads == 0 && v->type->code < T_FC32 && v->n <= GRB_DIM_DEVICE_MAX && device_ok() && !edit_env_off();
 }
-// what was derived from the VALUES of the device CSR: an overwrite in place drops it (mat_set, the values-only flush)
-static void mat_values_changed(GrB_Matrix A) { A->csc.clear(); A->csr.xcd.reset(); A->csr.range_state = 0; A->bm.clear(); A->csr.heads_valid = false; }      // (the row heads carry the BOOL value of a row's first four entries)
-// what was derived from the structure of the device CSR (the list of mat_invalidate_host, and the bitmap cache)
-static void mat_drop_derived(GrB_Matrix A) {
-  A->csc.clear(); A->bm.clear(); A->csr.has_plan = false; A->csr.plan_blocks.reset(); A->csr.plan_aux.reset();
-  A->csr.wp_rs.reset(); A->csr.wp_hot.reset(); A->csr.wp_pcol.reset(); A->csr.wp_tsize = 0; A->csr.xcd.reset();
-  A->csr.heads_valid = false; A->csr.range_state = 0; A->csr.locality_pct = -1; A->csr.pipe_uses = 0;
-}
 void mat_edit_flush(GrB_Matrix A) {
   if (!mat_edits_queued(A)) return;
   if (!A->dev_valid || !A->csr.valid) fail(GrB_PANIC, "edit: queued element edits without a device image");
@@ -105,7 +102,7 @@ void mat_edit_flush(GrB_Matrix A) {
   DevCSR out; bool structural = false;
   const EditCounts n = csr_apply_edits(A->csr, ts, k, ei.data(), ej.data(), del.data(), x.data(), out, &structural);      // (neither csr_apply_edits nor anything it calls comes back here)
   P.clear(); P.shrink_to_fit();                              // only now: a flush that failed (allocation, launch, the entry-count limit) leaves the queue as it was, and the caller its error
-  if (structural) { A->csr = std::move(out); mat_drop_derived(A); }
+  if (structural) { A->csr = std::move(out); mat_structure_changed(A); }
   else if (n.set) mat_values_changed(A);
   g_last_plan = "edit<on=matrix,set=" + std::to_string(n.set) + ",ins=" + std::to_string(n.ins) + ",del=" + std::to_string(n.del) + "> k_edit_locate " +
                 (structural ? "k_edit_rowptr k_edit_stream k_edit_place " : n.set ? "k_edit_values " : "") + g_last_plan;
@@ -476,7 +473,7 @@ GrB_Info GrB_Matrix_resize(GrB_Matrix A, GrB_Index nr, GrB_Index nc) {
         A->csr = std::move(t);
       }
       A->csr.ncols = nc32;
-      if (changed) mat_drop_derived(A);
+      if (changed) mat_structure_changed(A);
       A->nrows = nr; A->ncols = nc;
       g_last_plan = "resize<on=matrix,rows=" + std::to_string(nr) + ",cols=" + std::to_string(nc) + "> ";
       return;

@@ -2,7 +2,7 @@
 //
 // Layout in HBM:
 //   Matrix : CSR  rowptr u32[nrows+1] | col u32[nnz] (sorted within a row) | val T[nnz]
-//            + a lazily built, cached CSR of the transpose ("CSC view") and SpMV row-block plan.
+//            + a lazily built, cached CSR of the transpose ("CSC view") and what the products derive from a CSR (grb_devcsr.hpp: CsrDerived).
 //   Vector : bitmap  val T[n] | present u8[n]   (+ nvals); sparse index lists are transient.
 // Host mirrors (sorted tuples) exist only for element-wise host access (setElement /
 // extractTuples) and are synchronised lazily in either direction.
@@ -17,6 +17,7 @@
 #include <memory>
 #include "grb_ops.hpp"
 #include "grb_vecfacts.hpp"
+#include "grb_devcsr.hpp"
 
 typedef uint64_t GrB_Index;
 
@@ -71,8 +72,6 @@ namespace grb {
 bool device_ok();                 // a HIP device was found at init
 const char* device_error();       // why not
 hipStream_t stream();             // the stream every kernel of the library is launched on
-void* dev_alloc(size_t bytes);    // pooled hipMalloc; throws GrbError(OUT_OF_MEMORY/PANIC)
-void dev_free(void* p);
 void dev_pool_release();          // return cached blocks to the driver
 size_t dev_bytes_in_use();
 int device_cus();                 // compute units of the device (256 on MI355X)
@@ -82,58 +81,10 @@ struct GrbError { int info; std::string msg; };
 #define GRB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
   ::grb::fail(GrB_PANIC, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 
-// owning device buffer
-uint64_t dev_alloc_serial();      // a number no other allocation of this process gets (the pool hands the same addresses out again)
-struct DevBuf {
-  void* p = nullptr; size_t bytes = 0;
-  uint64_t serial = 0;              // identifies this allocation where a raw address could be a recycled one (VecFacts::fe_lb_key)
-  bool borrowed = false;            // a view of memory another DevBuf owns (a row of a batch matrix's bitmap handed to a vector kernel, grb_mxm_rows.cpp): never freed here
-  DevBuf() {}
-  explicit DevBuf(size_t n) { alloc(n); }
-  DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), serial(o.serial), borrowed(o.borrowed) { o.p = nullptr; o.bytes = 0; o.serial = 0; o.borrowed = false; }
-  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; bytes = o.bytes; serial = o.serial; borrowed = o.borrowed; o.p = nullptr; o.bytes = 0; o.serial = 0; o.borrowed = false; } return *this; }
-  ~DevBuf() { reset(); }
-  void alloc(size_t n) { reset(); if (n) { p = dev_alloc(n); bytes = n; serial = dev_alloc_serial(); } }
-  void borrow(void* q, size_t n) { reset(); p = q; bytes = n; serial = dev_alloc_serial(); borrowed = true; }
-  void reset() { if (p && !borrowed) dev_free(p); p = nullptr; bytes = 0; serial = 0; borrowed = false; }
-  template <class T> T* as() const { return (T*)p; }
-};
-
-// ---- device CSR ---------------------------------------------------------------------------
-struct DevCSR {
-  uint32_t nrows = 0, ncols = 0; uint64_t nnz = 0;
-  DevBuf rowptr, col, val;      // u32[nrows+1], u32[nnz], T[nnz]
-  // SpMV row-block plan (grb_spmv.hip): blocks of consecutive rows holding <= SPMV_BLOCK_NNZ
-  // entries, long rows split into parts.  Built on first mxv, cached with the matrix.
-  DevBuf plan_blocks; uint32_t plan_nblocks = 0; DevBuf plan_aux; uint32_t plan_nlong = 0;
-  bool has_plan = false;
-  int range_state = 0;          // largest |value| of the stored values: 0 not measured, 1 = range_abs holds it, 2 = not usable (NaN / infinity / a type without a range)
-  double range_abs = 0;         // (as a double: an upper bound is all the caller needs — grb_mxv.cpp "big holes")
-  int locality_pct = -1;        // share of entries whose column is < 16 behind its predecessor in the row (measured once, -1 = not yet): gathers with locality need no panels
-  // kernel-W plan (grb_spmv_wavepipe.hpp): per-task first row, hot-column list, remapped column array, per-wave carries
-  DevBuf wp_rs, wp_hot, wp_pcol, wp_carry; uint32_t wp_nhot = 0, wp_ntasks = 0, wp_nwarm = 0; int wp_tsize = 0;
-  std::shared_ptr<void> xcd;    // kernel-X plan (grb_spmv_xcd.hpp: XcdPlan), panel-major copy of the matrix
-  // row heads (grb_spmv_kernels.hpp, round 5): for the masked pull of a BFS level — per row its first four entries as one 16-byte word (per entry:
-  // bits 29..0 the column, bit 31 its BOOL value, in the fourth bit 30 = the row has more entries; absent = 0xFFFFFFFF) and one bit per row "has an
-  // entry": a level then costs what its unvisited NON-EMPTY rows cost, and a row decided by its first entries never touches the column array.
-  // Built at the first masked pull of a matrix with < 2^30 - 1 columns; heads_vals: the value bits come from one-byte BOOL values (else they are 1).
-  DevBuf heads, nonempty; bool heads_valid = false, heads_vals = false;
-  uint32_t pipe_uses = 0;       // full-operand pull products this matrix has served: the first runs kernel W (cheap plan), kernel X's plan is built for the second
-  bool valid = false;
-  void clear() { rowptr.reset(); col.reset(); val.reset(); plan_blocks.reset(); plan_aux.reset();
-                 wp_rs.reset(); wp_hot.reset(); wp_pcol.reset(); wp_carry.reset(); wp_nhot = wp_ntasks = 0; wp_tsize = 0; xcd.reset(); pipe_uses = 0; heads.reset(); nonempty.reset(); heads_valid = false;
-                 nnz = 0; has_plan = false; locality_pct = -1; range_state = 0; valid = false; plan_nblocks = plan_nlong = 0; }
-};
+// DevBuf (owning device buffer, dev_alloc / dev_free), DevCSR with its CsrDerived record, DevBitmap: grb_devcsr.hpp
 
 }  // namespace grb
 
-// A matrix of a few very long rows (the ns x n batches of the reference's betweenness centrality, gap/bcmark.py:16-67) as a BITMAP: val T[nrows x ncols]
-// | pres u8[nrows x ncols], row-major — i.e. ns bitmap vectors back to back, or one bitmap vector of nrows x ncols positions.  Round 6: such a matrix may
-// live in this form alone (dev_valid == host_valid == false, bm.valid == true): the batch operations (grb_mxm_rows.cpp) read and write it directly, and the
-// CSR is made from it only when something else asks (mat_to_device).
-namespace grb { struct DevBitmap { DevBuf val, pres; bool valid = false; uint64_t nvals = 0; bool nvals_known = false;
-                                  void clear() { val.reset(); pres.reset(); valid = false; nvals = 0; nvals_known = false; } }; }
 struct GrB_Matrix_opaque {
   uint64_t magic = GRB_MAGIC;
   GrB_Type type = nullptr;
@@ -202,8 +153,8 @@ namespace grb {
 void mat_host_assemble(GrB_Matrix A);     // apply pending edits to the host mirror
 void mat_to_host(GrB_Matrix A);           // ensure host mirror valid (downloads if needed)
 void mat_to_device(GrB_Matrix A);         // ensure device CSR valid (assembles + uploads)
-void mat_invalidate_host(GrB_Matrix A);   // device was written
-void mat_invalidate_device(GrB_Matrix A); // host was written
+void mat_invalidate_host(GrB_Matrix A);   // the device image was replaced as a whole: the host mirror, the edit queue, csc, bm and everything in csr.derived go
+void mat_invalidate_device(GrB_Matrix A); // host was written: no device image
 uint64_t mat_nvals(GrB_Matrix A);
 // batch matrices (a few very long rows) in bitmap form — grb_mxm_rows.cpp
 bool mat_batch_shape(uint64_t nrows, uint64_t ncols, int type_code);   // <= 64 rows of >= 65536 (a multiple of 64) columns, a non-complex type, < 2^32 positions

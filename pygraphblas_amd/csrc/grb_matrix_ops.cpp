@@ -61,9 +61,7 @@ DevCSR pattern_copy(const DevCSR& S, size_t val_bytes) {
 void adopt(GrB_Matrix C, DevCSR& T, int tcode) {
   // C becomes exactly T (cast values if the types differ)
   if (tcode != C->type->code && T.nnz) { DevBuf c(T.nnz * C->type->size); vec_cast_values(C->type->code, c.p, tcode, T.val.p, T.nnz); T.val = std::move(c); }
-  mat_invalidate_host(C); C->csc.clear(); C->csr.clear(); C->bm.clear();
-  C->csr.nrows = T.nrows; C->csr.ncols = T.ncols; C->csr.nnz = T.nnz;
-  C->csr.rowptr = std::move(T.rowptr); C->csr.col = std::move(T.col); C->csr.val = std::move(T.val);
+  C->csr = std::move(T); mat_invalidate_host(C);      // (the old image is freed by the move; what was derived from it, the caches, the host mirror and the edit queue go)
   if (!C->csr.val.p) C->csr.val.alloc(8);
   if (!C->csr.col.p) C->csr.col.alloc(8);
   C->csr.valid = true; C->dev_valid = true; C->host_valid = false;

@@ -258,7 +258,7 @@ void mat_bitmap_to_csr(GrB_Matrix A) {
 
 // C becomes the bitmap (val, pres): the batch operations' way of writing a result
 static void adopt_bitmap(GrB_Matrix C, DevBuf&& val, DevBuf&& pres, bool known, uint64_t nvals) {
-  mat_invalidate_host(C); C->csc.clear(); C->csr.clear(); C->dev_valid = false; C->iso_full = false;
+  mat_invalidate_host(C); C->csr.clear(); C->dev_valid = false; C->iso_full = false;      // (the bitmap is the only form: no CSR image)
   C->bm.val = std::move(val); C->bm.pres = std::move(pres); C->bm.valid = true; C->bm.nvals = nvals; C->bm.nvals_known = known;
 }
 
@@ -539,7 +539,7 @@ static bool spmm_pull_batch(GrB_Matrix A, DevBitmap& ab, GrB_Matrix Mmask, const
   // per-row route pays two counting kernels and a host round trip per row, so the pass wins from a few thousand entries on.)
   if (!(e && atoi(e) == 1) && tot * 4096 < (uint64_t)nr * nin) return false;
   SemiringDesc sd = make_semiring_desc(semiring, /*swap_mult_args=*/true);       // vxm orientation: mult(u(i), B(i, j)); the kernels call mult(matrix value, operand value)
-  DevCSR& R = const_cast<DevCSR&>(dv.tran1 ? (mat_to_device(B), B->csr) : mat_csc(B));            // rows of R = output positions
+  const DevCSR& R = dv.tran1 ? (mat_to_device(B), B->csr) : mat_csc(B);            // rows of R = output positions
   if (R.nrows != nout || R.ncols != nin) return false;
   spmv_build_plan(R);                                                              // its row blocks (cached with the matrix, shared with kernel A)
   const bool uses_a = sd.flip ? binop_uses_y(sd.mulop) : binop_uses_x(sd.mulop);
@@ -560,7 +560,7 @@ static bool spmm_pull_batch(GrB_Matrix A, DevBitmap& ab, GrB_Matrix Mmask, const
         hipLaunchKernelGGL((k_spb_interleave<T, N>), dim3(grid_of(nin)), dim3(256), 0, stream(), (const T*)ab.val.p, ab.pres.as<uint8_t>(), nr, nin, (T*)ui.p, upm.as<uint8_t>());
         with_semiring<T>(sd, [&](auto sr) {
           typedef decltype(sr) SR;
-          if (R.plan_nblocks) hipLaunchKernelGGL((k_spb_blocks<T, SR, N>), dim3(R.plan_nblocks), dim3(SPMV_THREADS), 0, stream(), (const SpmvBlock*)R.plan_blocks.p, R.rowptr.as<uint32_t>(), R.col.as<uint32_t>(),
+          if (R.derived.plan_nblocks) hipLaunchKernelGGL((k_spb_blocks<T, SR, N>), dim3(R.derived.plan_nblocks), dim3(SPMV_THREADS), 0, stream(), (const SpmvBlock*)R.derived.plan_blocks.p, R.rowptr.as<uint32_t>(), R.col.as<uint32_t>(),
                                                  (const T*)av, nout, (const T*)ui.p, upm.as<uint8_t>(), allowm.as<uint8_t>(), (T*)tval.p, tpres.as<uint8_t>(), sr);
           hipLaunchKernelGGL((k_spb_pull_long<T, SR, N>), dim3(2048), dim3(SPB_LT), 0, stream(), R.rowptr.as<uint32_t>(), R.col.as<uint32_t>(), (const T*)av, lcnt.as<uint32_t>(), lrec.as<uint32_t>(), litem.as<uint32_t>(),
                              (const T*)ui.p, upm.as<uint8_t>(), allowm.as<uint8_t>(), (T*)lpval.p, lphas.as<uint32_t>(), sr);

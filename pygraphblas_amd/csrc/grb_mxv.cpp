@@ -105,18 +105,18 @@ static BigHoles plan_big_holes(bool eligible, const SemiringDesc& sd, GrB_Matrix
   BigHoles big{false, {0}, {0}, 0, 0};
   if (!(eligible && !sd.flip && sd.mulop == B_PLUS && (sd.addop == B_MIN || sd.addop == B_MAX) &&
         (sd.zcode == T_INT32 || sd.zcode == T_INT64 || sd.zcode == T_FP32 || sd.zcode == T_FP64) && A->type->code == sd.zcode && u->type->code == sd.zcode)) return big;
-  DevCSR& R = useT ? const_cast<DevCSR&>(mat_csc(A)) : A->csr;
+  const DevCSR& R = useT ? mat_csc(A) : A->csr;
   if (!(R.nnz >= (1u << 20) && u_nvals * 64 >= u->n)) return big;                       // a product the pipeline kernels take, an operand that is not nearly empty
   uint8_t mn[8], mx[8]; uint64_t bad = 0, cnt = 0;
-  if (R.range_state == 0) {                       // the matrix's range: measured once, cached with the CSR
-    R.range_state = 2;
-    if (value_range(sd.zcode, R.nnz, R.val.p, nullptr, mn, mx, &bad, &cnt) && bad == 0 && cnt) { R.range_abs = range_abs_of(sd.zcode, mn, mx); R.range_state = 1; }
+  if (R.derived.range_state == 0) {                       // the matrix's range: measured once, cached with the CSR
+    R.derived.range_state = 2;
+    if (value_range(sd.zcode, R.nnz, R.val.p, nullptr, mn, mx, &bad, &cnt) && bad == 0 && cnt) { R.derived.range_abs = range_abs_of(sd.zcode, mn, mx); R.derived.range_state = 1; }
   }
-  if (R.range_state != 1) return big;
+  if (R.derived.range_state != 1) return big;
   bad = 0; cnt = 0;
   const bool bound_known = u->facts.abs_bound >= 0 && u->lazy == 0 && u->dev_valid;          // left by the previous sweep: no kernel, no read-back
   if (!bound_known && !(value_range(sd.zcode, u->n, u->dval.p, u->dpres.as<uint8_t>(), mn, mx, &bad, &cnt) && bad == 0 && cnt)) return big;
-  big.uabs = bound_known ? std::fabs(u->facts.abs_bound) : range_abs_of(sd.zcode, mn, mx); big.aabs = R.range_abs;
+  big.uabs = bound_known ? std::fabs(u->facts.abs_bound) : range_abs_of(sd.zcode, mn, mx); big.aabs = R.derived.range_abs;
   const BigHolesConstants c = big_holes_constants(sd.zcode, sd.addop == B_MIN, big.aabs, big.uabs);
   big.on = c.admitted; memcpy(big.fill, c.fill, 16); memcpy(big.thresh, c.thresh, 16);
   return big;
@@ -249,13 +249,13 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
   const void* const tkey = tval.p;
   if (push) {
     // push walks rows of M^T:  M^T = useT ? A : A^T
-    DevCSR& P = useT ? A->csr : const_cast<DevCSR&>(mat_csc(A));
+    const DevCSR& P = useT ? A->csr : mat_csc(A);
     call.M = &P; call.upres = u->dpres.as<uint8_t>();
     if (u->facts.small_valid && u->facts.small_idx.size() == u_nvals) { call.small_idx = u->facts.small_idx.data(); call.small_n = (uint32_t)u_nvals; call.excl_small = excl_small; }
     call.aval = uses_a ? cast_values(sd.zcode, A->type->code, P.val.p, P.nnz, acast) : nullptr;
     spmspv_push(call, sd, u_nvals);
   } else {
-    DevCSR& R = useT ? const_cast<DevCSR&>(mat_csc(A)) : A->csr;
+    const DevCSR& R = useT ? mat_csc(A) : A->csr;
     call.M = &R; call.upres = (u_full || fill_holes || big.on) ? nullptr : u->dpres.as<uint8_t>();
     if (fused_mask) {
       call.upres = u->dpres.as<uint8_t>(); call.fm_val = u->dval.as<uint8_t>(); call.fm_flags = (uint8_t)((dv.mask_struct ? 1 : 0) | (dv.mask_comp ? 2 : 0));

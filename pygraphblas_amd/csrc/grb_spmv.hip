@@ -31,8 +31,9 @@ template <class T> void run_pull(const SpmvCall& c, const SemiringDesc& d);
 template <class T> void run_push(const SpmvCall& c, const SemiringDesc& d, const uint32_t* fidx, uint64_t u_nvals, uint32_t* longlist);
 
 // ---- plan: greedy row blocking, once per matrix -------------------------------------------------------------
-void spmv_build_plan(DevCSR& M) {
-  if (M.has_plan) return;
+void spmv_build_plan(const DevCSR& M) {
+  CsrDerived& D = M.derived;
+  if (D.has_plan) return;
   std::vector<uint32_t> rp((size_t)M.nrows + 1);
   GRB_HIP(hipMemcpyAsync(rp.data(), M.rowptr.p, rp.size() * 4, hipMemcpyDeviceToHost, stream()));
   GRB_HIP(hipStreamSynchronize(stream()));
@@ -57,16 +58,16 @@ void spmv_build_plan(DevCSR& M) {
       r = e;
     }
   }
-  M.plan_nblocks = (uint32_t)blocks.size(); M.plan_nlong = nslots;
-  M.plan_blocks.alloc(blocks.size() * sizeof(SpmvBlock) + 16);
-  GRB_HIP(hipMemcpyAsync(M.plan_blocks.p, blocks.data(), blocks.size() * sizeof(SpmvBlock), hipMemcpyHostToDevice, stream()));
+  D.plan_nblocks = (uint32_t)blocks.size(); D.plan_nlong = nslots;
+  D.plan_blocks.alloc(blocks.size() * sizeof(SpmvBlock) + 16);
+  GRB_HIP(hipMemcpyAsync(D.plan_blocks.p, blocks.data(), blocks.size() * sizeof(SpmvBlock), hipMemcpyHostToDevice, stream()));
   // aux: [partials 8 B * nslots] [tickets u32 * nslots] [partial flags u8 * nslots]  (tickets indexed by `slot`; the 8-byte
   // partials come first so that they are 8-byte aligned whatever nslots is)
   const size_t aux = (size_t)(nslots + 1) * 8 + (size_t)(nslots + 1) * 4 + (size_t)(nslots + 1);
-  M.plan_aux.alloc(aux);
-  GRB_HIP(hipMemsetAsync(M.plan_aux.p, 0, aux, stream()));
+  D.plan_aux.alloc(aux);
+  GRB_HIP(hipMemsetAsync(D.plan_aux.p, 0, aux, stream()));
   GRB_HIP(hipStreamSynchronize(stream()));
-  M.has_plan = true;
+  D.has_plan = true;
 }
 
 bool spmv_rowlane_applies(const DevCSR& M, const SemiringDesc& d, int method) {
@@ -99,7 +100,7 @@ __global__ void k_compact_idx(const uint8_t* __restrict__ pres, const uint32_t* 
 
 void spmspv_push(const SpmvCall& c, const SemiringDesc& d, uint64_t u_nvals) {
   // c.M here is the CSR whose ROWS are indexed like u (i.e. the transpose of the pull operand)
-  DevCSR& M = *c.M; const uint64_t nu = M.nrows, nout = M.ncols;
+  const DevCSR& M = *c.M; const uint64_t nu = M.nrows, nout = M.ncols;
   auto grid_of = [](uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (unsigned)b; };
   DevBuf flags, pos, fidx((u_nvals + 1) * 4), longlist((u_nvals + 2) * 4);
   if (c.small_idx && c.small_n == u_nvals && u_nvals <= 64) {

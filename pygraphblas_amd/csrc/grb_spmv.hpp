@@ -18,7 +18,7 @@ struct SpmvBlock { uint32_t row, aux, nparts, slot; };
 enum SpmvMethod { SPMV_AUTO = 0, SPMV_ADAPTIVE = 1, SPMV_ROWGROUP = 2, SPMV_PUSH = 3, SPMV_WAVEPIPE = 4, SPMV_XCD = 5 };
 
 struct SpmvCall {
-  DevCSR* M;                // pull: rows of M index the output.  push: rows of M index the input u.
+  const DevCSR* M;              // pull: rows of M index the output.  push: rows of M index the input u.
   const void* aval;         // M's values already in the semiring type (nullptr when the multiply ignores them)
   const void* uval;         // u values in the semiring type (dense array of length ncols(M) / nrows(M) for push)
   const uint8_t* upres;     // presence bytes, nullptr when every entry of u is present (pull only)
@@ -61,7 +61,7 @@ struct SpmvCall {
 bool spmv_rowlane_applies(const DevCSR& M, const SemiringDesc& d, int method);      // would a masked pull of this matrix run the row-lane kernel?
 
 const std::string& xcd_mapping();   // "roundrobin8" when workgroup b of a full-chip launch runs on XCD b % 8 (probed once)
-void spmv_build_plan(DevCSR& M);
+void spmv_build_plan(const DevCSR& M);
 void spmv_pull(const SpmvCall& c, const SemiringDesc& d);
 bool spmspv_push_supported(const SemiringDesc& d);
 void spmspv_push(const SpmvCall& c, const SemiringDesc& d, uint64_t u_nvals);

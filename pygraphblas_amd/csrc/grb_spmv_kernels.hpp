@@ -608,14 +608,14 @@ static __global__ void k_col_locality(const uint32_t* __restrict__ rowptr, const
   if ((threadIdx.x & 63) == 0 && seen) { atomicAdd(out, near); atomicAdd(out + 1, seen); }
 }
 // share (in %) of the sampled entries whose column lies within 16 of the previous entry of the row; measured once per matrix
-static inline int spmv_locality_pct(DevCSR& M) {
-  if (M.locality_pct >= 0) return M.locality_pct;
+static inline int spmv_locality_pct(const DevCSR& M) {
+  if (M.derived.locality_pct >= 0) return M.derived.locality_pct;
   DevBuf cnt(16); GRB_HIP(hipMemsetAsync(cnt.p, 0, 16, stream()));
   const unsigned nb = (unsigned)((M.nrows / 16 + 255) / 256 + 1);
   hipLaunchKernelGGL(k_col_locality, dim3(nb > 512 ? 512 : nb), dim3(256), 0, stream(), M.rowptr.as<uint32_t>(), M.col.as<uint32_t>(), M.nrows, (unsigned long long*)cnt.p);
   unsigned long long res[2] = {0, 0}; GRB_HIP(hipMemcpyAsync(res, cnt.p, 16, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
-  M.locality_pct = res[1] ? (int)(100.0 * (double)res[0] / (double)res[1]) : 0;
-  return M.locality_pct;
+  M.derived.locality_pct = res[1] ? (int)(100.0 * (double)res[0] / (double)res[1]) : 0;
+  return M.derived.locality_pct;
 }
 
 // ---- row heads (DevCSR::heads / nonempty) --------------------------------------------------------------------------------------------------
@@ -636,17 +636,18 @@ static __global__ void k_row_heads(uint32_t nrows, const uint32_t* __restrict__ 
   }
 }
 // bool8_vals: the matrix values as one-byte BOOLs in place (nullptr: the caller's multiplier ignores them)
-static inline bool spmv_row_heads(DevCSR& M, const uint8_t* bool8_vals) {
-  if (M.heads_valid && (M.heads_vals || !bool8_vals)) return true;
+static inline bool spmv_row_heads(const DevCSR& M, const uint8_t* bool8_vals) {
+  CsrDerived& D = M.derived;
+  if (D.heads_valid && (D.heads_vals || !bool8_vals)) return true;
   if (M.ncols >= 0x3FFFFFFFu || !M.nrows) return false;
-  if (!M.heads_valid) { M.heads.alloc((size_t)M.nrows * 16 + 16); M.nonempty.alloc(((size_t)M.nrows + 31) / 32 * 4 + 64); }
-  hipLaunchKernelGGL(k_row_heads, dim3((unsigned)(((uint64_t)M.nrows + 255) / 256)), dim3(256), 0, stream(), M.nrows, M.rowptr.as<uint32_t>(), M.col.as<uint32_t>(), bool8_vals, (uint4*)M.heads.p, M.nonempty.as<uint32_t>());
-  M.heads_valid = true; M.heads_vals = bool8_vals != nullptr;
+  if (!D.heads_valid) { D.heads.alloc((size_t)M.nrows * 16 + 16); D.nonempty.alloc(((size_t)M.nrows + 31) / 32 * 4 + 64); }
+  hipLaunchKernelGGL(k_row_heads, dim3((unsigned)(((uint64_t)M.nrows + 255) / 256)), dim3(256), 0, stream(), M.nrows, M.rowptr.as<uint32_t>(), M.col.as<uint32_t>(), bool8_vals, (uint4*)D.heads.p, D.nonempty.as<uint32_t>());
+  D.heads_valid = true; D.heads_vals = bool8_vals != nullptr;
   return true;
 }
 
 template <class T> void run_pull(const SpmvCall& c, const SemiringDesc& d) {
-  DevCSR& M = *c.M;
+  const DevCSR& M = *c.M;
   with_semiring<T>(d, [&](auto sr) {
     typedef decltype(sr) SR;
     SpmvKArgs<T> a{};
@@ -685,7 +686,7 @@ template <class T> void run_pull(const SpmvCall& c, const SemiringDesc& d) {
             static const bool no_heads = wp_env("GRB_MI355X_NO_ROW_HEADS", 0) != 0;                    // measurement hook: round 5's first half (row pointers + column array)
             // (the value bits need the matrix values as one-byte BOOLs where they lie: a BOOL matrix under a Boolean semiring — the adjacency matrix of the BFS)
             const bool vals_in_place = c.aval == M.val.p;
-            if (kk > 1 && !no_heads && (!sr.uses_a() || vals_in_place) && spmv_row_heads(M, sr.uses_a() ? (const uint8_t*)M.val.p : nullptr)) { a.heads = (const uint4*)M.heads.p; a.nonempty = M.nonempty.as<uint32_t>(); }
+            if (kk > 1 && !no_heads && (!sr.uses_a() || vals_in_place) && spmv_row_heads(M, sr.uses_a() ? (const uint8_t*)M.val.p : nullptr)) { a.heads = (const uint4*)M.derived.heads.p; a.nonempty = M.derived.nonempty.as<uint32_t>(); }
             if (kk == 4 && a.fm_code) hipLaunchKernelGGL((k_spmv_rowlane_k<T, SR, false, true, 4, true>), dim3((unsigned)nbk), dim3(thr), 0, stream(), a, sr);
             else if (kk == 4) hipLaunchKernelGGL((k_spmv_rowlane_k<T, SR, false, true, 4>), dim3((unsigned)nbk), dim3(thr), 0, stream(), a, sr);
             else if (kk == 2) hipLaunchKernelGGL((k_spmv_rowlane_k<T, SR, false, true, 2>), dim3((unsigned)nbk), dim3(thr), 0, stream(), a, sr);
@@ -724,15 +725,15 @@ template <class T> void run_pull(const SpmvCall& c, const SemiringDesc& d) {
         // (tests/test_baseline_configs_gpu.py::test_config4_rmat25_pagerank_single_gpu).
         static const uint32_t after_env = wp_env("GRB_MI355X_XPLAN_AFTER", 1);
         const uint32_t after = std::is_same<T, float>::value ? 0u : after_env;
-        const XcdPlan* have = static_cast<const XcdPlan*>(M.xcd.get());
+        const XcdPlan* have = static_cast<const XcdPlan*>(M.derived.xcd.get());
         const bool planned = have && have->tsize == (int)sizeof(T);
-        if (planned || c.method == SPMV_XCD || M.pipe_uses >= after) {
+        if (planned || c.method == SPMV_XCD || M.derived.pipe_uses >= after) {
           if (run_xcd<T>(c, d, device_cus())) {
-            if (!planned && M.wp_tsize) { M.wp_rs.reset(); M.wp_hot.reset(); M.wp_pcol.reset(); M.wp_carry.reset(); M.wp_nhot = M.wp_ntasks = 0; M.wp_tsize = 0; }
+            if (!planned) M.derived.drop_wavepipe();
             return;
           }
         }
-        M.pipe_uses++;
+        M.derived.pipe_uses++;
       }
       const bool want = c.method == SPMV_WAVEPIPE || c.method == SPMV_XCD || (c.method == SPMV_AUTO && M.nnz >= (1u << 20));
       if (want && full && !c.allow && M.ncols < 0x70000000u && M.nnz >= (uint64_t)WP_ENT && device_cus() > 0) {
@@ -741,12 +742,12 @@ template <class T> void run_pull(const SpmvCall& c, const SemiringDesc& d) {
       }
     }
     spmv_build_plan(M);
-    a.blocks = M.plan_blocks.as<SpmvBlock>();
-    uint8_t* aux = M.plan_aux.as<uint8_t>();
-    const size_t ns = (size_t)M.plan_nlong + 1;
+    a.blocks = M.derived.plan_blocks.as<SpmvBlock>();
+    uint8_t* aux = M.derived.plan_aux.as<uint8_t>();
+    const size_t ns = (size_t)M.derived.plan_nlong + 1;
     a.partial = (T*)aux; a.tickets = (uint32_t*)(aux + ns * 8); a.pflag = aux + ns * 8 + ns * 4;
-    if (M.plan_nblocks == 0) return;
-    const dim3 grid(M.plan_nblocks), block(SPMV_THREADS);
+    if (M.derived.plan_nblocks == 0) return;
+    const dim3 grid(M.derived.plan_nblocks), block(SPMV_THREADS);
     if constexpr (std::is_same<T, double>::value && SR::is_static) {
       const char* eg = getenv("GRB_MI355X_GATHER"); const char* es = getenv("GRB_MI355X_STREAM");
       const int gm = eg ? atoi(eg) : 0, sm = es ? atoi(es) : 0;
@@ -784,7 +785,7 @@ template <class T> __global__ void k_push_init(T* __restrict__ tval, uint8_t* __
   for (uint64_t i = n16 * 16 + blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) { tpres[i] = 0; tval[i] = ident; }
 }
 template <class T> void run_push(const SpmvCall& c, const SemiringDesc& d, const uint32_t* fidx, uint64_t u_nvals, uint32_t* longlist) {
-  DevCSR& M = *c.M; const uint64_t nout = M.ncols;
+  const DevCSR& M = *c.M; const uint64_t nout = M.ncols;
   uint32_t* const fidx_w = const_cast<uint32_t*>(fidx);
   auto grid_of = [](uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (unsigned)b; };
   with_semiring<T>(d, [&](auto sr) {

@@ -383,13 +383,14 @@ static __global__ void k_wp_mark_row_starts(const uint32_t* __restrict__ rowptr,
   for (uint32_t r = blockIdx.x * 256 + threadIdx.x; r < nrows; r += gridDim.x * 256) { const uint32_t s = rowptr[r]; if (rowptr[r + 1] > s) pcol[s] |= WP_ROWSTART; }
 }
 
-template <class T> void build_wavepipe_plan(DevCSR& M) {
+template <class T> void build_wavepipe_plan(const DevCSR& M) {
+  CsrDerived& D = M.derived;
   constexpr uint32_t H = wp_hot<T>::H;
   auto grid_n = [](uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 8192) b = 8192; return (unsigned)b; };
   const uint32_t n = M.ncols, ntasks = (uint32_t)((M.nnz + M.nrows + WP_ENT - 1) / WP_ENT);
-  M.wp_rs.alloc(((size_t)ntasks + 1) * 8);            // trow[ntasks+1] then tent[ntasks+1]
+  D.wp_rs.alloc(((size_t)ntasks + 1) * 8);            // trow[ntasks+1] then tent[ntasks+1]
   hipLaunchKernelGGL(k_wp_task_starts, dim3(grid_n(ntasks + 1)), dim3(256), 0, stream(), M.rowptr.as<uint32_t>(), M.nrows, (uint32_t)M.nnz, ntasks,
-                     M.wp_rs.as<uint32_t>(), M.wp_rs.as<uint32_t>() + (ntasks + 1));
+                     D.wp_rs.as<uint32_t>(), D.wp_rs.as<uint32_t>() + (ntasks + 1));
   DevBuf cnt((size_t)n * 4 + 4), key((size_t)n * 4 + 4), id((size_t)n * 4 + 4), key2((size_t)n * 4 + 4), id2((size_t)n * 4 + 4), rank((size_t)n * 4 + 4);
   GRB_HIP(hipMemsetAsync(cnt.p, 0, (size_t)n * 4 + 4, stream()));
   // Column frequencies from a SAMPLE of ~2^22 entries (round 4).  The ranking only decides which columns sit in the LDS table and in the
@@ -412,15 +413,15 @@ template <class T> void build_wavepipe_plan(DevCSR& M) {
   // rarer ones straight from u
   const uint32_t nwarm_cap = (uint32_t)((8u << 20) / sizeof(T));
   const uint32_t nwarm = n < nwarm_cap ? n : nwarm_cap;
-  M.wp_hot.alloc((size_t)nwarm * 4 + 4);               // order[rank] = original column for rank < nwarm
-  GRB_HIP(hipMemcpyAsync(M.wp_hot.p, id2.p, (size_t)nwarm * 4, hipMemcpyDeviceToDevice, stream()));
-  M.wp_nwarm = nwarm;
+  D.wp_hot.alloc((size_t)nwarm * 4 + 4);               // order[rank] = original column for rank < nwarm
+  GRB_HIP(hipMemcpyAsync(D.wp_hot.p, id2.p, (size_t)nwarm * 4, hipMemcpyDeviceToDevice, stream()));
+  D.wp_nwarm = nwarm;
   GRB_HIP(hipMemsetAsync(rank.p, 0xFF, (size_t)n * 4 + 4, stream()));
   hipLaunchKernelGGL(k_wp_rank, dim3(grid_n(n)), dim3(256), 0, stream(), id2.as<uint32_t>(), n, rank.as<uint32_t>());
-  M.wp_pcol.alloc(M.nnz * 4 + 4);
-  hipLaunchKernelGGL(k_wp_remap, dim3(grid_n(M.nnz)), dim3(256), 0, stream(), M.col.as<uint32_t>(), M.nnz, rank.as<uint32_t>(), nwarm, M.wp_pcol.as<uint32_t>());
-  hipLaunchKernelGGL(k_wp_mark_row_starts, dim3(grid_n(M.nrows)), dim3(256), 0, stream(), M.rowptr.as<uint32_t>(), M.nrows, M.wp_pcol.as<uint32_t>());
-  M.wp_nhot = nhot; M.wp_ntasks = ntasks; M.wp_tsize = (int)sizeof(T);
+  D.wp_pcol.alloc(M.nnz * 4 + 4);
+  hipLaunchKernelGGL(k_wp_remap, dim3(grid_n(M.nnz)), dim3(256), 0, stream(), M.col.as<uint32_t>(), M.nnz, rank.as<uint32_t>(), nwarm, D.wp_pcol.as<uint32_t>());
+  hipLaunchKernelGGL(k_wp_mark_row_starts, dim3(grid_n(M.nrows)), dim3(256), 0, stream(), M.rowptr.as<uint32_t>(), M.nrows, D.wp_pcol.as<uint32_t>());
+  D.wp_nhot = nhot; D.wp_ntasks = ntasks; D.wp_tsize = (int)sizeof(T);
   GRB_HIP(hipStreamSynchronize(stream()));
 }
 
@@ -429,22 +430,22 @@ template <class T> __global__ void k_wp_permute(const T* __restrict__ x, const u
 }
 
 template <class T> bool run_wavepipe(const SpmvCall& c, const SemiringDesc& d, int ncu) {
-  DevCSR& M = *c.M;
-  if (M.wp_tsize != (int)sizeof(T)) build_wavepipe_plan<T>(M);
+  const DevCSR& M = *c.M; CsrDerived& D = M.derived;
+  if (D.wp_tsize != (int)sizeof(T)) build_wavepipe_plan<T>(M);
   // u in column-rank order: frequently used entries share cache lines (and the first H of them are the LDS table)
-  DevBuf xp((size_t)M.wp_nwarm * sizeof(T) + 8);
+  DevBuf xp((size_t)D.wp_nwarm * sizeof(T) + 8);
   const bool uses_u = d.flip ? binop_uses_x(d.mulop) : binop_uses_y(d.mulop);
-  if (uses_u) hipLaunchKernelGGL((k_wp_permute<T>), dim3(2048), dim3(256), 0, stream(), (const T*)c.uval, M.wp_hot.as<uint32_t>(), M.wp_nwarm, xp.as<T>());
-  const uint32_t tpw = wp_chunk_tasks(M.wp_ntasks, (uint32_t)ncu * WP_WGS_PER_CU * WP_WAVES), nwaves = (M.wp_ntasks + tpw - 1) / tpw;      // one record per chunk
-  if (M.wp_carry.bytes < (size_t)nwaves * sizeof(WpCarry<T>)) M.wp_carry.alloc((size_t)nwaves * sizeof(WpCarry<T>));
-  WpArgs<T> a{M.rowptr.as<uint32_t>(), M.wp_pcol.as<uint32_t>(), (const T*)c.aval, (const T*)xp.p, (const T*)c.uval, M.wp_hot.as<uint32_t>(), M.wp_rs.as<uint32_t>(), M.wp_rs.as<uint32_t>() + (M.wp_ntasks + 1),
-              (T*)c.tval, c.tpres, M.wp_carry.as<WpCarry<T>>(), M.nrows, M.wp_ntasks, (uint32_t)M.nnz, tpw, wp_env("GRB_MI355X_WP_STATIC", WP_STATIC_PCT), M.wp_nhot, M.wp_nwarm};
+  if (uses_u) hipLaunchKernelGGL((k_wp_permute<T>), dim3(2048), dim3(256), 0, stream(), (const T*)c.uval, D.wp_hot.as<uint32_t>(), D.wp_nwarm, xp.as<T>());
+  const uint32_t tpw = wp_chunk_tasks(D.wp_ntasks, (uint32_t)ncu * WP_WGS_PER_CU * WP_WAVES), nwaves = (D.wp_ntasks + tpw - 1) / tpw;      // one record per chunk
+  if (D.wp_carry.bytes < (size_t)nwaves * sizeof(WpCarry<T>)) D.wp_carry.alloc((size_t)nwaves * sizeof(WpCarry<T>));
+  WpArgs<T> a{M.rowptr.as<uint32_t>(), D.wp_pcol.as<uint32_t>(), (const T*)c.aval, (const T*)xp.p, (const T*)c.uval, D.wp_hot.as<uint32_t>(), D.wp_rs.as<uint32_t>(), D.wp_rs.as<uint32_t>() + (D.wp_ntasks + 1),
+              (T*)c.tval, c.tpres, D.wp_carry.as<WpCarry<T>>(), M.nrows, D.wp_ntasks, (uint32_t)M.nnz, tpw, wp_env("GRB_MI355X_WP_STATIC", WP_STATIC_PCT), D.wp_nhot, D.wp_nwarm};
   with_semiring<T>(d, [&](auto sr) {
     typedef decltype(sr) SR;
     hipLaunchKernelGGL((k_spmv_wavepipe<T, SR>), dim3(ncu * WP_WGS_PER_CU), dim3(WP_WAVES * 64), 0, stream(), a, sr);
-    hipLaunchKernelGGL((k_spmv_wavepipe_fixup<T, SR>), dim3((nwaves + 255) / 256), dim3(256), 0, stream(), M.wp_carry.as<WpCarry<T>>(), nwaves, (T*)c.tval, c.tpres,
+    hipLaunchKernelGGL((k_spmv_wavepipe_fixup<T, SR>), dim3((nwaves + 255) / 256), dim3(256), 0, stream(), D.wp_carry.as<WpCarry<T>>(), nwaves, (T*)c.tval, c.tpres,
                        (const WpArgs<T>*)nullptr, sr);
-    g_last_plan += std::string("k_spmv_wavepipe<") + (sr.is_static ? "static" : "dynamic") + ",hot=" + std::to_string(M.wp_nhot) + "> ";
+    g_last_plan += std::string("k_spmv_wavepipe<") + (sr.is_static ? "static" : "dynamic") + ",hot=" + std::to_string(D.wp_nhot) + "> ";
   });
   return true;
 }

@@ -817,10 +817,10 @@ template <class T> static __global__ void k_xt_narrow16(const T* __restrict__ v,
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) out[i] = (int16_t)v[i];
 }
 
-template <class T> void build_xcd_plan(DevCSR& M, int ncu, bool with_vals, int force_S = 0) {
+template <class T> void build_xcd_plan(const DevCSR& M, int ncu, bool with_vals, int force_S = 0) {
   auto grid_n = [](uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 8192) b = 8192; return (unsigned)b; };
   hipEvent_t ev0, ev1; GRB_HIP(hipEventCreate(&ev0)); GRB_HIP(hipEventCreate(&ev1)); GRB_HIP(hipEventRecord(ev0, stream()));
-  auto* P = new XcdPlan(); M.xcd.reset(P);
+  auto* P = new XcdPlan(); M.derived.xcd.reset(P);
   const uint32_t n = M.ncols; const uint64_t nnz = M.nnz;
   constexpr uint32_t H = xt_hot<T>::H;
   const bool sell = xp_sell_wanted<T>();
@@ -1155,13 +1155,13 @@ template <class T> void build_xcd_plan(DevCSR& M, int ncu, bool with_vals, int f
 }
 
 template <class T> bool run_xcd(const SpmvCall& c, const SemiringDesc& d, int ncu) {
-  DevCSR& M = *c.M;
+  const DevCSR& M = *c.M;
   if (ncu < XP || ncu % XP) return false;
   if ((uint64_t)M.ncols > xt_hot<T>::MAXCOLS) return false;        // a column must fit a code word (16-bit plane: 2^29 columns and more go to kernel W)
   const bool need_vals = c.aval != nullptr;
   if (need_vals && c.aval != M.val.p) return false;   // the plan's panel-major values are a copy of the stored ones (no typecast)
-  auto* P = static_cast<XcdPlan*>(M.xcd.get());
-  if (!P || P->tsize != (int)sizeof(T) || (need_vals && !P->has_vals)) { build_xcd_plan<T>(M, ncu, need_vals); P = static_cast<XcdPlan*>(M.xcd.get()); }
+  auto* P = static_cast<XcdPlan*>(M.derived.xcd.get());
+  if (!P || P->tsize != (int)sizeof(T) || (need_vals && !P->has_vals)) { build_xcd_plan<T>(M, ncu, need_vals); P = static_cast<XcdPlan*>(M.derived.xcd.get()); }
   const bool uses_u = d.flip ? binop_uses_x(d.mulop) : binop_uses_y(d.mulop);
   constexpr uint32_t H = xt_hot<T>::H;
   XtCall<T> call{(const T*)c.uval, M.ncols, (uint32_t)(P->NS / XP), P->partial.as<T>()};
