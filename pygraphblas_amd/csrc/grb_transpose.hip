@@ -9,6 +9,7 @@
 #include "grb_api.hpp"
 #include "grb_index.hpp"
 #include "grb_matops.hpp"
+#include "grb_build.hpp"
 
 namespace grb {
 namespace {
@@ -35,6 +36,12 @@ template <int TS> __global__ void k_gather_perm(const uint32_t* __restrict__ per
 
 }  // namespace
 
+// (also the last step of build-from-tuples, grb_build.hip: the rows of the run heads are sorted keys too)
+void rowptr_from_sorted(const uint32_t* keys, uint64_t n, uint32_t nkeys, uint32_t* rowptr) {
+  if (!n) { GRB_HIP(hipMemsetAsync(rowptr, 0, ((size_t)nkeys + 1) * 4, stream())); return; }      // (no key: one thread would write every word)
+  hipLaunchKernelGGL(k_rowptr_from_sorted, dim3(grid_1d(n + 1)), dim3(256), 0, stream(), keys, n, nkeys, rowptr);
+}
+
 void csr_transpose(const DevCSR& A, size_t ts, DevCSR& At) {
   At.clear();
   At.nrows = A.ncols; At.ncols = A.nrows; At.nnz = A.nnz;
@@ -47,7 +54,7 @@ void csr_transpose(const DevCSR& A, size_t ts, DevCSR& At) {
     fill_iota_u32(perm_in.as<uint32_t>(), nnz);
     int bits = 1; while (bits < 32 && (1ull << bits) < (uint64_t)A.ncols) bits++;
     sort_pairs_u32(A.col.as<uint32_t>(), keys_out.as<uint32_t>(), perm_in.as<uint32_t>(), perm.as<uint32_t>(), nnz, bits);
-    hipLaunchKernelGGL(k_rowptr_from_sorted, dim3(grid_1d(nnz + 1)), dim3(256), 0, stream(), keys_out.as<uint32_t>(), nnz, At.nrows, At.rowptr.as<uint32_t>());
+    rowptr_from_sorted(keys_out.as<uint32_t>(), nnz, At.nrows, At.rowptr.as<uint32_t>());
     dispatch_value_size(ts, [&]<int TS>() {
       hipLaunchKernelGGL((k_gather_perm<TS>), dim3(grid_1d(nnz)), dim3(256), 0, stream(), perm.as<uint32_t>(), nnz, rowidx.as<uint32_t>(), A.val.as<uint8_t>(), At.col.as<uint32_t>(), At.val.as<uint8_t>());
     });

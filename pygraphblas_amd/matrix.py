@@ -60,6 +60,32 @@ def build_range(rslice, stop_val):
     return _p(keep), ni, size, keep
 
 
+def _tensor_tuples(typ, indices, V):
+    """(type, [index pointers..., value pointer], n, location) of the torch tensors of a `from_tensors` call: all on one device, contiguous, int64 indices
+    (non-negative: read as the 64-bit unsigned indices of the C ABI), values of the type's dtype.  location 1 = HBM pointers, 0 = host pointers."""
+    import torch
+    by_dtype = {str(np.dtype(t._np)): t for t in (types.BOOL, types.INT8, types.UINT8, types.INT16, types.UINT16, types.INT32, types.UINT32, types.INT64,
+                                                  types.UINT64, types.FP32, types.FP64)}
+    name = str(V.dtype).replace("torch.", "")
+    if typ is None:
+        if name not in by_dtype:
+            raise TypeError(f"no GraphBLAS type for tensors of dtype {V.dtype}")
+        typ = by_dtype[name]
+    if name != str(np.dtype(typ._np)):
+        raise TypeError(f"values of dtype {V.dtype} for a {typ.__name__} container: from_tensors does not cast (use V.to(...) first)")
+    n = int(V.numel())
+    for t in tuple(indices) + (V,):
+        if t.device != V.device or not t.is_contiguous() or t.dim() != 1 or int(t.numel()) != n:
+            raise ValueError("from_tensors takes contiguous one-dimensional tensors of one length on one device")
+    for t in indices:
+        if t.dtype != torch.int64:
+            raise TypeError("from_tensors takes int64 index tensors")
+    on_gpu = V.device.type == "cuda"
+    if on_gpu:
+        torch.cuda.current_stream(V.device).synchronize()      # whatever produced the tensors has finished before the library's stream reads them
+    return typ, [C.c_void_p(t.data_ptr()) for t in tuple(indices) + (V,)], n, 1 if on_gpu else 0
+
+
 _diag_min = None
 
 
@@ -137,6 +163,15 @@ class Matrix:
         I = np.ascontiguousarray(I, np.uint64); J = np.ascontiguousarray(J, np.uint64); V = np.ascontiguousarray(V, typ._np)
         fn = getattr(lib, "GrB_Matrix_build_" + typ.__name__)
         check(fn(m._h, _p(I), _p(J), _p(V), u64(len(I)), C.c_void_p(dup.get_op()) if dup is not None else None), m)
+        return m
+
+    @classmethod
+    def from_tensors(cls, I, J, V, nrows, ncols, typ=None, dup=None):
+        """Bulk build from contiguous torch tensors (int64 indices, V of the type's dtype) through GrBX_Matrix_build_at.  Tensors that live on the GPU are read where
+        they are: on the device route (large builds, see GrBX_build_thresholds) the tuples never visit the host.  CPU tensors are host arrays, as in from_arrays."""
+        typ, args, n, location = _tensor_tuples(typ, (I, J), V)
+        m = cls.sparse(typ, nrows, ncols)
+        check(lib.GrBX_Matrix_build_at(m._h, args[0], args[1], args[2], u64(n), C.c_void_p(dup.get_op()) if dup is not None else None, location), m)
         return m
 
     # ---- text formats (SURVEY.md §8f rank 3): one numpy parse + one bulk build instead of one setElement per entry -------------

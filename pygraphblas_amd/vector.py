@@ -67,6 +67,16 @@ class Vector:
         return v
 
     @classmethod
+    def from_tensors(cls, I, V, size, typ=None, dup=None):
+        """Bulk build from contiguous torch tensors (int64 indices, V of the type's dtype) through GrBX_Vector_build_at; GPU tensors are read where they are
+        (Matrix.from_tensors)."""
+        from .matrix import _tensor_tuples
+        typ, args, n, location = _tensor_tuples(typ, (I,), V)
+        v = cls.sparse(typ, size)
+        check(lib.GrBX_Vector_build_at(v._h, args[0], args[1], u64(n), C.c_void_p(dup.get_op()) if dup is not None else None, location), v)
+        return v
+
+    @classmethod
     def from_dense_array(cls, values, typ, present=None, device=False):
         """Import a full (or bitmap) vector in one call; `device=True`: `values`/`present` are (HBM address, n)."""
         h = C.c_void_p()

@@ -550,6 +550,11 @@ GrB_Info GrBX_kron_fill_ms(float *milliseconds);   /* device time of k_kron_fill
 GrB_Info GxB_Matrix_diag(GrB_Matrix C, const GrB_Vector v, int64_t k, const GrB_Descriptor desc);   /* Matrix.from_diag, pygraphblas/matrix.py:333-375 */
 GrB_Info GxB_Vector_diag(GrB_Vector v, const GrB_Matrix A, int64_t k, const GrB_Descriptor desc);   /* Matrix.vector_diag, pygraphblas/matrix.py:2225-2277 */
 GrB_Info GrBX_diag_thresholds(uint64_t *matrix_min_entries, uint64_t *vector_min_entries);   /* entries of a host-resident operand from which GxB_Matrix_diag / GxB_Vector_diag take their device route (an operand that lives in HBM only always does) */
+/* build from tuples that may live in HBM: I / J are 64-bit indices, X holds values of the container's own type; location 0 = host arrays,
+   1 = device arrays (read where they are on the device route, downloaded once for the host route).  Same outcomes as GrB_*_build_<T>. */
+GrB_Info GrBX_Matrix_build_at(GrB_Matrix C, const GrB_Index *I, const GrB_Index *J, const void *X, GrB_Index nvals, const GrB_BinaryOp dup, int location);
+GrB_Info GrBX_Vector_build_at(GrB_Vector w, const GrB_Index *I, const void *X, GrB_Index nvals, const GrB_BinaryOp dup, int location);
+GrB_Info GrBX_build_thresholds(uint64_t *out);   /* three words: tuples from which a build takes its device route; the run of duplicates one lane folds; the longest run of an operator that is not exactly associative the device folds (beyond it: host route) */
 GrB_Info GxB_Matrix_apply_BinaryOp1st(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GxB_Scalar x, const GrB_Matrix A, const GrB_Descriptor desc);
 GrB_Info GxB_Matrix_apply_BinaryOp2nd(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GxB_Scalar y, const GrB_Descriptor desc);
 GrB_Info GxB_Vector_apply_BinaryOp1st(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GxB_Scalar x, const GrB_Vector u, const GrB_Descriptor desc);
