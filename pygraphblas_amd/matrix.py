@@ -60,12 +60,47 @@ def build_range(rslice, stop_val):
     return _p(keep), ni, size, keep
 
 
+def _types_by_dtype_name():
+    """dtype name ("float64", "bool", ...: numpy's and torch's names agree) -> the GraphBLAS type stored as that dtype: the map `from_tensors` reads forwards and
+    `to_tensors` backwards."""
+    return {str(np.dtype(t._np)): t for t in (types.BOOL, types.INT8, types.UINT8, types.INT16, types.UINT16, types.INT32, types.UINT32, types.INT64,
+                                              types.UINT64, types.FP32, types.FP64)}
+
+
+def _torch_dtype(typ):
+    """The torch dtype of a type's values (the reverse of _types_by_dtype_name); TypeError for a type without one in the installed torch."""
+    import torch
+    for name, t in _types_by_dtype_name().items():
+        if t is typ:
+            dt = getattr(torch, name, None)
+            if isinstance(dt, torch.dtype):
+                return dt
+            raise TypeError(f"the installed torch has no dtype {name}: no tensors for a {typ.__name__} container")
+    raise TypeError(f"no torch dtype for a {typ.__name__} container")
+
+
+def _tensor_target():
+    """(torch device, location) of the tensors `to_tensors` returns: the library's GPU (GRB_MI355X_DEVICE, else LOCAL_RANK modulo the device count, else 0 — what
+    GrB_init selects) filled through location 1, or the CPU through location 0 when there is no device."""
+    import os
+    import torch
+    if not (_capi.device_info()["ok"] and torch.cuda.is_available()):
+        return torch.device("cpu"), 0
+    dev = os.environ.get("GRB_MI355X_DEVICE")
+    rank = os.environ.get("LOCAL_RANK")
+    index = int(dev) if dev else int(rank) % torch.cuda.device_count() if rank else 0
+    return torch.device("cuda", index), 1
+
+
+def _tensor_ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
 def _tensor_tuples(typ, indices, V):
     """(type, [index pointers..., value pointer], n, location) of the torch tensors of a `from_tensors` call: all on one device, contiguous, int64 indices
     (non-negative: read as the 64-bit unsigned indices of the C ABI), values of the type's dtype.  location 1 = HBM pointers, 0 = host pointers."""
     import torch
-    by_dtype = {str(np.dtype(t._np)): t for t in (types.BOOL, types.INT8, types.UINT8, types.INT16, types.UINT16, types.INT32, types.UINT32, types.INT64,
-                                                  types.UINT64, types.FP32, types.FP64)}
+    by_dtype = _types_by_dtype_name()
     name = str(V.dtype).replace("torch.", "")
     if typ is None:
         if name not in by_dtype:
@@ -435,10 +470,41 @@ class Matrix:
         I, J, X = self.to_arrays()
         return [I.tolist(), J.tolist(), X.tolist()]
 
+    def to_tensors(self, values=True):
+        """(I, J, V) — `values=False`: (I, J) — as contiguous torch tensors on the library's GPU: int64 indices, V of the type's dtype, row-major with ascending
+        columns inside a row, bit for bit what to_arrays returns.  Filled in HBM through GrBX_Matrix_extractTuples_at (grb_tuples.hip): a matrix that lives there
+        is expanded where it is and no host mirror is built.  Without a GPU: CPU tensors.  `Matrix.from_tensors(*A.to_tensors(), nrows, ncols)` reproduces A."""
+        import torch
+        vdt = _torch_dtype(self.type) if values else None
+        dev, location = _tensor_target()
+        n = self.nvals
+        I, J = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+        V = torch.empty(n, dtype=vdt, device=dev) if values else None
+        if n:
+            if location:
+                torch.cuda.current_stream(dev).synchronize()
+            nn = u64(n)
+            check(lib.GrBX_Matrix_extractTuples_at(_tensor_ptr(I), _tensor_ptr(J), _tensor_ptr(V), C.byref(nn), self._h, C.c_int(location)), self)
+        return (I, J, V) if values else (I, J)
+
     def to_csr(self):
         n = self.nvals
         rp, ci, x = np.zeros(self.nrows + 1, np.uint32), np.zeros(n, np.uint32), np.zeros(n, self.type._np)
         check(lib.GrBX_Matrix_export_CSR(self._h, _p(rp), _p(ci), _p(x), C.c_int(0)), self)
+        return rp, ci, x
+
+    def to_csr_tensors(self):
+        """(rowptr, colidx, values) as torch tensors on the library's GPU — the library's own CSR layout, copied in HBM by GrBX_Matrix_export_CSR(..., 1): int32
+        row pointers and columns (the bits of the unsigned 32-bit words), values of the type's dtype.  Like to_csr it needs a device: the CSR is the HBM layout."""
+        import torch
+        vdt = _torch_dtype(self.type)
+        dev, location = _tensor_target()
+        n = self.nvals
+        rp, ci = torch.empty(self.nrows + 1, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        x = torch.empty(n, dtype=vdt, device=dev)
+        if location:
+            torch.cuda.current_stream(dev).synchronize()
+        check(lib.GrBX_Matrix_export_CSR(self._h, _tensor_ptr(rp), _tensor_ptr(ci), _tensor_ptr(x), C.c_int(location)), self)
         return rp, ci, x
 
     def to_scipy_sparse(self):

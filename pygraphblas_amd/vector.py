@@ -139,11 +139,44 @@ class Vector:
         I, X = self.to_arrays()
         return [I.tolist(), X.tolist()]
 
+    def to_tensors(self, values=True):
+        """(I, V) — `values=False`: (I,) — as contiguous torch tensors on the library's GPU: int64 indices ascending, V of the type's dtype, bit for bit what
+        to_arrays returns.  Filled in HBM through GrBX_Vector_extractTuples_at (Matrix.to_tensors); a pending deferred chain that writes the vector completes
+        first.  Without a GPU: CPU tensors.  `Vector.from_tensors(*v.to_tensors(), size)` reproduces v."""
+        import torch
+        from .matrix import _torch_dtype, _tensor_target, _tensor_ptr
+        vdt = _torch_dtype(self.type) if values else None
+        dev, location = _tensor_target()
+        n = self.nvals
+        I = torch.empty(n, dtype=torch.int64, device=dev)
+        V = torch.empty(n, dtype=vdt, device=dev) if values else None
+        if n:
+            if location:
+                torch.cuda.current_stream(dev).synchronize()
+            nn = u64(n)
+            check(lib.GrBX_Vector_extractTuples_at(_tensor_ptr(I), _tensor_ptr(V), C.byref(nn), self._h, C.c_int(location)), self)
+        return (I, V) if values else (I,)
+
     def to_dense_arrays(self):
         """(values, present) as dense numpy arrays of length size."""
         n = self.size
         x, p = np.zeros(n, self.type._np), np.zeros(n, np.uint8)
         check(lib.GrBX_Vector_export_Bitmap(self._h, _p(x), _p(p), C.c_int(0)), self)
+        return x, p
+
+    def to_dense_tensors(self):
+        """(values, present) as dense torch tensors of length size on the library's GPU — the library's bitmap layout, copied in HBM by
+        GrBX_Vector_export_Bitmap(..., 1): values of the type's dtype (those of absent positions are unspecified), present as uint8 (non-zero = present).
+        Like to_dense_arrays it needs a device: the bitmap is the HBM layout."""
+        import torch
+        from .matrix import _torch_dtype, _tensor_target, _tensor_ptr
+        vdt = _torch_dtype(self.type)
+        dev, location = _tensor_target()
+        n = self.size
+        x, p = torch.empty(n, dtype=vdt, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+        if location:
+            torch.cuda.current_stream(dev).synchronize()
+        check(lib.GrBX_Vector_export_Bitmap(self._h, _tensor_ptr(x), _tensor_ptr(p), C.c_int(location)), self)
         return x, p
 
     def device_view(self):

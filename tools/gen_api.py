@@ -555,6 +555,12 @@ GrB_Info GrBX_diag_thresholds(uint64_t *matrix_min_entries, uint64_t *vector_min
 GrB_Info GrBX_Matrix_build_at(GrB_Matrix C, const GrB_Index *I, const GrB_Index *J, const void *X, GrB_Index nvals, const GrB_BinaryOp dup, int location);
 GrB_Info GrBX_Vector_build_at(GrB_Vector w, const GrB_Index *I, const void *X, GrB_Index nvals, const GrB_BinaryOp dup, int location);
 GrB_Info GrBX_build_thresholds(uint64_t *out);   /* three words: tuples from which a build takes its device route; the run of duplicates one lane folds; the longest run of an operator that is not exactly associative the device folds (beyond it: host route) */
+/* extractTuples into arrays that may live in HBM: I / J are 64-bit indices, X holds values of the container's own type (no cast); *n is the capacity on entry and
+   nvals on return; any of I / J / X may be NULL (that stream is not written; all NULL: only nvals).  location 0 = host arrays: exactly GrB_*_extractTuples_<own type>;
+   1 = device arrays, filled in HBM (grb_tuples.hip) without a host mirror being built.  *n < nvals with an output: GrB_INSUFFICIENT_SPACE, nothing written. */
+GrB_Info GrBX_Matrix_extractTuples_at(GrB_Index *I, GrB_Index *J, void *X, GrB_Index *n, const GrB_Matrix A, int location);
+GrB_Info GrBX_Vector_extractTuples_at(GrB_Index *I, void *X, GrB_Index *n, const GrB_Vector v, int location);
+GrB_Info GrBX_tuples_geometry(uint64_t *out);   /* out[0] entries per tile of the matrix kernel, out[1] positions per tile of the vector kernel, out[2] the grid cap in workgroups: what the tests take their edges from */
 GrB_Info GxB_Matrix_apply_BinaryOp1st(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GxB_Scalar x, const GrB_Matrix A, const GrB_Descriptor desc);
 GrB_Info GxB_Matrix_apply_BinaryOp2nd(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GxB_Scalar y, const GrB_Descriptor desc);
 GrB_Info GxB_Vector_apply_BinaryOp1st(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GxB_Scalar x, const GrB_Vector u, const GrB_Descriptor desc);
