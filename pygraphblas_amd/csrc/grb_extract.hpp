@@ -13,7 +13,12 @@ struct ExIdx {
   const uint32_t* list = nullptr;     // device copy of an explicit list (uploaded once per call by extract_upload)
   bool increasing = true;             // strictly increasing in k
   std::vector<uint32_t> host;         // the explicit list, narrowed after validation
+  bool hbm = false;                   // the list was parsed where it lay, in HBM (index_parse_device): `host` stays empty, extract_upload has nothing to do
+  DevBuf own;                         // ... and this holds the narrowed list `list` points into
 };
+// An index argument as an entry point received it: (I, n) as in the C API, and whether an explicit list lies in HBM (the GrBX_*_at entry points with location 1,
+// the GrBX_*_Vector entry points) or on the host.  GrB_ALL is GrB_ALL either way.
+struct IdxArg { const GrB_Index* I; GrB_Index n; bool hbm; bool in_hbm() const { return hbm && I != GrB_ALL; } };
 // Validates (I, ni) against `dim` with the errors of expand_index_list (GrB_NULL_POINTER, GrB_INDEX_OUT_OF_BOUNDS, GrB_INVALID_VALUE),
 // ranges in closed form.  dim <= GRB_DIM_DEVICE_MAX.
 inline void extract_parse(ExIdx& x, const GrB_Index* I, GrB_Index ni, uint64_t dim, const char* what) {
@@ -37,6 +42,23 @@ inline void extract_parse(ExIdx& x, const GrB_Index* I, GrB_Index ni, uint64_t d
   uint64_t prev = 0;
   for (uint64_t k = 0; k < ni; k++) { const uint64_t v = I[k]; if (v >= dim) oob(); if (k && v <= prev) x.increasing = false; prev = v; x.host[k] = (uint32_t)v; }
 }
+
+// ---- grb_index.hip: the parse of an explicit list that lies in HBM ----
+// One workgroup of k_index_parse takes INDEX_PARSE_THREADS * INDEX_PARSE_PER_LANE indices per round, the grid is capped at INDEX_PARSE_GRID_CAP workgroups
+// (GrBX_index_geometry reports both: the tests take their edges from them).
+constexpr uint32_t INDEX_PARSE_THREADS = 256, INDEX_PARSE_PER_LANE = 2, INDEX_PARSE_GRID_CAP = 4096;
+inline unsigned index_parse_grid(uint64_t n) {
+  const uint64_t per = (uint64_t)INDEX_PARSE_THREADS * INDEX_PARSE_PER_LANE; uint64_t b = (n + per - 1) / per;
+  if (b < 1) b = 1; if (b > INDEX_PARSE_GRID_CAP) b = INDEX_PARSE_GRID_CAP; return (unsigned)b;
+}
+// extract_parse for `ni` 64-bit indices at the device address I: the same errors (NULL, out of bounds — before anything else of the call is looked at), x.list /
+// x.n / x.increasing from one kernel, nothing downloaded but the status word.  After it returns the caller's array is not read again.
+void index_parse_device(ExIdx& x, const GrB_Index* I, GrB_Index ni, uint64_t dim, const char* what);
+inline void extract_parse(ExIdx& x, const IdxArg& a, uint64_t dim, const char* what) {
+  if (a.in_hbm()) index_parse_device(x, a.I, a.n, dim, what); else extract_parse(x, a.I, a.n, dim, what);
+}
+// out[k] = x[k] as a 64-bit index for n device values of the integer type `code` (signed: sign-extended, so negative values are out of bounds)
+void index_widen(int code, const void* x, uint64_t n, uint64_t* out);
 
 struct ExtractPlan { const char* cols = "all"; bool rowsort = false, transposed = false; uint64_t src_entries = 0; };   // src_entries: entries of the selected rows (read twice)
 

@@ -24,6 +24,7 @@
 #include "grb_kron.hpp"
 #include "grb_diag.hpp"
 #include "grb_matops.hpp"
+#include "grb_tuples.hpp"
 #include <array>
 #include <map>
 
@@ -182,28 +183,41 @@ int route_env(const char* name) { const char* e = getenv(name); return (e && *e)
 bool extract_bisect_env() { const char* e = getenv("GRB_MI355X_EXTRACT_BISECT"); return e && atoi(e) != 0; }
 bool dev_capable(GrB_Matrix A) { return !A || (!is_hyper(A) && A->type->code < T_FC32 && !A->iso_full); }
 bool dev_capable(GrB_Vector v) { return !v || (!is_hyper(v) && v->type->code < T_FC32 && !v->iso_full); }
-bool extract_on_device(GrB_Matrix A, bool others_capable) {
+// `list_in_hbm`: an index list of the call lies in HBM (IdxArg) — the device route wherever it is legal, whatever the entry counts: the list is not downloaded to pick a route
+bool extract_on_device(GrB_Matrix A, bool others_capable, bool list_in_hbm) {
   const int env = route_env("GRB_MI355X_EXTRACT");
   if (env == 0 || !device_ok() || !others_capable || !dev_capable(A) || mat_bitmap_only(A)) return false;
-  if (env == 1) return true;
+  if (env == 1 || list_in_hbm) return true;
   if (A->dev_valid && !A->host_valid) return true;                      // it lives in HBM: it is not downloaded for this
   return A->host_valid && mat_nvals(A) >= EXTRACT_DEVICE_MIN_ENTRIES;   // (the count of a valid host mirror: no device work)
 }
-bool extract_on_device(GrB_Vector u, bool others_capable) {
+bool extract_on_device(GrB_Vector u, bool others_capable, bool list_in_hbm) {
   const int env = route_env("GRB_MI355X_EXTRACT");
   if (env == 0 || !device_ok() || !others_capable || !dev_capable(u)) return false;
-  if (env == 1) return true;
+  if (env == 1 || list_in_hbm) return true;
   vec_gate(u);                                                          // deferred work that involves u is completed first, as every reader does
   if (u->dev_valid && !u->host_valid) return true;
   return u->host_valid && vec_nvals(u) >= EXTRACT_DEVICE_MIN_ENTRIES;
 }
-const char* kind_name(const ExIdx& x) { return x.kind == EX_ALL ? "all" : x.kind == EX_LIST ? "list" : "range"; }
+const char* kind_name(const ExIdx& x) { return x.kind == EX_ALL ? "all" : x.kind == EX_LIST ? (x.hbm ? "list@hbm" : "list") : "range"; }
+// the plan's word for a list that was parsed in HBM (grb_index.hip); nothing for every other index argument, so that host-list calls keep their strings
+std::string parse_name(const ExIdx& x) { return (x.hbm && x.n) ? std::string("k_index_parse<increasing=") + (x.increasing ? "1" : "0") + "> " : std::string(); }
+// The host route of a call whose list lies in HBM: the list is copied down once, and the route's own parse reports what it always reports.
+struct HostList {
+  std::vector<GrB_Index> v;
+  const GrB_Index* get(const IdxArg& a) {
+    if (!a.in_hbm() || !a.I) return a.I;
+    need_device(); v.resize(a.n ? a.n : 1);
+    if (a.n) { GRB_HIP(hipMemcpyAsync(v.data(), a.I, a.n * 8, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream())); }
+    return v.data();
+  }
+};
 
 // The prelude of the two vector-valued extracts (vector_prelude with the index argument parsed first and the accumulator checked before the mask is touched):
 // `idx` over `dim` positions, the checks in the host route's order, the mask as `allow`.  True: nothing may be written — w has been cleared under replace, and
 // the caller returns.
-bool extract_vector_prelude(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const GrB_Index* I, GrB_Index ni, uint64_t dim, const DescView& dv, ExIdx& idx, DevBuf& allow_buf, const uint8_t*& allow) {
-  extract_parse(idx, I, ni, dim, "extract");
+bool extract_vector_prelude(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const IdxArg& ia, uint64_t dim, const DescView& dv, ExIdx& idx, DevBuf& allow_buf, const uint8_t*& allow) {
+  extract_parse(idx, ia, dim, "extract");
   if (w->n != idx.n || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "extract: output size must equal the number of indices");
   if (accum) check_binop(accum, "accum");
   bool nothing = false;
@@ -212,22 +226,22 @@ bool extract_vector_prelude(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, c
   return nothing;
 }
 
-void extract_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, const GrB_Index* I, GrB_Index ni, const DescView& dv) {
+void extract_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, const IdxArg& ia, const DescView& dv) {
   ExIdx idx; DevBuf allow_buf; const uint8_t* allow;
-  if (extract_vector_prelude(w, mask, accum, I, ni, u->n, dv, idx, allow_buf, allow)) return;
+  if (extract_vector_prelude(w, mask, accum, ia, u->n, dv, idx, allow_buf, allow)) return;
   vec_to_device(u);
   const uint64_t n = idx.n; const size_t ts = u->type->size;
   DevBuf keep, tval(n * ts + 8), tpres(n + 1);
   extract_upload(idx, keep);
   extract_vector(ts, u->dval.p, u->dpres.as<uint8_t>(), idx, tval.p, tpres.as<uint8_t>());
   if (keep.p) GRB_HIP(hipStreamSynchronize(stream()));                  // (the uploaded list returns to the pool)
-  g_last_plan = std::string("extract_vector<index=") + kind_name(idx) + "> k_extract_vector ";
+  g_last_plan = std::string("extract_vector<index=") + kind_name(idx) + "> " + parse_name(idx) + "k_extract_vector ";
   vector_write_back(w, u->type->code, tval, tpres, allow, accum, dv.replace, false);
 }
 
-void extract_col_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Matrix A, const GrB_Index* I, GrB_Index ni, GrB_Index j, const DescView& dv, uint64_t ar) {
+void extract_col_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Matrix A, const IdxArg& ia, GrB_Index j, const DescView& dv, uint64_t ar) {
   ExIdx idx; DevBuf allow_buf; const uint8_t* allow;
-  if (extract_vector_prelude(w, mask, accum, I, ni, ar, dv, idx, allow_buf, allow)) return;
+  if (extract_vector_prelude(w, mask, accum, ia, ar, dv, idx, allow_buf, allow)) return;
   mat_to_device(A);
   const uint64_t n = idx.n; const size_t ts = A->type->size;
   DevBuf keep, tval(n * ts + 8), tpres(n + 1);
@@ -236,13 +250,12 @@ void extract_col_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_M
   if (keep.p) GRB_HIP(hipStreamSynchronize(stream()));
   const bool scatter = dv.tran0 && idx.kind == EX_ALL;
   g_last_plan = std::string("extract_col<") + (dv.tran0 ? "row of the CSR" : "column of the CSR") + ",index=" + kind_name(idx) + "> " +
-                (scatter ? "k_extract_row_scatter " : "k_extract_lookup ");
+                parse_name(idx) + (scatter ? "k_extract_row_scatter " : "k_extract_lookup ");
   vector_write_back(w, A->type->code, tval, tpres, allow, accum, dv.replace, false);
 }
 
-void extract_matrix_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, const DescView& dv,
-                           uint64_t ar, uint64_t ac) {
-  ExIdx ri, ci; extract_parse(ri, I, ni, ar, "extract"); extract_parse(ci, J, nj, ac, "extract");
+void extract_matrix_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_Matrix A, const IdxArg& ia, const IdxArg& ja, const DescView& dv, uint64_t ar, uint64_t ac) {
+  ExIdx ri, ci; extract_parse(ri, ia, ar, "extract"); extract_parse(ci, ja, ac, "extract");
   if (C->nrows != ri.n || C->ncols != ci.n || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "extract: output shape must be |I| x |J|");
   if (accum) check_binop(accum, "accum");
   if (!Mask && dv.mask_comp) { if (dv.replace) GrB_Matrix_clear(C); return; }      // no mask + complement: nothing may be written
@@ -253,20 +266,22 @@ void extract_matrix_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, Gr
   ExtractPlan plan; DevCSR T, Tt;
   extract_csr(A->csr, ts, dv.tran0 ? ci : ri, dv.tran0 ? ri : ci, extract_bisect_env(), T, plan);
   if (dv.tran0) { csr_transpose(T, ts, Tt); T.clear(); }
-  g_last_plan = std::string("extract_matrix<cols=") + plan.cols + ",rowsort=" + (plan.rowsort ? "1" : "0") + ",transpose=" + (dv.tran0 ? "1" : "0") + "> k_extract_rows<count> k_extract_rows<fill> ";
+  g_last_plan = std::string("extract_matrix<cols=") + plan.cols + ",rowsort=" + (plan.rowsort ? "1" : "0") + ",transpose=" + (dv.tran0 ? "1" : "0") + (ri.hbm ? ",rows=list@hbm" : "") + (ci.hbm ? ",columns=list@hbm" : "") + "> " +
+                parse_name(ri) + parse_name(ci) + "k_extract_rows<count> k_extract_rows<fill> ";
   matrix_write_back(C, dv.tran0 ? Tt : T, A->type->code, Mask, dv, accum, false);
 }
 
 }  // namespace
 
-extern "C" {
-
-GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, const GrB_Descriptor desc) {
+// The seven index-list operations, each once for both kinds of list: GrB_<name> passes a host list (or GrB_ALL, or a range triple), GrBX_<name>_at with
+// location 1 and the GrBX_*_Vector entry points pass a list that lies in HBM (IdxArg).
+static GrB_Info vector_extract_any(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const IdxArg& ia, const GrB_Descriptor desc) {
   if (!w || !u) return GrB_NULL_POINTER; if (!check_obj(w)) return GrB_UNINITIALIZED_OBJECT;
   return guarded(w, [&] {
     check_v(u, "extract"); if (mask) check_v(mask, "extract");
     const DescView dv(desc);
-    if (extract_on_device(u, dev_capable(w) && dev_capable(mask))) { extract_vector_device(w, mask, accum, u, I, ni, dv); return; }
+    if (extract_on_device(u, dev_capable(w) && dev_capable(mask), ia.in_hbm())) { extract_vector_device(w, mask, accum, u, ia, dv); return; }
+    HostList hl; const GrB_Index* I = hl.get(ia); const GrB_Index ni = ia.n;
     const Sel idx(I, ni, u->n, "extract");
     if (w->n != idx.size() || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "extract: output size must equal the number of indices");
     Map U = load(u), T, C = load(w), Mm; if (mask) Mm = load(mask);
@@ -277,14 +292,15 @@ GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
   });
 }
 
-GrB_Info GrB_Col_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc) {
+static GrB_Info col_extract_any(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Matrix A, const IdxArg& ia, GrB_Index j, const GrB_Descriptor desc) {
   if (!w || !A) return GrB_NULL_POINTER; if (!check_obj(w)) return GrB_UNINITIALIZED_OBJECT;
   return guarded(w, [&] {
     check_m(A, "extract"); if (mask) check_v(mask, "extract");
     const DescView dv(desc);
     const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
     if (j >= ac) fail(GrB_INVALID_INDEX, "extract: column index out of range");
-    if (extract_on_device(A, dev_capable(w) && dev_capable(mask))) { extract_col_device(w, mask, accum, A, I, ni, j, dv, ar); return; }
+    if (extract_on_device(A, dev_capable(w) && dev_capable(mask), ia.in_hbm())) { extract_col_device(w, mask, accum, A, ia, j, dv, ar); return; }
+    HostList hl; const GrB_Index* I = hl.get(ia); const GrB_Index ni = ia.n;
     const Sel idx(I, ni, ar, "extract");
     if (w->n != idx.size() || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "extract: output size must equal the number of indices");
     const Line col = line_of(A, dv.tran0, j);                             // (index in op(A)'s column j, value), sorted
@@ -299,14 +315,14 @@ GrB_Info GrB_Col_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp
   });
 }
 
-GrB_Info GrB_Matrix_extract(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj,
-                            const GrB_Descriptor desc) {
+static GrB_Info matrix_extract_any(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const IdxArg& ia, const IdxArg& ja, const GrB_Descriptor desc) {
   if (!C || !A) return GrB_NULL_POINTER; if (!check_obj(C)) return GrB_UNINITIALIZED_OBJECT;
   return guarded(C, [&] {
     check_m(A, "extract"); if (Mask) check_m(Mask, "extract");
     const DescView dv(desc);
     const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
-    if (extract_on_device(A, dev_capable(C) && dev_capable(Mask))) { extract_matrix_device(C, Mask, accum, A, I, ni, J, nj, dv, ar, ac); return; }
+    if (extract_on_device(A, dev_capable(C) && dev_capable(Mask), ia.in_hbm() || ja.in_hbm())) { extract_matrix_device(C, Mask, accum, A, ia, ja, dv, ar, ac); return; }
+    HostList hli, hlj; const GrB_Index* I = hli.get(ia); const GrB_Index* J = hlj.get(ja); const GrB_Index ni = ia.n, nj = ja.n;
     const Sel ri(I, ni, ar, "extract"), ci(J, nj, ac, "extract");
     if (C->nrows != ri.size() || C->ncols != ci.size() || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "extract: output shape must be |I| x |J|");
     if (!Mask && !dv.mask_comp && !accum && ri.increasing() && ci.increasing()) {       // a slice `A[a:b, c:d]` into a fresh output: one pass over A's tuples
@@ -343,7 +359,6 @@ GrB_Info GrB_Matrix_extract(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binar
 }
 
 // ---- assign: C(I,J)<M> = accum(C(I,J), A) --------------------------------------------------------------------------------------
-}  // extern "C"
 namespace {
 // the region update: positions of the index grid take A's entry (or lose theirs), combined with accum when given
 void region_update(Map& C, int ccode, const Map& A, int acode, const std::vector<uint64_t>& ri, const std::vector<uint64_t>& ci, GrB_BinaryOp accum, const MaskView& mk, bool replace,
@@ -389,17 +404,18 @@ constexpr uint64_t ASSIGN_COL_DEVICE_MIN_ENTRIES = 100000;       // GrB_Col_assi
 constexpr uint64_t ASSIGN_VEC_DEVICE_MIN_ENTRIES = 500;          // GrB_Vector_assign: the host route is map-based for every shape (the smallest size measured; the device route won all)
 uint64_t entries_known(GrB_Vector u) { return u->host_valid ? vec_nvals(u) : (u->facts.dnvals_known ? u->facts.dnvals : 0); }      // (no device work for a count)
 // `operand_entries`: asked only after the variable, the device and the residency of C have not decided
-template <class F> bool assign_on_device(GrB_Matrix C, bool others_capable, uint64_t min_entries, F&& operand_entries) {
+// `list_in_hbm`: as for extract — the device route wherever it is legal
+template <class F> bool assign_on_device(GrB_Matrix C, bool others_capable, uint64_t min_entries, F&& operand_entries, bool list_in_hbm) {
   const int env = route_env("GRB_MI355X_ASSIGN");
   if (env == 0 || !device_ok() || !others_capable || !dev_capable(C) || mat_bitmap_only(C)) return false;
-  if (env == 1) return true;
+  if (env == 1 || list_in_hbm) return true;
   if (C->dev_valid && !C->host_valid) return true;                      // it lives in HBM: it is not downloaded for this
   return mat_nvals(C) >= min_entries || operand_entries() >= min_entries;
 }
-template <class F> bool assign_on_device(GrB_Vector w, bool others_capable, uint64_t min_entries, F&& operand_entries) {
+template <class F> bool assign_on_device(GrB_Vector w, bool others_capable, uint64_t min_entries, F&& operand_entries, bool list_in_hbm) {
   const int env = route_env("GRB_MI355X_ASSIGN");
   if (env == 0 || !device_ok() || !others_capable || !dev_capable(w)) return false;
-  if (env == 1) return true;
+  if (env == 1 || list_in_hbm) return true;
   if (w->dev_valid && !w->host_valid) return true;
   return entries_known(w) >= min_entries || operand_entries() >= min_entries;
 }
@@ -421,8 +437,8 @@ void region_replace(GrB_Matrix C, GrB_Matrix Mask, const DescView& dv, DevCSR& T
   matrix_write_back(C, Z, ccode, Mask, dv, nullptr, false);
 }
 
-bool assign_matrix_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, const DescView& dv) {
-  ExIdx ri, ci; extract_parse(ri, I, ni, C->nrows, "assign"); extract_parse(ci, J, nj, C->ncols, "assign");
+bool assign_matrix_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_Matrix A, const IdxArg& ia, const IdxArg& ja, const DescView& dv) {
+  ExIdx ri, ci; extract_parse(ri, ia, C->nrows, "assign"); extract_parse(ci, ja, C->ncols, "assign");
   const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
   if (ar != ri.n || ac != ci.n || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "assign: the matrix must be |I| x |J|");
   if (accum) check_binop(accum, "accum");
@@ -434,7 +450,7 @@ bool assign_matrix_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB
   DevCSR T; AssignPlan plan;
   assign_relocate(Ad, A->type->size, ri, ci, (uint32_t)C->nrows, (uint32_t)C->ncols, T, plan);
   g_last_plan = std::string("assign_matrix<rows=") + kind_name(ri) + ",cols=" + kind_name(ci) + ",rowsort=" + (plan.rowsort ? "1" : "0") + ",transpose=" + (dv.tran0 ? "1" : "0") + ",accum=" + accum_name(accum) +
-                "> k_assign_rowlen k_assign_move " + (accum ? "" : "k_assign_region_keep ");
+                "> " + parse_name(ri) + parse_name(ci) + "k_assign_rowlen k_assign_move " + (accum ? "" : "k_assign_region_keep ");
   if (accum) matrix_write_back(C, T, A->type->code, Mask, dv, accum, false);      // accum(C, T) on the union of the patterns: entries of C inside the region that A lacks are kept
   else region_replace(C, Mask, dv, T, A->type->code, ri, inv_i, ci, inv_j);
   return true;
@@ -455,8 +471,8 @@ void line_assign(int lcode, uint64_t n, void* lval, uint8_t* lpres, const uint8_
   GRB_HIP(hipStreamSynchronize(stream()));                              // (the cast copies return to the pool)
 }
 
-bool assign_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, const GrB_Index* I, GrB_Index ni, const DescView& dv) {
-  ExIdx idx; extract_parse(idx, I, ni, w->n, "assign");
+bool assign_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, const IdxArg& ia, const DescView& dv) {
+  ExIdx idx; extract_parse(idx, ia, w->n, "assign");
   if (u->n != idx.n || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "assign: the vector's size must equal the number of indices");
   if (accum) check_binop(accum, "accum");
   DevBuf keep, inv; extract_upload(idx, keep);
@@ -466,15 +482,15 @@ bool assign_vector_device(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB
   vec_to_device(u); vec_to_device(w);
   line_assign(w->type->code, w->n, w->dval.p, w->dpres.as<uint8_t>(), allow, idx, inv, u, accum, dv.replace);
   vec_invalidate_host(w);
-  g_last_plan = std::string("assign_vector<index=") + kind_name(idx) + ",accum=" + accum_name(accum) + "> k_assign_vector ";
+  g_last_plan = std::string("assign_vector<index=") + kind_name(idx) + ",accum=" + accum_name(accum) + "> " + parse_name(idx) + "k_assign_vector ";
   return true;
 }
 
 // C(i, J) = u (`is_row`) or C(I, j) = u: the line of C as a bitmap, the vector kernel on it under the vector mask, then the line put back as a region of C
-bool assign_line_device(GrB_Matrix C, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, bool is_row, uint64_t fixed, const GrB_Index* L, GrB_Index nl, const DescView& dv) {
+bool assign_line_device(GrB_Matrix C, GrB_Vector mask, GrB_BinaryOp accum, GrB_Vector u, bool is_row, uint64_t fixed, const IdxArg& la, const DescView& dv) {
   const uint64_t len = is_row ? C->ncols : C->nrows;
   const char* const msg = is_row ? "assign: the vector's size must equal the number of column indices" : "assign: the vector's size must equal the number of row indices";
-  ExIdx idx; extract_parse(idx, L, nl, len, "assign");
+  ExIdx idx; extract_parse(idx, la, len, "assign");
   if (u->n != idx.n || (mask && mask->n != len)) fail(GrB_DIMENSION_MISMATCH, msg);
   if (accum) check_binop(accum, "accum");
   if (!len) return false;
@@ -493,7 +509,7 @@ bool assign_line_device(GrB_Matrix C, GrB_Vector mask, GrB_BinaryOp accum, GrB_V
   ExIdx one; one.kind = EX_RANGE; one.lo = (uint32_t)fixed; one.step = 1; one.n = 1;
   const ExIdx& ri = is_row ? one : all; const ExIdx& ci = is_row ? all : one;
   assign_relocate(Tl, cs, ri, ci, (uint32_t)C->nrows, (uint32_t)C->ncols, T, plan);
-  g_last_plan = std::string(is_row ? "assign_row<index=" : "assign_col<index=") + kind_name(idx) + ",accum=" + accum_name(accum) + "> " + (is_row ? "k_extract_row_scatter" : "k_extract_lookup") +
+  g_last_plan = std::string(is_row ? "assign_row<index=" : "assign_col<index=") + kind_name(idx) + ",accum=" + accum_name(accum) + "> " + parse_name(idx) + (is_row ? "k_extract_row_scatter" : "k_extract_lookup") +
                 " k_assign_vector k_assign_line_fill k_assign_move k_assign_region_keep ";
   const DevBuf none_i, none_j;
   region_replace(C, nullptr, DescView(nullptr), T, ccode, ri, none_i, ci, none_j);
@@ -543,17 +559,17 @@ void kron_device(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, GrB_BinaryOp
 // the whole-container fast paths forward to eWiseAdd without the caller's descriptor: only when it asks for nothing they would
 // drop (a complemented mask without a mask object allows no writes at all; an invalid descriptor is the general path's error)
 static inline bool plain_desc(GrB_Descriptor d) { return !d || (check_obj(d) && (d->mask & GrB_COMP) == 0); }
-extern "C" {
 
-GrB_Info GrB_Vector_assign(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, const GrB_Descriptor desc) {
+static GrB_Info vector_assign_any(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const IdxArg& ia, const GrB_Descriptor desc) {
+  const GrB_Index* const I = ia.I;
   if (!w || !u) return GrB_NULL_POINTER; if (!check_obj(w)) return GrB_UNINITIALIZED_OBJECT;
   if (I == GrB_ALL && !mask && plain_desc(desc) && accum && check_obj(u) && device_ok() && u->n == w->n) return GrB_Vector_eWiseAdd_BinaryOp(w, nullptr, nullptr, accum, w, u, nullptr);   // w = accum(w, u), in HBM
   return guarded(w, [&] {
     check_v(u, "assign"); if (mask) check_v(mask, "assign");
     const DescView dv(desc);
     vec_gate(w); vec_gate(u);                                            // deferred work that involves them is completed first, as every reader does
-    if (u != w && (mask || !dv.mask_comp) && assign_on_device(w, dev_capable(u) && dev_capable(mask), ASSIGN_VEC_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }) && assign_vector_device(w, mask, accum, u, I, ni, dv)) return;
-    const auto idx = indices(I, ni, w->n, "assign");
+    if (u != w && (mask || !dv.mask_comp) && assign_on_device(w, dev_capable(u) && dev_capable(mask), ASSIGN_VEC_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }, ia.in_hbm()) && assign_vector_device(w, mask, accum, u, ia, dv)) return;
+    HostList hl; const auto idx = indices(hl.get(ia), ia.n, w->n, "assign");
     if (u->n != idx.size() || (mask && mask->n != w->n)) fail(GrB_DIMENSION_MISMATCH, "assign: the vector's size must equal the number of indices");
     Map C = load(w), U = load(u), Mm; if (mask) Mm = load(mask);
     region_update(C, w->type->code, U, u->type->code, idx, std::vector<uint64_t>{0}, accum, MaskView{&Mm, mask ? mask->type->code : 0, dv.mask_struct, dv.mask_comp, mask != nullptr}, dv.replace,
@@ -562,8 +578,8 @@ GrB_Info GrB_Vector_assign(GrB_Vector w, const GrB_Vector mask, const GrB_Binary
   });
 }
 
-GrB_Info GrB_Matrix_assign(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj,
-                           const GrB_Descriptor desc) {
+static GrB_Info matrix_assign_any(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const IdxArg& ia, const IdxArg& ja, const GrB_Descriptor desc) {
+  const GrB_Index* const I = ia.I; const GrB_Index* const J = ja.I;
   if (!C || !A) return GrB_NULL_POINTER; if (!check_obj(C)) return GrB_UNINITIALIZED_OBJECT;
   // the whole container, no mask, with an accumulator (`paths.assign_matrix(frontier, accum=PLUS)`, gap/bcmark.py:41): that is
   // C = accum(C, A) on the union of the patterns — the eWiseAdd kernel, in HBM (a dense ns x n `paths` must not visit the host)
@@ -574,8 +590,8 @@ GrB_Info GrB_Matrix_assign(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binary
   return guarded(C, [&] {
     check_m(A, "assign"); if (Mask) check_m(Mask, "assign");
     const DescView dv(desc);
-    if (A != C && (Mask || !dv.mask_comp) && assign_on_device(C, mat_capable(A) && mat_capable(Mask), ASSIGN_DEVICE_MIN_ENTRIES, [&] { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }) && assign_matrix_device(C, Mask, accum, A, I, ni, J, nj, dv)) return;
-    const auto ri = indices(I, ni, C->nrows, "assign"), ci = indices(J, nj, C->ncols, "assign");
+    if (A != C && (Mask || !dv.mask_comp) && assign_on_device(C, mat_capable(A) && mat_capable(Mask), ASSIGN_DEVICE_MIN_ENTRIES, [&] { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }, ia.in_hbm() || ja.in_hbm()) && assign_matrix_device(C, Mask, accum, A, ia, ja, dv)) return;
+    HostList hli, hlj; const auto ri = indices(hli.get(ia), ia.n, C->nrows, "assign"), ci = indices(hlj.get(ja), ja.n, C->ncols, "assign");
     const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
     if (ar != ri.size() || ac != ci.size() || (Mask && (Mask->nrows != C->nrows || Mask->ncols != C->ncols))) fail(GrB_DIMENSION_MISMATCH, "assign: the matrix must be |I| x |J|");
     if (!Mask && !dv.mask_comp && !dv.tran0 && C != A && strictly_increasing(ri) && strictly_increasing(ci) && C->type->code < T_FC32 && A->type->code < T_FC32) {
@@ -613,14 +629,15 @@ GrB_Info GrB_Matrix_assign(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binary
   });
 }
 
-GrB_Info GrB_Row_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, GrB_Index i, const GrB_Index* J, GrB_Index nj, const GrB_Descriptor desc) {
+static GrB_Info row_assign_any(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, GrB_Index i, const IdxArg& ja, const GrB_Descriptor desc) {
+  const GrB_Index* const J = ja.I;
   if (!C || !u) return GrB_NULL_POINTER; if (!check_obj(C)) return GrB_UNINITIALIZED_OBJECT;
   return guarded(C, [&] {
     check_v(u, "assign"); if (mask) check_v(mask, "assign");
     const DescView dv(desc);
     if (i >= C->nrows) fail(GrB_INVALID_INDEX, "assign: row index out of range");
     vec_gate(u);
-    if ((mask || !dv.mask_comp) && assign_on_device(C, dev_capable(u) && dev_capable(mask), ASSIGN_ROW_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }) && assign_line_device(C, mask, accum, u, true, i, J, nj, dv)) return;
+    if ((mask || !dv.mask_comp) && assign_on_device(C, dev_capable(u) && dev_capable(mask), ASSIGN_ROW_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }, ja.in_hbm()) && assign_line_device(C, mask, accum, u, true, i, ja, dv)) return;
     if (!mask && !dv.mask_comp && J == GrB_ALL && u->n == C->ncols && C->type->code < T_FC32 && u->type->code < T_FC32) {   // `M[i] = v`: the row's run of tuples is replaced in place (GrB_ALL is never listed: C may be 2^60 wide)
       mat_to_host(C);
       const auto r = row_range(C, i); Line cur; cur.reserve(r.second - r.first);
@@ -629,7 +646,7 @@ GrB_Info GrB_Row_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp 
       return;
     }
     if (J == GrB_ALL && u->n != C->ncols) fail(GrB_DIMENSION_MISMATCH, "assign: the vector's size must equal the number of column indices");   // (before the list is asked for: GrB_ALL over 2^60 columns is never materialised)
-    const auto ci = indices(J, nj, C->ncols, "assign");
+    HostList hl; const auto ci = indices(hl.get(ja), ja.n, C->ncols, "assign");
     if (u->n != ci.size() || (mask && mask->n != C->ncols)) fail(GrB_DIMENSION_MISMATCH, "assign: the vector's size must equal the number of column indices");
     Map Cm = load(C, false), U = load(u), Ut, Mm; if (mask) Mm = load(mask);
     for (auto& kv : U) Ut[{0, kv.first.first}] = kv.second;             // the vector as a 1 x nj row
@@ -639,26 +656,188 @@ GrB_Info GrB_Row_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp 
   });
 }
 
-GrB_Info GrB_Col_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc) {
+static GrB_Info col_assign_any(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const IdxArg& ia, GrB_Index j, const GrB_Descriptor desc) {
+  const GrB_Index* const I = ia.I;
   if (!C || !u) return GrB_NULL_POINTER; if (!check_obj(C)) return GrB_UNINITIALIZED_OBJECT;
   return guarded(C, [&] {
     check_v(u, "assign"); if (mask) check_v(mask, "assign");
     const DescView dv(desc);
     if (j >= C->ncols) fail(GrB_INVALID_INDEX, "assign: column index out of range");
     vec_gate(u);
-    if ((mask || !dv.mask_comp) && assign_on_device(C, dev_capable(u) && dev_capable(mask), ASSIGN_COL_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }) && assign_line_device(C, mask, accum, u, false, j, I, ni, dv)) return;
+    if ((mask || !dv.mask_comp) && assign_on_device(C, dev_capable(u) && dev_capable(mask), ASSIGN_COL_DEVICE_MIN_ENTRIES, [&] { return entries_known(u); }, ia.in_hbm()) && assign_line_device(C, mask, accum, u, false, j, ia, dv)) return;
     if (!mask && !dv.mask_comp && I == GrB_ALL && u->n == C->nrows && C->type->code < T_FC32 && u->type->code < T_FC32) {   // `M[:, j] = v`: one merge pass over the tuples (GrB_ALL is never listed)
       replace_line(C, false, j, assigned_line(line_of(C, false, j), C->type->code, u, accum));
       return;
     }
     if (I == GrB_ALL && u->n != C->nrows) fail(GrB_DIMENSION_MISMATCH, "assign: the vector's size must equal the number of row indices");   // (as in GrB_Row_assign: before the list is asked for)
-    const auto ri = indices(I, ni, C->nrows, "assign");
+    HostList hl; const auto ri = indices(hl.get(ia), ia.n, C->nrows, "assign");
     if (u->n != ri.size() || (mask && mask->n != C->nrows)) fail(GrB_DIMENSION_MISMATCH, "assign: the vector's size must equal the number of row indices");
     Map Cm = load(C, false), U = load(u), Mm; if (mask) Mm = load(mask);
     region_update(Cm, C->type->code, U, u->type->code, ri, std::vector<uint64_t>{j}, accum, MaskView{&Mm, mask ? mask->type->code : 0, dv.mask_struct, dv.mask_comp, mask != nullptr}, dv.replace,
                   false, false, true, j);
     store(C, Cm);
   });
+}
+
+// ---- a vector as an index list: the VALUES of its entries, in index order (what extractTuples returns as X) -----------------------
+// With a device the list is made in HBM and nothing visits the host: the bitmap compaction of grb_tuples.hip (skipped for a vector whose facts say "all
+// present": its value array is the list), then k_index_widen (skipped for the two 64-bit types), then the parse of grb_index.hip like any list in HBM.
+// Without a device, or for an index vector that has no HBM layout, the list is made from the host mirror and the call is the host-list call.
+namespace {
+struct VecList {
+  DevBuf compact, wide; std::vector<GrB_Index> host; std::string kernels;
+  const GrB_Index* I = GrB_ALL; GrB_Index n = 0; bool hbm = false;
+  IdxArg arg() const { return IdxArg{I, n, hbm}; }
+};
+void vector_as_list(GrB_Vector iv, GrB_Vector out, VecList& L) {
+  if (!iv) return;                                                        // no vector: GrB_ALL
+  check_v(iv, "index vector");
+  if (iv == out) fail(GrB_INVALID_VALUE, "the index vector must not be the output");
+  const int code = iv->type->code; const size_t ts = iv->type->size;
+  if (code < T_INT8 || code > T_UINT64) fail(GrB_DOMAIN_MISMATCH, "an index vector must have an integer type");
+  const bool is_signed = code == T_INT8 || code == T_INT16 || code == T_INT32 || code == T_INT64;
+  if (!device_ok() || !dev_capable(iv) || iv->n > GRB_DIM_DEVICE_MAX) {
+    vec_to_host(iv); L.n = iv->hi.size(); L.host.resize(L.n ? L.n : 1);
+    for (GrB_Index k = 0; k < L.n; k++) cast_scalar(is_signed ? T_INT64 : T_UINT64, &L.host[k], code, &iv->hx[k * ts]);      // (sign-extended, then read as unsigned)
+    L.I = L.host.data(); return;
+  }
+  L.hbm = true;
+  vec_to_device(iv);                                                      // deferred work that writes it completes, queued edits are applied, a host-resident vector is uploaded
+  const uint64_t len = iv->n; const void* vals = iv->dval.p;
+  if (len && iv->facts.dnvals_known && iv->facts.dnvals == len) L.n = len;
+  else if (len) {
+    DevBuf offs;
+    L.n = tuples_count_bitmap(iv->dpres.as<uint8_t>(), len, offs);
+    iv->facts.dnvals = L.n; iv->facts.dnvals_known = true;                // (learnt by reading the image, as GrBX_Vector_extractTuples_at records it)
+    L.kernels = "k_tuples_count ";
+    if (L.n) { L.compact.alloc(L.n * ts + 8); tuples_from_bitmap(iv->dpres.as<uint8_t>(), iv->dval.p, ts, len, offs, nullptr, L.compact.p); L.kernels += "k_tuples_scatter "; }
+    GRB_HIP(hipStreamSynchronize(stream()));                              // `offs` goes out of scope
+    vals = L.compact.p;
+  }
+  if (!L.n) { L.wide.alloc(8); L.I = L.wide.as<GrB_Index>(); return; }     // (an empty list still needs an address that is not NULL)
+  if (ts == 8) { L.I = (const GrB_Index*)vals; return; }
+  L.wide.alloc(L.n * 8); index_widen(code, vals, L.n, L.wide.as<uint64_t>()); L.kernels += "k_index_widen ";
+  L.I = L.wide.as<GrB_Index>();
+}
+// The list's own kernels go in front of the operation's in the plan string — only when THIS call wrote one: the plan is set aside before the dispatch, and a
+// call that ended on a host route (which writes none) gets the earlier word back untouched.
+struct VectorListPlan {
+  std::string before;
+  VectorListPlan() { before.swap(g_last_plan); }
+  void done(const VecList& a, const VecList& b) {
+    if (g_last_plan.empty()) { g_last_plan.swap(before); return; }
+    const size_t at = g_last_plan.find("> ");
+    if (at != std::string::npos) g_last_plan.insert(at + 2, a.kernels + b.kernels);
+  }
+};
+bool is_range_code(GrB_Index n) { return n == GXB_RANGE || n == GXB_STRIDE || n == GXB_BACKWARDS; }
+// the `location` of an index argument: 0 a host array (or GrB_ALL, or a range triple), 1 a list of `ni` 64-bit indices in HBM (or GrB_ALL)
+GrB_Info location_ok(int location, const GrB_Index* I, GrB_Index ni) {
+  if (location != 0 && location != 1) return GrB_INVALID_VALUE;
+  if (location == 1 && I != GrB_ALL && is_range_code(ni)) return GrB_INVALID_VALUE;
+  return GrB_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, const GrB_Descriptor desc) {
+  return vector_extract_any(w, mask, accum, u, IdxArg{I, ni, false}, desc);
+}
+GrB_Info GrB_Col_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc) {
+  return col_extract_any(w, mask, accum, A, IdxArg{I, ni, false}, j, desc);
+}
+GrB_Info GrB_Matrix_extract(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj,
+                            const GrB_Descriptor desc) {
+  return matrix_extract_any(C, Mask, accum, A, IdxArg{I, ni, false}, IdxArg{J, nj, false}, desc);
+}
+GrB_Info GrB_Vector_assign(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, const GrB_Descriptor desc) {
+  return vector_assign_any(w, mask, accum, u, IdxArg{I, ni, false}, desc);
+}
+GrB_Info GrB_Matrix_assign(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj,
+                           const GrB_Descriptor desc) {
+  return matrix_assign_any(C, Mask, accum, A, IdxArg{I, ni, false}, IdxArg{J, nj, false}, desc);
+}
+GrB_Info GrB_Row_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, GrB_Index i, const GrB_Index* J, GrB_Index nj, const GrB_Descriptor desc) {
+  return row_assign_any(C, mask, accum, u, i, IdxArg{J, nj, false}, desc);
+}
+GrB_Info GrB_Col_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc) {
+  return col_assign_any(C, mask, accum, u, IdxArg{I, ni, false}, j, desc);
+}
+
+// ---- the same seven with an index list that may lie in HBM: location 0 IS the GrB_ call; location 1: `ni` 64-bit indices at a device address (GrB_ALL is
+// accepted with either value; a range code as the count of a list in HBM is GrB_INVALID_VALUE).  The call takes the device route wherever that route is legal —
+// the entry-count thresholds do not apply, GRB_MI355X_EXTRACT / GRB_MI355X_ASSIGN = 0 still force the host route — and the list is parsed where it lies
+// (grb_index.hip).  Where the device route is not legal (a hypersparse, complex, full one-valued or bitmap-only container, an operand that is the output, an assign
+// whose list names an index twice) the list is copied down once and the host route answers.
+GrB_Info GrBX_Vector_extract_at(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, const GrB_Descriptor desc, int location) {
+  if (!w) return GrB_NULL_POINTER; if (const GrB_Info e = location_ok(location, I, ni)) return e;
+  if (!location) return GrB_Vector_extract(w, mask, accum, u, I, ni, desc);
+  return vector_extract_any(w, mask, accum, u, IdxArg{I, ni, true}, desc);
+}
+GrB_Info GrBX_Col_extract_at(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc, int location) {
+  if (!w) return GrB_NULL_POINTER; if (const GrB_Info e = location_ok(location, I, ni)) return e;
+  if (!location) return GrB_Col_extract(w, mask, accum, A, I, ni, j, desc);
+  return col_extract_any(w, mask, accum, A, IdxArg{I, ni, true}, j, desc);
+}
+GrB_Info GrBX_Matrix_extract_at(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj,
+                                const GrB_Descriptor desc, int location_i, int location_j) {
+  if (!C) return GrB_NULL_POINTER;
+  if (const GrB_Info e = location_ok(location_i, I, ni)) return e; if (const GrB_Info e = location_ok(location_j, J, nj)) return e;
+  if (!location_i && !location_j) return GrB_Matrix_extract(C, Mask, accum, A, I, ni, J, nj, desc);
+  return matrix_extract_any(C, Mask, accum, A, IdxArg{I, ni, location_i == 1}, IdxArg{J, nj, location_j == 1}, desc);
+}
+GrB_Info GrBX_Vector_assign_at(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, const GrB_Descriptor desc, int location) {
+  if (!w) return GrB_NULL_POINTER; if (const GrB_Info e = location_ok(location, I, ni)) return e;
+  if (!location) return GrB_Vector_assign(w, mask, accum, u, I, ni, desc);
+  return vector_assign_any(w, mask, accum, u, IdxArg{I, ni, true}, desc);
+}
+GrB_Info GrBX_Matrix_assign_at(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj,
+                               const GrB_Descriptor desc, int location_i, int location_j) {
+  if (!C) return GrB_NULL_POINTER;
+  if (const GrB_Info e = location_ok(location_i, I, ni)) return e; if (const GrB_Info e = location_ok(location_j, J, nj)) return e;
+  if (!location_i && !location_j) return GrB_Matrix_assign(C, Mask, accum, A, I, ni, J, nj, desc);
+  return matrix_assign_any(C, Mask, accum, A, IdxArg{I, ni, location_i == 1}, IdxArg{J, nj, location_j == 1}, desc);
+}
+GrB_Info GrBX_Row_assign_at(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, GrB_Index i, const GrB_Index* J, GrB_Index nj, const GrB_Descriptor desc, int location) {
+  if (!C) return GrB_NULL_POINTER; if (const GrB_Info e = location_ok(location, J, nj)) return e;
+  if (!location) return GrB_Row_assign(C, mask, accum, u, i, J, nj, desc);
+  return row_assign_any(C, mask, accum, u, i, IdxArg{J, nj, true}, desc);
+}
+GrB_Info GrBX_Col_assign_at(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index* I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc, int location) {
+  if (!C) return GrB_NULL_POINTER; if (const GrB_Info e = location_ok(location, I, ni)) return e;
+  if (!location) return GrB_Col_assign(C, mask, accum, u, I, ni, j, desc);
+  return col_assign_any(C, mask, accum, u, IdxArg{I, ni, true}, j, desc);
+}
+GrB_Info GrBX_index_geometry(uint64_t* out) {
+  if (!out) return GrB_NULL_POINTER;
+  out[0] = (uint64_t)INDEX_PARSE_THREADS * INDEX_PARSE_PER_LANE; out[1] = INDEX_PARSE_GRID_CAP; return GrB_SUCCESS;
+}
+
+// the parse alone (tools/index_probe.py times it): `ni` 64-bit indices in HBM against `dim`, with the errors of the entry points above
+GrB_Info GrBX_index_parse(const GrB_Index* I, GrB_Index ni, GrB_Index dim, int* increasing) {
+  if (!increasing) return GrB_NULL_POINTER;
+  return guarded((GrB_Vector) nullptr, [&] { need_device(); ExIdx x; index_parse_device(x, I, ni, dim, "index parse"); *increasing = x.increasing ? 1 : 0; });
+}
+
+// ---- vectors as index lists (GxB_Vector_extract_Vector / GxB_Vector_assign_Vector / GxB_Matrix_extract_Vector of newer SuiteSparse): a NULL vector means all
+GrB_Info GrBX_Vector_extract_Vector(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Vector Ivec, const GrB_Descriptor desc) {
+  if (!w || !u) return GrB_NULL_POINTER; if (!check_obj(w)) return GrB_UNINITIALIZED_OBJECT;
+  VecList L; if (const GrB_Info e = guarded(w, [&] { vector_as_list(Ivec, w, L); })) return e;
+  VectorListPlan plan; const GrB_Info info = vector_extract_any(w, mask, accum, u, L.arg(), desc);
+  plan.done(L, VecList()); return info;
+}
+GrB_Info GrBX_Vector_assign_Vector(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Vector Ivec, const GrB_Descriptor desc) {
+  if (!w || !u) return GrB_NULL_POINTER; if (!check_obj(w)) return GrB_UNINITIALIZED_OBJECT;
+  VecList L; if (const GrB_Info e = guarded(w, [&] { vector_as_list(Ivec, w, L); })) return e;
+  VectorListPlan plan; const GrB_Info info = vector_assign_any(w, mask, accum, u, L.arg(), desc);
+  plan.done(L, VecList()); return info;
+}
+GrB_Info GrBX_Matrix_extract_Vector(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Vector Ivec, const GrB_Vector Jvec, const GrB_Descriptor desc) {
+  if (!C || !A) return GrB_NULL_POINTER; if (!check_obj(C)) return GrB_UNINITIALIZED_OBJECT;
+  VecList Li, Lj; if (const GrB_Info e = guarded(C, [&] { vector_as_list(Ivec, nullptr, Li); vector_as_list(Jvec, nullptr, Lj); })) return e;
+  VectorListPlan plan; const GrB_Info info = matrix_extract_any(C, Mask, accum, A, Li.arg(), Lj.arg(), desc);
+  plan.done(Li, Lj); return info;
 }
 
 GrB_Info GrB_Matrix_kronecker_BinaryOp(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {

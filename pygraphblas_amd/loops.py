@@ -6,6 +6,10 @@ same stopping rule); nothing here is part of the GraphBLAS API surface.
   bfs(A, start)            demo/Introduction-to-GraphBLAS-with-Python.ipynb:4301-4313  BOOL LOR_LAND  (configs[2])
   sssp(A, start)           demo/Intro-Prez.ipynb:1034-1045; pygraphblas/vector.py:883-885  MIN_PLUS, accum MIN
   triangle_count(L)        demo/TriangleCentrality.ipynb:1446-1449  PLUS_PAIR, mask L                 (configs[3])
+
+and one loop the reference has no driver for, written here because it needs an index list that never leaves HBM:
+
+  connected_components(A)  min-label propagation with one pointer jump per sweep: INT64 MIN_SECOND, accum MIN, then g.extract(g)
 """
 from . import Vector, UINT8, BOOL, FP32, INT64, descriptor as D, last_kernel_plan      # (the package is initialised by the time this submodule is asked for)
 
@@ -74,3 +78,29 @@ def sssp(A, start, plans=None, max_sweeps=None, before_sweep=None):
 
 def triangle_count(L):
     return L.mxm(L, semiring=INT64.PLUS_PAIR, mask=L).reduce_int()
+
+
+def connected_components(A, plans=None):
+    """Every vertex of the symmetric pattern matrix A labelled with the smallest vertex id of its component.  f starts as the vertex ids; a sweep takes the
+    smallest label among a vertex and its neighbours, g = min(f, A min.second f), and then jumps one pointer, g = g(g) — an extract whose index list is the
+    vector itself (GrBX_Vector_extract_Vector: the list is made and parsed in HBM).  Labels only ever decrease, f(v) <= v, and f(v) lies in v's component, so a
+    sweep that changes nothing has reached the component minima.  The jump halves the label chains a long path leaves behind: on a path with shuffled ids it takes
+    about half the sweeps plain propagation needs, and fewer still where small labels sit close together.  Raises after n sweeps without a fixed point (it cannot happen for a symmetric A).  `plans` collects the kernel plan of every
+    jump.  Returns (f, sweeps)."""
+    import torch
+    from .matrix import _tensor_target
+    n = A.nrows
+    ids = torch.arange(n, dtype=torch.int64, device=_tensor_target()[0])
+    f = Vector.from_tensors(ids, ids.clone(), n, INT64)
+    for sweeps in range(1, n + 1):
+        g = f.dup()
+        A.mxv(f, semiring=INT64.MIN_SECOND, out=g, accum=INT64.MIN)
+        g = g.extract(g)
+        if plans is not None:
+            plans.append(last_kernel_plan())
+        if g.iseq(f):
+            return f, sweeps
+        f = g
+    if n == 0:
+        return f, 0
+    raise RuntimeError(f"connected_components: no fixed point after {n} sweeps (is the matrix symmetric?)")

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _capi, types, descriptor as _d
 from ._capi import lib, u64
-from .base import check, NoValue
+from .base import check, NoValue, DomainMismatch
 from .types import current_semiring, current_accum, current_binop, current_monoid
 
 NULL = None
@@ -39,15 +39,70 @@ def get_args(mask, accum, desc):
     return mh, ah, dh
 
 
-def build_range(rslice, stop_val):
+class _IndexArg(tuple):
+    """What build_range returns: the 4-tuple (I pointer, ni, size or None, keep-alive object), and beside it where the list lies — `location` 1: `ni` int64
+    indices in HBM (a GPU tensor), for the GrBX_*_at entry points — or the `vector` whose values are the list, for the GrBX_*_Vector entry points."""
+    def __new__(cls, I, ni, size, keep, location=0, vector=None):
+        self = super().__new__(cls, (I, ni, size, keep))
+        self.location, self.vector = location, vector
+        return self
+
+
+def _is_tensor(x):
+    import sys
+    torch = sys.modules.get("torch")                 # (a tensor cannot exist before torch was imported: no import here)
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def _tensor_index(t):
+    """A torch tensor as an index list: one-dimensional, contiguous, int64.  On the GPU it is read where it is (location 1) once whatever produced it has finished;
+    on the CPU it is a host list."""
+    import torch
+    if t.dtype != torch.int64:
+        raise TypeError(f"an index tensor must be int64, not {t.dtype} (use I.to(torch.int64) first)")
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("an index tensor must be contiguous and one-dimensional")
+    n = int(t.numel())
+    if t.device.type != "cuda" or n == 0:            # (an empty tensor has no address: the empty host list)
+        keep = np.ascontiguousarray(t.cpu().numpy()).view(np.uint64)
+        return _IndexArg(_p(keep), n, n, keep)
+    torch.cuda.current_stream(t.device).synchronize()      # whatever produced the tensor has finished before the library's stream reads it
+    return _IndexArg(C.c_void_p(t.data_ptr()), n, n, t, location=1)
+
+
+def _vector_index_tensor(v):
+    """The values of an index vector as an int64 tensor (for the operations that have no GrBX_*_Vector form): made in HBM by to_tensors."""
+    import torch
+    if v.type not in (types.INT8, types.UINT8, types.INT16, types.UINT16, types.INT32, types.UINT32, types.INT64, types.UINT64):
+        raise DomainMismatch("an index vector must have an integer type")
+    return v.to_tensors()[1].to(torch.int64).contiguous()
+
+
+def _no_device_list(*indices):
+    """Scalar assign takes host lists only."""
+    from .vector import Vector
+    for x in indices:
+        if _is_tensor(x) or isinstance(x, Vector):
+            raise TypeError("scalar assign through a tensor or a vector as the index list is not supported: pass the list as a numpy array")
+
+
+def build_range(rslice, stop_val, vector_ok=False):
     """An index argument of the slicing operations -> (I pointer, ni, size or None, keep-alive array): a list, `None` / `:` for
     all, or a slice — whose `stop` is INCLUSIVE, as in the reference (`_build_range`, pygraphblas/base.py:216-250: GxB_RANGE /
-    GxB_STRIDE / GxB_BACKWARDS index triples)."""
+    GxB_STRIDE / GxB_BACKWARDS index triples).  Also a torch int64 tensor (on the GPU: read in HBM, `.location` 1) and a Vector, whose values are the list
+    (`vector_ok`: the caller has a GrBX_*_Vector entry point and gets `.vector`; otherwise the values become a tensor first)."""
+    from .vector import Vector
+    if isinstance(rslice, Vector):
+        if vector_ok:
+            return _IndexArg(None, 0, rslice.nvals, rslice, vector=rslice)
+        rslice = _vector_index_tensor(rslice)
+    if _is_tensor(rslice):
+        return _tensor_index(rslice)
     if isinstance(rslice, (list, tuple, np.ndarray, range)):
         keep = np.ascontiguousarray(rslice, np.uint64)
-        return _p(keep), len(keep), len(keep), keep
+        return _IndexArg(_p(keep), len(keep), len(keep), keep)
     if rslice is None or rslice == slice(None):
-        return _capi.all_indices(), 0, None, None
+        return _IndexArg(_capi.all_indices(), 0, None, None)
     start = 0 if rslice.start is None else rslice.start
     stop = stop_val if rslice.stop is None else rslice.stop
     step = rslice.step
@@ -57,7 +112,7 @@ def build_range(rslice, stop_val):
         keep, ni, size = np.array([start, stop, -step], np.uint64), _capi.constants["GxB_BACKWARDS"], (0 if start < stop else (start - stop) // -step + 1)
     else:
         keep, ni, size = np.array([start, stop, step], np.uint64), _capi.constants["GxB_STRIDE"], (0 if start > stop or step == 0 else (stop - start) // step + 1)
-    return _p(keep), ni, size, keep
+    return _IndexArg(_p(keep), ni, size, keep)
 
 
 def _types_by_dtype_name():
@@ -570,11 +625,19 @@ class Matrix:
         """`out<mask> = accum(out, op(self)(I, J))` (reference: matrix.py:2807-2900)."""
         t0 = desc is not None and _d.T0 in desc
         nr, nc = (self.ncols, self.nrows) if t0 else (self.nrows, self.ncols)
-        I, ni, isz, k1 = build_range(row_index, nr - 1); J, nj, jsz, k2 = build_range(col_index, nc - 1)
+        from .vector import Vector
+        both = all(x is None or isinstance(x, Vector) for x in (row_index, col_index))      # vectors (or all) on both sides: GrBX_Matrix_extract_Vector; mixed: the vector's values as a tensor
+        ri = build_range(row_index, nr - 1, vector_ok=both); ci = build_range(col_index, nc - 1, vector_ok=both)
+        (I, ni, isz, k1), (J, nj, jsz, k2) = ri, ci
         if out is None:
             out = Matrix.sparse(self.type, nr if isz is None else isz, nc if jsz is None else jsz)
         mh, ah, dh = get_args(mask, accum, desc)
-        check(lib.GrB_Matrix_extract(out._h, mh, ah, self._h, I, u64(ni), J, u64(nj), dh), out)
+        if ri.vector is not None or ci.vector is not None:
+            check(lib.GrBX_Matrix_extract_Vector(out._h, mh, ah, self._h, ri.vector._h if ri.vector is not None else None, ci.vector._h if ci.vector is not None else None, dh), out)
+        elif ri.location or ci.location:
+            check(lib.GrBX_Matrix_extract_at(out._h, mh, ah, self._h, I, u64(ni), J, u64(nj), dh, C.c_int(ri.location), C.c_int(ci.location)), out)
+        else:
+            check(lib.GrB_Matrix_extract(out._h, mh, ah, self._h, I, u64(ni), J, u64(nj), dh), out)
         return out
 
     def extract_col(self, col_index, row_slice=None, out=None, mask=None, accum=None, desc=None):
@@ -582,11 +645,14 @@ class Matrix:
         from .vector import Vector
         t0 = desc is not None and _d.T0 in desc
         length = self.ncols if t0 else self.nrows
-        I, ni, size, keep = build_range(row_slice, length - 1)
+        ix = build_range(row_slice, length - 1); I, ni, size, keep = ix
         if out is None:
             out = Vector.sparse(self.type, length if size is None else size)
         mh, ah, dh = get_args(mask, accum, desc)
-        check(lib.GrB_Col_extract(out._h, mh, ah, self._h, I, u64(ni), u64(col_index), dh), out)
+        if ix.location:
+            check(lib.GrBX_Col_extract_at(out._h, mh, ah, self._h, I, u64(ni), u64(col_index), dh, C.c_int(1)), out)
+        else:
+            check(lib.GrB_Col_extract(out._h, mh, ah, self._h, I, u64(ni), u64(col_index), dh), out)
         return out
 
     def extract_row(self, row_index, col_slice=None, out=None, mask=None, accum=None, desc=None):
@@ -595,15 +661,21 @@ class Matrix:
 
     def assign_col(self, col_index, value, row_slice=None, mask=None, accum=None, desc=None):
         """`self(I, j)<mask> = accum(self(I, j), value)` (reference: matrix.py:3005-3029)."""
-        I, ni, size, keep = build_range(row_slice, self.nrows - 1)
+        ix = build_range(row_slice, self.nrows - 1); I, ni, size, keep = ix
         mh, ah, dh = get_args(mask, accum, desc)
-        check(lib.GrB_Col_assign(self._h, mh, ah, value._h, I, u64(ni), u64(col_index), dh), self)
+        if ix.location:
+            check(lib.GrBX_Col_assign_at(self._h, mh, ah, value._h, I, u64(ni), u64(col_index), dh, C.c_int(1)), self)
+        else:
+            check(lib.GrB_Col_assign(self._h, mh, ah, value._h, I, u64(ni), u64(col_index), dh), self)
 
     def assign_row(self, row_index, value, col_slice=None, mask=None, accum=None, desc=None):
         """`self(i, J)<mask> = accum(self(i, J), value)` (reference: matrix.py:3031-3055)."""
-        J, nj, size, keep = build_range(col_slice, self.ncols - 1)
+        jx = build_range(col_slice, self.ncols - 1); J, nj, size, keep = jx
         mh, ah, dh = get_args(mask, accum, desc)
-        check(lib.GrB_Row_assign(self._h, mh, ah, value._h, u64(row_index), J, u64(nj), dh), self)
+        if jx.location:
+            check(lib.GrBX_Row_assign_at(self._h, mh, ah, value._h, u64(row_index), J, u64(nj), dh, C.c_int(1)), self)
+        else:
+            check(lib.GrB_Row_assign(self._h, mh, ah, value._h, u64(row_index), J, u64(nj), dh), self)
 
     @classmethod
     def from_diag(cls, v, k=0):
@@ -835,8 +907,12 @@ class Matrix:
     def assign_matrix(self, value, rindex=None, cindex=None, mask=None, accum=None, desc=None):
         """`C(I,J)<mask> = accum(C(I,J), value)` (reference: pygraphblas/matrix.py:3057-3130); index lists or None for all."""
         mh, ah, dh = get_args(mask, accum, desc)
-        I, ni, _s1, k1 = build_range(rindex, self.nrows - 1); J, nj, _s2, k2 = build_range(cindex, self.ncols - 1)
-        check(lib.GrB_Matrix_assign(self._h, mh, ah, value._h, I, u64(ni), J, u64(nj), dh), self)
+        ri = build_range(rindex, self.nrows - 1); ci = build_range(cindex, self.ncols - 1)
+        (I, ni, _s1, k1), (J, nj, _s2, k2) = ri, ci
+        if ri.location or ci.location:
+            check(lib.GrBX_Matrix_assign_at(self._h, mh, ah, value._h, I, u64(ni), J, u64(nj), dh, C.c_int(ri.location), C.c_int(ci.location)), self)
+        else:
+            check(lib.GrB_Matrix_assign(self._h, mh, ah, value._h, I, u64(ni), J, u64(nj), dh), self)
 
     assign = assign_matrix
 
@@ -849,6 +925,7 @@ class Matrix:
             row_slice = slice(int(row_slice), int(row_slice))
         if isinstance(col_slice, (int, np.integer)):
             col_slice = slice(int(col_slice), int(col_slice))
+        _no_device_list(row_slice, col_slice)
         I, ni, _s1, k1 = build_range(row_slice, self.nrows - 1); J, nj, _s2, k2 = build_range(col_slice, self.ncols - 1)
         fn = self.type.__dict__.get("_matrix_assign_fn")
         if fn is None:

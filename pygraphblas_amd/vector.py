@@ -191,7 +191,8 @@ class Vector:
 
     def __getitem__(self, i):
         """`v[i]` (element) or `v[a:b]` / `v[[..]]` (sub-vector; a slice includes its stop, as in the reference: vector.py:1526-1547)."""
-        if isinstance(i, (slice, list, tuple, np.ndarray, range)):
+        from .matrix import _is_tensor
+        if isinstance(i, (slice, list, tuple, np.ndarray, range, Vector)) or _is_tensor(i):      # (a tensor or a vector: an index list that stays in HBM)
             return self.extract(i)
         out = self.type._c()
         check(getattr(lib, "GrB_Vector_extractElement_" + self.type.__name__)(C.byref(out), self._h, u64(i)), self)
@@ -200,19 +201,29 @@ class Vector:
     def extract(self, index, out=None, mask=None, accum=None, desc=None):
         """`out<mask> = accum(out, self(I))` (reference: vector.py:1549-1575); a gather kernel when `self` lives in HBM or is large, the host mirror otherwise."""
         from .matrix import build_range
-        I, ni, size, keep = build_range(index, self.size - 1)
+        ix = build_range(index, self.size - 1, vector_ok=True); I, ni, size, keep = ix
         if out is None:
             out = Vector.sparse(self.type, self.size if size is None else size)
         mh, ah, dh = get_args(mask, accum, desc)
-        check(lib.GrB_Vector_extract(out._h, mh, ah, self._h, I, u64(ni), dh), out)
+        if ix.vector is not None:
+            check(lib.GrBX_Vector_extract_Vector(out._h, mh, ah, self._h, ix.vector._h, dh), out)
+        elif ix.location:
+            check(lib.GrBX_Vector_extract_at(out._h, mh, ah, self._h, I, u64(ni), dh, C.c_int(1)), out)
+        else:
+            check(lib.GrB_Vector_extract(out._h, mh, ah, self._h, I, u64(ni), dh), out)
         return out
 
     def assign(self, value, index=None, mask=None, accum=None, desc=None):
         """`self(I)<mask> = accum(self(I), value)` (reference: vector.py:1454-1492)."""
         from .matrix import build_range
-        I, ni, size, keep = build_range(index, self.size - 1)
+        ix = build_range(index, self.size - 1, vector_ok=True); I, ni, size, keep = ix
         mh, ah, dh = get_args(mask, accum, desc)
-        check(lib.GrB_Vector_assign(self._h, mh, ah, value._h, I, u64(ni), dh), self)
+        if ix.vector is not None:
+            check(lib.GrBX_Vector_assign_Vector(self._h, mh, ah, value._h, ix.vector._h, dh), self)
+        elif ix.location:
+            check(lib.GrBX_Vector_assign_at(self._h, mh, ah, value._h, I, u64(ni), dh, C.c_int(1)), self)
+        else:
+            check(lib.GrB_Vector_assign(self._h, mh, ah, value._h, I, u64(ni), dh), self)
 
     def get(self, i, default=None):
         try:
@@ -223,6 +234,8 @@ class Vector:
     def __setitem__(self, index, value):
         if isinstance(value, Vector):
             return self.assign(value, index if not isinstance(index, Vector) else None, mask=index if isinstance(index, Vector) else None)
+        from .matrix import _no_device_list
+        _no_device_list(index if not isinstance(index, Vector) else None)
         if isinstance(index, Vector):                       # `v[q] = level`: scalar assign under the mask q (reference: vector.py:1428-1441)
             return self.assign_scalar(value, mask=index)
         if isinstance(index, slice):
@@ -293,6 +306,8 @@ class Vector:
     # ---- O(n) companions ------------------------------------------------------------------------------------------
     def assign_scalar(self, value, index=None, mask=None, accum=None, desc=None):
         """`w<mask>(:) = accum(w, value)` (reference: vector.py:1494-1524) — `v.assign_scalar(level, mask=q)` in BFS."""
+        from .matrix import _no_device_list
+        _no_device_list(index)
         mh, ah, dh = get_args(mask, accum, desc)
         if index is None:
             I, ni = _capi.all_indices(), 0

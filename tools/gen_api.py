@@ -561,6 +561,24 @@ GrB_Info GrBX_build_thresholds(uint64_t *out);   /* three words: tuples from whi
 GrB_Info GrBX_Matrix_extractTuples_at(GrB_Index *I, GrB_Index *J, void *X, GrB_Index *n, const GrB_Matrix A, int location);
 GrB_Info GrBX_Vector_extractTuples_at(GrB_Index *I, void *X, GrB_Index *n, const GrB_Vector v, int location);
 GrB_Info GrBX_tuples_geometry(uint64_t *out);   /* out[0] entries per tile of the matrix kernel, out[1] positions per tile of the vector kernel, out[2] the grid cap in workgroups: what the tests take their edges from */
+/* index-list extract / assign with a list that may lie in HBM: the arguments of the GrB_ namesake plus the location of each list.  location 0 = a host array, GrB_ALL
+   or a GxB_RANGE / GxB_STRIDE / GxB_BACKWARDS triple: exactly the GrB_ call.  1 = `ni` 64-bit indices at a device address (or GrB_ALL; a range code as the count is
+   GrB_INVALID_VALUE): parsed where they lie (grb_index.hip), the device route wherever it is legal, else the list is copied down once for the host route.
+   Same outcomes as the GrB_ call with the same list on the host. */
+GrB_Info GrBX_Vector_extract_at(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index *I, GrB_Index ni, const GrB_Descriptor desc, int location);
+GrB_Info GrBX_Col_extract_at(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index *I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc, int location);
+GrB_Info GrBX_Matrix_extract_at(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index *I, GrB_Index ni, const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc, int location_i, int location_j);
+GrB_Info GrBX_Vector_assign_at(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index *I, GrB_Index ni, const GrB_Descriptor desc, int location);
+GrB_Info GrBX_Matrix_assign_at(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Index *I, GrB_Index ni, const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc, int location_i, int location_j);
+GrB_Info GrBX_Row_assign_at(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, GrB_Index i, const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc, int location);
+GrB_Info GrBX_Col_assign_at(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index *I, GrB_Index ni, GrB_Index j, const GrB_Descriptor desc, int location);
+/* a vector as an index list: the VALUES of its entries in index order (one of the eight integer types, else GrB_DOMAIN_MISMATCH; signed values are sign-extended
+   and read as unsigned, so a negative value is out of bounds); NULL = all; the output itself as the index vector is GrB_INVALID_VALUE.  The list is made in HBM. */
+GrB_Info GrBX_Vector_extract_Vector(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Vector Ivec, const GrB_Descriptor desc);
+GrB_Info GrBX_Vector_assign_Vector(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Vector Ivec, const GrB_Descriptor desc);
+GrB_Info GrBX_Matrix_extract_Vector(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A, const GrB_Vector Ivec, const GrB_Vector Jvec, const GrB_Descriptor desc);
+GrB_Info GrBX_index_parse(const GrB_Index *I, GrB_Index ni, GrB_Index dim, int *increasing);   /* the parse of a list in HBM alone (bounds against dim, the strictly-increasing flag): what tools/index_probe.py times */
+GrB_Info GrBX_index_geometry(uint64_t *out);   /* out[0] indices one workgroup of the parse kernel takes per round, out[1] its grid cap in workgroups: what the tests take their edges from */
 GrB_Info GxB_Matrix_apply_BinaryOp1st(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GxB_Scalar x, const GrB_Matrix A, const GrB_Descriptor desc);
 GrB_Info GxB_Matrix_apply_BinaryOp2nd(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GxB_Scalar y, const GrB_Descriptor desc);
 GrB_Info GxB_Vector_apply_BinaryOp1st(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GxB_Scalar x, const GrB_Vector u, const GrB_Descriptor desc);
