@@ -14,7 +14,7 @@
 //   traffic  (12 + ts) bytes read and (4 + ts) written per entry of A, 8 bytes per row of C.
 // No atomics anywhere: every output position has exactly one writer.
 #include "grb_assign.hpp"
-#include "grb_index.hpp"
+#include "grb_compact.hpp"
 #include "grb_matops.hpp"
 
 namespace grb {
@@ -84,15 +84,6 @@ __global__ void k_assign_cast_touched(uint64_t n, D* __restrict__ dst, const S* 
 }
 
 // ---- a bitmap as a CSR of one row or one column ------------------------------------------------------------------------------
-__global__ void k_assign_pres_u32(const uint8_t* __restrict__ pres, uint64_t n, uint32_t* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i <= n; i += gridDim.x * 256ull) out[i] = (i < n && pres[i]) ? 1u : 0u;
-}
-template <int TS>
-__global__ void k_assign_line_fill(uint64_t n, const uint8_t* __restrict__ lval, const uint8_t* __restrict__ lpres, const uint32_t* __restrict__ pos, bool as_row, uint32_t* __restrict__ ocol, uint8_t* __restrict__ oval) {
-  typedef typename WordOf<TS>::type W;
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull)
-    if (lpres[i]) { const uint32_t o = pos[i]; ocol[o] = as_row ? (uint32_t)i : 0u; ((W*)oval)[o] = ((const W*)lval)[i]; }
-}
 __global__ void k_assign_two(uint32_t* p, uint32_t total) { if (threadIdx.x == 0 && blockIdx.x == 0) { p[0] = 0; p[1] = total; } }
 
 }  // namespace
@@ -169,17 +160,14 @@ void assign_cast_touched(int dst_code, void* dst, int src_code, const void* src,
 void assign_line_to_csr(size_t ts, uint64_t n, const void* lval, const uint8_t* lpres, bool as_row, DevCSR& T) {
   check_value_size(ts, "assign");
   T.clear(); T.nrows = as_row ? 1u : (uint32_t)n; T.ncols = as_row ? (uint32_t)n : 1u;
-  DevBuf flags((n + 1) * 4), pos_buf;
-  hipLaunchKernelGGL(k_assign_pres_u32, dim3(grid_1d(n + 1)), dim3(256), 0, stream(), lpres, n, flags.as<uint32_t>());
+  DevBuf pos_buf;
   // a column's entry positions ARE its row pointer: the scan goes straight into it
   if (as_row) { pos_buf.alloc((n + 1) * 4); T.rowptr.alloc(8); } else T.rowptr.alloc((n + 1) * 4);
   uint32_t* pos = as_row ? pos_buf.as<uint32_t>() : T.rowptr.as<uint32_t>();
-  exclusive_scan_u32(flags.as<uint32_t>(), pos, n + 1);
-  uint32_t total = 0;
-  GRB_HIP(hipMemcpyAsync(&total, pos + n, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+  const uint32_t total = present_positions_total(lpres, n, pos);
   T.nnz = total; T.col.alloc((size_t)total * 4 + 4); T.val.alloc((size_t)total * ts + 8);
   if (as_row) hipLaunchKernelGGL(k_assign_two, dim3(1), dim3(64), 0, stream(), T.rowptr.as<uint32_t>(), total);
-  if (total) dispatch_value_size(ts, [&]<int TS>() { hipLaunchKernelGGL((k_assign_line_fill<TS>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (const uint8_t*)lval, lpres, pos, as_row, T.col.as<uint32_t>(), T.val.as<uint8_t>()); });
+  if (total) scatter_present(lpres, pos, n, 0, as_row ? COMPACT_COL_INDEX : COMPACT_COL_ZERO, 0, T.col.as<uint32_t>(), ts, lval, T.val.p);
   GRB_HIP(hipStreamSynchronize(stream()));
   T.valid = true;
 }

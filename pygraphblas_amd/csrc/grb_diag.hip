@@ -2,7 +2,7 @@
 // bitmap (behind GxB_Vector_diag); the routes are in grb_host_ops.cpp.  Both are streaming passes: no LDS, no atomics, every output position has one writer.
 //
 //   diag_to_csr         T has at most one entry per row, so its row pointer IS the exclusive scan of v's presence bytes, shifted by the |k| rows before the
-//                       diagonal (k < 0, all 0) and followed by the |k| rows after it (k >= 0, all nnz(T)).  The scan (rocPRIM, over the bytes widened to
+//                       diagonal (k < 0, all 0) and followed by the |k| rows after it (k >= 0, all nnz(T)).  The scan (present_positions: rocPRIM, over the bytes widened to
 //                       32 bits) goes straight into rowptr + row0; nnz(T) is its last word: the one read-back, for the allocation.
 //     k_diag_fill       ENTRY-PARALLEL: a lane owns DIAG_EPL = 4 consecutive positions of v.  It loads their presence bytes as one 4-byte word (nothing
 //                       else when that is 0), the values as one 16-byte pack (two for 8-byte values, a narrower one below 4), the scanned position of the
@@ -18,7 +18,7 @@
 //                       (0 where absent) stored.  Nothing is read back; the entry count stays unknown.
 // Values move as words of their size (1, 2, 4, 8 bytes), never by type: the typecast is the write-back's.
 #include "grb_diag.hpp"
-#include "grb_index.hpp"
+#include "grb_compact.hpp"
 #include <algorithm>
 
 namespace grb {
@@ -30,10 +30,6 @@ constexpr uint32_t DIAG_LINEAR = 8;                                          // 
 template <int TS> struct alignas(TS * DIAG_EPL > 16 ? 16 : TS * DIAG_EPL) ValPack { typename WordOf<TS>::type v[DIAG_EPL]; };
 struct alignas(16) U32Pack { uint32_t c[DIAG_EPL]; };
 struct alignas(4) PresPack { uint8_t b[DIAG_EPL]; };
-
-__global__ void k_diag_pres_u32(const uint8_t* __restrict__ pres, uint64_t n, uint32_t* __restrict__ out) {      // out[n] = 0: the scan's last word is the total
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i <= n; i += gridDim.x * 256ull) out[i] = (i < n && pres[i]) ? 1u : 0u;
-}
 
 // rp = T.rowptr + row0: rp[r] is the place of position r's entry (FULL: written here; else the scan put it there).  `flat`: the |k| row-pointer words outside
 // [row0, row0 + n] — T.rowptr (k < 0) or rp + n + 1 (k >= 0) — all `flat_val`.
@@ -104,14 +100,7 @@ bool diag_to_csr(int tcode, uint64_t n_v, const void* vval, const uint8_t* vpres
   T.rowptr.alloc((n + 1) * 4);
   uint32_t* rp = T.rowptr.as<uint32_t>() + row0;                              // rp[0 .. n_v]: the rows of the diagonal and the word after them
   uint64_t total = n_v;
-  if (!full) {
-    DevBuf flags((n_v + 1) * 4);
-    hipLaunchKernelGGL(k_diag_pres_u32, dim3(grid_1d(n_v + 1)), dim3(256), 0, stream(), vpres, n_v, flags.as<uint32_t>());
-    exclusive_scan_u32(flags.as<uint32_t>(), rp, n_v + 1);
-    uint32_t t32 = 0;
-    GRB_HIP(hipMemcpyAsync(&t32, rp + n_v, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));      // the one read-back (and `flags` returns to the pool)
-    total = t32;
-  }
+  if (!full) total = present_positions_total(vpres, n_v, rp);                 // the one read-back
   T.nnz = total; T.col.alloc(total * 4 + 4); T.val.alloc(total * ts + 8);
   uint32_t* flat = k < 0 ? T.rowptr.as<uint32_t>() : rp + n_v + 1;
   const uint32_t flat_val = k < 0 ? 0u : (uint32_t)total;

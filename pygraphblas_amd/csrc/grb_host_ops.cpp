@@ -510,7 +510,7 @@ bool assign_line_device(GrB_Matrix C, GrB_Vector mask, GrB_BinaryOp accum, GrB_V
   const ExIdx& ri = is_row ? one : all; const ExIdx& ci = is_row ? all : one;
   assign_relocate(Tl, cs, ri, ci, (uint32_t)C->nrows, (uint32_t)C->ncols, T, plan);
   g_last_plan = std::string(is_row ? "assign_row<index=" : "assign_col<index=") + kind_name(idx) + ",accum=" + accum_name(accum) + "> " + parse_name(idx) + (is_row ? "k_extract_row_scatter" : "k_extract_lookup") +
-                " k_assign_vector k_assign_line_fill k_assign_move k_assign_region_keep ";
+                " k_assign_vector k_scatter_present k_assign_move k_assign_region_keep ";
   const DevBuf none_i, none_j;
   region_replace(C, nullptr, DescView(nullptr), T, ccode, ri, none_i, ci, none_j);
   return true;

@@ -17,7 +17,7 @@
 //                  lane ~log2(ar) + log2(br) row-pointer words and up to 4 + 4 entries.
 // A side the operator ignores (FIRST / SECOND / PAIR / ANY) is passed as nullptr and never dereferenced.
 #include "grb_kron.hpp"
-#include "grb_device.hpp"
+#include "grb_index.hpp"
 
 namespace grb {
 namespace {
@@ -96,8 +96,6 @@ __global__ __launch_bounds__(256) void k_kron_fill(uint64_t nnzt, uint32_t ar, u
   }
 }
 
-inline int grid_of(uint64_t n) { uint64_t b = (n + 255) / 256, cap = (uint64_t)device_cus() * 8; if (b < 1) b = 1; if (b > cap) b = cap; return (int)b; }
-
 struct FillTimer {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ~FillTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
@@ -111,13 +109,14 @@ void kron_csr(int code, int opcode, const DevCSR& A, const void* aval, const Dev
     fail(GrB_PANIC, "kronecker: the product does not fit the 32-bit device layout");      // (the entry point checked it: the kernels' bounds depend on it)
   if (fill_ms) *fill_ms = 0.0f;
   const size_t ts = type_size(code);
+  const uint64_t grid_cap = (uint64_t)device_cus() * 8;
   T.clear(); T.nrows = (uint32_t)nrows; T.ncols = (uint32_t)ncols; T.nnz = nnz;
   T.rowptr.alloc((nrows + 1) * 4); T.col.alloc(nnz * 4 + 4); T.val.alloc(nnz * ts + 8);
   if (!nnz) { GRB_HIP(hipMemsetAsync(T.rowptr.p, 0, (nrows + 1) * 4, stream())); GRB_HIP(hipStreamSynchronize(stream())); T.valid = true; return; }
-  hipLaunchKernelGGL(k_kron_rowptr, dim3(grid_of(nrows + 1)), dim3(256), 0, stream(), A.nrows, B.nrows, (uint32_t)B.nnz, nnz, A.rowptr.as<uint32_t>(), B.rowptr.as<uint32_t>(), T.rowptr.as<uint32_t>());
+  hipLaunchKernelGGL(k_kron_rowptr, dim3(grid_1d(nrows + 1, grid_cap)), dim3(256), 0, stream(), A.nrows, B.nrows, (uint32_t)B.nnz, nnz, A.rowptr.as<uint32_t>(), B.rowptr.as<uint32_t>(), T.rowptr.as<uint32_t>());
   FillTimer tm;
   if (fill_ms) { GRB_HIP(hipEventCreate(&tm.e0)); GRB_HIP(hipEventCreate(&tm.e1)); GRB_HIP(hipEventRecord(tm.e0, stream())); }
-  const int grid = grid_of((nnz + KRON_EPL - 1) / KRON_EPL);
+  const unsigned grid = grid_1d((nnz + KRON_EPL - 1) / KRON_EPL, grid_cap);
 #define GRB_KRON_FILL(MATH, OPC) hipLaunchKernelGGL((k_kron_fill<V, MATH, OPC>), dim3(grid), dim3(256), 0, stream(), nnz, A.nrows, B.nrows, B.ncols, (uint32_t)B.nnz, A.rowptr.as<uint32_t>(), \
     A.col.as<uint32_t>(), (const V*)aval, B.rowptr.as<uint32_t>(), B.col.as<uint32_t>(), (const V*)bval, opcode, T.col.as<uint32_t>(), T.val.as<V>())
   dispatch_type(code, [&]<class V>() {

@@ -7,7 +7,7 @@
 // merge of (row, column) keys): a power-law graph has rows of 10^5 entries, and kernels that give a row to one thread ran at
 // 1-2 G entries/s on R-MAT-22.  The heavy lifting of the hot path is in grb_spgemm.hip / grb_spmv_kernels.hpp, not here.
 #include "grb_api.hpp"
-#include "grb_index.hpp"
+#include "grb_compact.hpp"
 #include "grb_atomics.hpp"
 #include "grb_matops.hpp"
 
@@ -73,9 +73,6 @@ void csr_sort_rows(DevCSR& T, size_t ts, const DevBuf& ucol, const DevBuf& uval,
   GRB_HIP(hipStreamSynchronize(stream()));                                   // (iota / perm return to the pool)
 }
 
-static __global__ void k_keep_to_u32(const uint8_t* __restrict__ keep, uint64_t n, uint32_t* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i <= n; i += gridDim.x * 256ull) out[i] = (i < n && keep[i]) ? 1u : 0u;
-}
 static __global__ void k_gather_rowptr(const uint32_t* __restrict__ rowptr, uint32_t nrows, const uint32_t* __restrict__ pos, uint32_t* __restrict__ orp) {
   for (uint64_t r = blockIdx.x * 256ull + threadIdx.x; r <= nrows; r += (uint64_t)gridDim.x * 256ull) orp[r] = pos[rowptr[r]];
 }
@@ -88,12 +85,9 @@ void csr_compact(const DevCSR& A, const void* aval, size_t ts, const uint8_t* ke
   const uint32_t nrows = A.nrows; const uint64_t n = A.nnz;
   out.clear(); out.nrows = nrows; out.ncols = A.ncols;
   out.rowptr.alloc(((size_t)nrows + 1) * 4);
-  DevBuf flags((n + 1) * 4 + 4), pos((n + 1) * 4 + 4);
-  hipLaunchKernelGGL(k_keep_to_u32, dim3(grid_1d(n + 1)), dim3(256), 0, stream(), keep, n, flags.as<uint32_t>());
-  exclusive_scan_u32(flags.as<uint32_t>(), pos.as<uint32_t>(), n + 1);
+  DevBuf pos((n + 1) * 4 + 4);
+  const uint32_t total = present_positions_total(keep, n, pos.as<uint32_t>());
   hipLaunchKernelGGL(k_gather_rowptr, dim3(grid_1d((uint64_t)nrows + 1)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), nrows, pos.as<uint32_t>(), out.rowptr.as<uint32_t>());
-  uint32_t total = 0;
-  GRB_HIP(hipMemcpyAsync(&total, pos.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
   out.nnz = total; out.col.alloc((size_t)total * 4 + 4); out.val.alloc((size_t)total * ts + 8);
   if (n) {
     dispatch_value_size(ts, [&]<int TS>() {
@@ -101,7 +95,7 @@ void csr_compact(const DevCSR& A, const void* aval, size_t ts, const uint8_t* ke
     });
   }
   GRB_HIP(hipGetLastError());
-  GRB_HIP(hipStreamSynchronize(stream()));       // flags / pos return to the pool
+  GRB_HIP(hipStreamSynchronize(stream()));       // pos returns to the pool
   out.valid = true;
 }
 

@@ -11,6 +11,7 @@
 // compacted into the CSR rows of T.  C<M,replace> = accum(C, T) then runs as for any other mxm.
 #include "grb_opcommon.hpp"
 #include "grb_matops.hpp"
+#include "grb_compact.hpp"
 #include "grb_semiring.hpp"
 #include "grb_spmv.hpp"
 
@@ -22,6 +23,7 @@ extern "C" GrB_Info GrB_Vector_eWiseMult_BinaryOp(GrB_Vector w, const GrB_Vector
 namespace grb {
 
 namespace {
+constexpr uint64_t ROWS_GRID_CAP = 8192;                                     // the grid cap of this file's streaming kernels (grid_1d's second argument)
 // entries of one CSR row -> bitmap (values are moved as raw bytes of the element size)
 template <int TS> __global__ void k_row_to_bitmap(const uint32_t* __restrict__ col, const uint8_t* __restrict__ val, uint32_t cnt, uint8_t* __restrict__ dval, uint8_t* __restrict__ dpres) {
   for (uint32_t p = blockIdx.x * 256 + threadIdx.x; p < cnt; p += gridDim.x * 256) {
@@ -31,36 +33,48 @@ template <int TS> __global__ void k_row_to_bitmap(const uint32_t* __restrict__ c
     dpres[c] = 1;
   }
 }
-__global__ void k_pres_to_u32(const uint8_t* __restrict__ pres, uint64_t n, uint32_t* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i <= n; i += gridDim.x * 256ull) out[i] = (i < n && pres[i]) ? 1u : 0u;
-}
-template <int TS> __global__ void k_bitmap_to_row(const uint8_t* __restrict__ pres, const uint8_t* __restrict__ val, const uint32_t* __restrict__ pos, uint64_t n, uint32_t base,
-                                                  uint32_t* __restrict__ ocol, uint8_t* __restrict__ oval) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) if (pres[i]) {
-    const size_t w = (size_t)base + pos[i]; ocol[w] = (uint32_t)i;
-#pragma unroll
-    for (int b = 0; b < TS; b++) oval[w * TS + b] = val[i * TS + b];
-  }
-}
-unsigned grid_of(uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 8192) b = 8192; return (unsigned)b; }
-template <class F> void by_size(size_t ts, F&& f) {
-  switch (ts) { case 1: f(std::integral_constant<int, 1>{}); break; case 2: f(std::integral_constant<int, 2>{}); break;
-                case 4: f(std::integral_constant<int, 4>{}); break; default: f(std::integral_constant<int, 8>{}); }
-}
 GrB_Vector row_vector(const DevCSR& S, GrB_Type type, uint32_t r, const std::vector<uint32_t>& rp, uint64_t n) {
   GrB_Vector v = nullptr; if (GrB_Vector_new(&v, type, n) != GrB_SUCCESS) fail(GrB_OUT_OF_MEMORY, "mxm: row vector");
   const size_t ts = type->size;
   v->dval.alloc(n * ts + 8); v->dpres.alloc(n + 8);
   GRB_HIP(hipMemsetAsync(v->dpres.p, 0, n + 8, stream()));
   const uint32_t b = rp[r], cnt = rp[r + 1] - rp[r];
-  if (cnt) by_size(ts, [&](auto TS) {
-    hipLaunchKernelGGL((k_row_to_bitmap<decltype(TS)::value>), dim3(grid_of(cnt)), dim3(256), 0, stream(), S.col.as<uint32_t>() + b, (const uint8_t*)S.val.p + (size_t)b * ts, cnt,
+  if (cnt) dispatch_value_size(ts, [&]<int TS>() {
+    hipLaunchKernelGGL((k_row_to_bitmap<TS>), dim3(grid_1d(cnt, ROWS_GRID_CAP)), dim3(256), 0, stream(), S.col.as<uint32_t>() + b, (const uint8_t*)S.val.p + (size_t)b * ts, cnt,
                        (uint8_t*)v->dval.p, v->dpres.as<uint8_t>());
   });
   v->dev_valid = true; v->host_valid = false; v->facts.image_replaced(cnt, true);
   return v;
 }
 struct VecGuard { std::vector<GrB_Vector> v; ~VecGuard() { for (auto& x : v) if (x) GrB_Vector_free(&x); } };
+
+// The result vectors of a row-wise operation (rows[s] of length n, values of ts bytes; nullptr: an empty row) compacted into the CSR rows of T.  Every row's
+// scan is queued first and ONE synchronisation brings the nr counts; the row pointer is laid out on the host, then one scatter per non-empty row.
+// `what` names the operation in the 2^32 message.
+void rows_to_csr(const std::vector<GrB_Vector>& rows, uint64_t n, size_t ts, const char* what, DevCSR& T) {
+  const uint32_t nr = (uint32_t)rows.size();
+  std::vector<uint32_t> cnt(nr, 0);
+  std::vector<DevBuf> pos(nr);
+  for (uint32_t s = 0; s < nr; s++) if (rows[s]) {
+    vec_to_device(rows[s]);
+    pos[s].alloc((n + 1) * 4 + 4);
+    present_positions(rows[s]->dpres.as<uint8_t>(), n, pos[s].as<uint32_t>(), ROWS_GRID_CAP);
+    GRB_HIP(hipMemcpyAsync(&cnt[s], pos[s].as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, stream()));
+  }
+  GRB_HIP(hipStreamSynchronize(stream()));
+  std::vector<uint32_t> trp((size_t)nr + 1, 0);
+  uint64_t total = 0; for (uint32_t s = 0; s < nr; s++) { trp[s] = (uint32_t)total; total += cnt[s]; }
+  if (total > 0xFFFFFFF0ull) fail(GrB_INSUFFICIENT_SPACE, std::string(what) + ": result has more than 2^32 entries");
+  trp[nr] = (uint32_t)total;
+  T.clear(); T.nrows = nr; T.ncols = (uint32_t)n; T.nnz = total;
+  T.rowptr.alloc(((size_t)nr + 1) * 4); T.col.alloc(total * 4 + 8); T.val.alloc(total * ts + 8);
+  GRB_HIP(hipMemcpyAsync(T.rowptr.p, trp.data(), trp.size() * 4, hipMemcpyHostToDevice, stream()));
+  for (uint32_t s = 0; s < nr; s++) if (cnt[s])
+    scatter_present(rows[s]->dpres.as<uint8_t>(), pos[s].as<uint32_t>(), n, trp[s], COMPACT_COL_INDEX, 0, T.col.as<uint32_t>(), ts, rows[s]->dval.p, T.val.p, ROWS_GRID_CAP);
+  GRB_HIP(hipGetLastError());
+  GRB_HIP(hipStreamSynchronize(stream()));                            // (trp lives on the host stack of this call)
+  T.valid = true;
+}
 }  // namespace
 
 // T = op(A) (+).(x) op(B) restricted by the mask, one GrB_vxm per row of op(A).  `Ad` = device CSR of op(A), of A's type.
@@ -80,8 +94,6 @@ void mxm_few_rows(const DevCSR& Ad, GrB_Type atype, GrB_Matrix Mmask, const Desc
   GrB_Descriptor_opaque d{GRB_MAGIC, 0, (dv.mask_comp ? GrB_COMP : 0) | (dv.mask_struct ? GrB_STRUCTURE : 0), 0, dv.tran1 ? GrB_TRAN : 0, 0, 0, 0, 0.0, false, "mxm_rows"};
   GrB_Type ztype = type_by_code(zcode);
   VecGuard outs; outs.v.resize(nr, nullptr);
-  std::vector<uint32_t> cnt(nr, 0);
-  std::vector<DevBuf> pos(nr);
   std::string plans;
   for (uint32_t s = 0; s < nr; s++) {
     if (arp[s + 1] == arp[s]) continue;                               // an empty row of op(A) gives an empty row of T
@@ -94,29 +106,8 @@ void mxm_few_rows(const DevCSR& Ad, GrB_Type atype, GrB_Matrix Mmask, const Desc
     const GrB_Info info = GrB_vxm(w, mv, nullptr, semiring, tmp.v[0], B, &d);
     if (info != GrB_SUCCESS) fail(info, "mxm (row-wise): " + w->err);
     if (s == 0 || plans.empty()) plans = g_last_plan;
-    vec_to_device(w);
-    pos[s].alloc((nout + 1) * 4 + 4);
-    DevBuf flags((nout + 1) * 4 + 4);
-    hipLaunchKernelGGL(k_pres_to_u32, dim3(grid_of(nout + 1)), dim3(256), 0, stream(), w->dpres.as<uint8_t>(), nout, flags.as<uint32_t>());
-    exclusive_scan_u32(flags.as<uint32_t>(), pos[s].as<uint32_t>(), nout + 1);
-    GRB_HIP(hipMemcpyAsync(&cnt[s], pos[s].as<uint32_t>() + nout, 4, hipMemcpyDeviceToHost, stream()));
   }
-  GRB_HIP(hipStreamSynchronize(stream()));
-  std::vector<uint32_t> trp((size_t)nr + 1, 0);
-  uint64_t total = 0; for (uint32_t s = 0; s < nr; s++) { trp[s] = (uint32_t)total; total += cnt[s]; }
-  if (total > 0xFFFFFFF0ull) fail(GrB_INSUFFICIENT_SPACE, "mxm: result has more than 2^32 entries");
-  trp[nr] = (uint32_t)total;
-  T.clear(); T.nrows = nr; T.ncols = (uint32_t)nout; T.nnz = total;
-  T.rowptr.alloc(((size_t)nr + 1) * 4); T.col.alloc(total * 4 + 8); T.val.alloc(total * zs + 8);
-  GRB_HIP(hipMemcpyAsync(T.rowptr.p, trp.data(), trp.size() * 4, hipMemcpyHostToDevice, stream()));
-  for (uint32_t s = 0; s < nr; s++) if (cnt[s]) by_size(zs, [&](auto TS) {
-    GrB_Vector w = outs.v[s];
-    hipLaunchKernelGGL((k_bitmap_to_row<decltype(TS)::value>), dim3(grid_of(nout)), dim3(256), 0, stream(), w->dpres.as<uint8_t>(), (const uint8_t*)w->dval.p, pos[s].as<uint32_t>(), nout,
-                       trp[s], T.col.as<uint32_t>(), (uint8_t*)T.val.p);
-  });
-  GRB_HIP(hipGetLastError());
-  GRB_HIP(hipStreamSynchronize(stream()));                            // (trp lives on the host stack of this call)
-  T.valid = true;
+  rows_to_csr(outs.v, nout, zs, "mxm", T);
   g_last_plan = "mxm_rows<" + std::to_string(nr) + " x vxm> first row: " + plans;
 }
 
@@ -141,7 +132,6 @@ void ewise_few_rows(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_Bina
   GRB_HIP(hipStreamSynchronize(stream()));
   GrB_Descriptor_opaque d{GRB_MAGIC, dv.replace ? GrB_REPLACE : 0, (dv.mask_comp ? GrB_COMP : 0) | (dv.mask_struct ? GrB_STRUCTURE : 0), 0, 0, 0, 0, 0, 0.0, false, "ewise_rows"};
   VecGuard outs; outs.v.resize(nr, nullptr);
-  std::vector<uint32_t> cnt(nr, 0); std::vector<DevBuf> pos(nr);
   for (uint32_t s = 0; s < nr; s++) {
     VecGuard tmp;
     GrB_Vector va = row_vector(Ad, atype, s, arp, n), vb = row_vector(Bd, btype, s, brp, n); tmp.v.push_back(va); tmp.v.push_back(vb);
@@ -149,29 +139,8 @@ void ewise_few_rows(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_Bina
     GrB_Vector vc = row_vector(C->csr, C->type, s, crp, n); outs.v[s] = vc;
     const GrB_Info info = is_union ? GrB_Vector_eWiseAdd_BinaryOp(vc, vm, accum, op, va, vb, &d) : GrB_Vector_eWiseMult_BinaryOp(vc, vm, accum, op, va, vb, &d);
     if (info != GrB_SUCCESS) fail(info, "eWise (row-wise): " + vc->err);
-    vec_to_device(vc);
-    pos[s].alloc((n + 1) * 4 + 4);
-    DevBuf flags((n + 1) * 4 + 4);
-    hipLaunchKernelGGL(k_pres_to_u32, dim3(grid_of(n + 1)), dim3(256), 0, stream(), vc->dpres.as<uint8_t>(), n, flags.as<uint32_t>());
-    exclusive_scan_u32(flags.as<uint32_t>(), pos[s].as<uint32_t>(), n + 1);
-    GRB_HIP(hipMemcpyAsync(&cnt[s], pos[s].as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, stream()));
   }
-  GRB_HIP(hipStreamSynchronize(stream()));
-  std::vector<uint32_t> trp((size_t)nr + 1, 0);
-  uint64_t total = 0; for (uint32_t s = 0; s < nr; s++) { trp[s] = (uint32_t)total; total += cnt[s]; }
-  if (total > 0xFFFFFFF0ull) fail(GrB_INSUFFICIENT_SPACE, "eWise: result has more than 2^32 entries");
-  trp[nr] = (uint32_t)total;
-  T.clear(); T.nrows = nr; T.ncols = (uint32_t)n; T.nnz = total;
-  T.rowptr.alloc(((size_t)nr + 1) * 4); T.col.alloc(total * 4 + 8); T.val.alloc(total * cs + 8);
-  GRB_HIP(hipMemcpyAsync(T.rowptr.p, trp.data(), trp.size() * 4, hipMemcpyHostToDevice, stream()));
-  for (uint32_t s = 0; s < nr; s++) if (cnt[s]) by_size(cs, [&](auto TS) {
-    GrB_Vector w = outs.v[s];
-    hipLaunchKernelGGL((k_bitmap_to_row<decltype(TS)::value>), dim3(grid_of(n)), dim3(256), 0, stream(), w->dpres.as<uint8_t>(), (const uint8_t*)w->dval.p, pos[s].as<uint32_t>(), n, trp[s],
-                       T.col.as<uint32_t>(), (uint8_t*)T.val.p);
-  });
-  GRB_HIP(hipGetLastError());
-  GRB_HIP(hipStreamSynchronize(stream()));
-  T.valid = true;
+  rows_to_csr(outs.v, n, cs, "eWise", T);
   g_last_plan = "ewise_rows<" + std::to_string(nr) + " x vector eWise> ";
 }
 
@@ -200,14 +169,6 @@ template <int TS> __global__ void k_csr_to_bitmap(const uint32_t* __restrict__ r
 __global__ void k_bm_rowptr(const uint32_t* __restrict__ pos, uint32_t nrows, uint64_t ncols, uint32_t* __restrict__ rowptr) {
   if (threadIdx.x <= nrows) rowptr[threadIdx.x] = pos[(uint64_t)threadIdx.x * ncols];
 }
-template <int TS> __global__ void k_bm_compact(const uint8_t* __restrict__ pres, const uint8_t* __restrict__ val, const uint32_t* __restrict__ pos, uint64_t np, uint64_t ncols,
-                                               uint32_t* __restrict__ ocol, uint8_t* __restrict__ oval) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < np; i += gridDim.x * 256ull) if (pres[i]) {
-    const size_t w = pos[i]; ocol[w] = (uint32_t)(i % ncols);
-#pragma unroll
-    for (int b = 0; b < TS; b++) oval[w * TS + b] = val[i * TS + b];
-  }
-}
 // a vector object over (a slice of) a bitmap: `own` moves the buffers in (the op may replace them; take them back with vec_release), else they are borrowed
 GrB_Vector view_vector(GrB_Type type, uint64_t n, void* val, void* pres, bool known, uint64_t nvals) {
   GrB_Vector v = nullptr; if (GrB_Vector_new(&v, type, n) != GrB_SUCCESS) fail(GrB_OUT_OF_MEMORY, "batch: vector view");
@@ -226,8 +187,8 @@ DevBitmap& mat_bitmap(GrB_Matrix A) {
   const DevCSR& S = A->csr; const size_t ts = A->type->size; const uint64_t np = (uint64_t)A->nrows * A->ncols;
   A->bm.val.alloc(np * ts + 64); A->bm.pres.alloc(np + 64);
   GRB_HIP(hipMemsetAsync(A->bm.pres.p, 0, np + 64, stream()));
-  if (S.nnz) by_size(ts, [&](auto TS) {
-    hipLaunchKernelGGL((k_csr_to_bitmap<decltype(TS)::value>), dim3(grid_of(S.nnz)), dim3(256), 0, stream(), S.rowptr.as<uint32_t>(), S.col.as<uint32_t>(), (const uint8_t*)S.val.p, (uint32_t)A->nrows,
+  if (S.nnz) dispatch_value_size(ts, [&]<int TS>() {
+    hipLaunchKernelGGL((k_csr_to_bitmap<TS>), dim3(grid_1d(S.nnz, ROWS_GRID_CAP)), dim3(256), 0, stream(), S.rowptr.as<uint32_t>(), S.col.as<uint32_t>(), (const uint8_t*)S.val.p, (uint32_t)A->nrows,
                        (uint64_t)A->ncols, (uint64_t)S.nnz, (uint8_t*)A->bm.val.p, A->bm.pres.as<uint8_t>());
   });
   A->bm.valid = true; A->bm.nvals = S.nnz; A->bm.nvals_known = true;
@@ -239,19 +200,13 @@ uint64_t mat_bitmap_nvals(GrB_Matrix A) {
 }
 void mat_bitmap_to_csr(GrB_Matrix A) {
   const uint64_t np = (uint64_t)A->nrows * A->ncols; const size_t ts = A->type->size;
-  DevBuf flags((np + 1) * 4 + 4), pos((np + 1) * 4 + 4);
-  hipLaunchKernelGGL(k_pres_to_u32, dim3(grid_of(np + 1)), dim3(256), 0, stream(), A->bm.pres.as<uint8_t>(), np, flags.as<uint32_t>());
-  exclusive_scan_u32(flags.as<uint32_t>(), pos.as<uint32_t>(), np + 1);
-  uint32_t nnz = 0;
-  GRB_HIP(hipMemcpyAsync(&nnz, pos.as<uint32_t>() + np, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+  DevBuf pos((np + 1) * 4 + 4);
+  const uint32_t nnz = present_positions_total(A->bm.pres.as<uint8_t>(), np, pos.as<uint32_t>(), ROWS_GRID_CAP);
   DevCSR& c = A->csr; c.clear(); A->csc.clear();
   c.nrows = (uint32_t)A->nrows; c.ncols = (uint32_t)A->ncols; c.nnz = nnz;
   c.rowptr.alloc(((size_t)c.nrows + 1) * 4); c.col.alloc((size_t)nnz * 4 + 8); c.val.alloc((size_t)nnz * ts + 8);
   hipLaunchKernelGGL(k_bm_rowptr, dim3(1), dim3(128), 0, stream(), pos.as<uint32_t>(), c.nrows, (uint64_t)A->ncols, c.rowptr.as<uint32_t>());
-  if (nnz) by_size(ts, [&](auto TS) {
-    hipLaunchKernelGGL((k_bm_compact<decltype(TS)::value>), dim3(grid_of(np)), dim3(256), 0, stream(), A->bm.pres.as<uint8_t>(), (const uint8_t*)A->bm.val.p, pos.as<uint32_t>(), np, (uint64_t)A->ncols,
-                       c.col.as<uint32_t>(), (uint8_t*)c.val.p);
-  });
+  if (nnz) scatter_present(A->bm.pres.as<uint8_t>(), pos.as<uint32_t>(), np, 0, COMPACT_COL_MOD, (uint64_t)A->ncols, c.col.as<uint32_t>(), ts, A->bm.val.p, c.val.p, ROWS_GRID_CAP);
   GRB_HIP(hipGetLastError());
   c.valid = true; A->dev_valid = true; A->bm.nvals = nnz; A->bm.nvals_known = true;
 }
@@ -550,14 +505,14 @@ static bool spmm_pull_batch(GrB_Matrix A, DevBitmap& ab, GrB_Matrix Mmask, const
   DevBuf lrec(max_long * 12 + 64), litem(max_items * 4 + 64), lpval(max_items * NSP * zs + 64), lphas(max_items * 4 + 64);
   const uint8_t* mbool = nullptr; const uint8_t* mpres = nullptr;
   if (Mmask) { mpres = Mmask->bm.pres.as<uint8_t>(); mbool = (const uint8_t*)cast_values(T_BOOL, Mmask->type->code, Mmask->bm.val.p, (uint64_t)nr * nout, mb); }
-  hipLaunchKernelGGL(k_spb_allow, dim3(grid_of(nout)), dim3(256), 0, stream(), mbool, mpres, nr, nout, dv.mask_struct ? 1 : 0, dv.mask_comp ? 1 : 0, allowm.as<uint8_t>());
+  hipLaunchKernelGGL(k_spb_allow, dim3(grid_1d(nout, ROWS_GRID_CAP)), dim3(256), 0, stream(), mbool, mpres, nr, nout, dv.mask_struct ? 1 : 0, dv.mask_comp ? 1 : 0, allowm.as<uint8_t>());
   GRB_HIP(hipMemsetAsync(tpres.p, 0, (size_t)nr * nout, stream())); GRB_HIP(hipMemsetAsync(lcnt.p, 0, 16, stream()));
-  hipLaunchKernelGGL(k_spb_long_rows, dim3(grid_of(R.nrows)), dim3(256), 0, stream(), R.rowptr.as<uint32_t>(), allowm.as<uint8_t>(), R.nrows, lcnt.as<uint32_t>(), lrec.as<uint32_t>(), litem.as<uint32_t>());
+  hipLaunchKernelGGL(k_spb_long_rows, dim3(grid_1d(R.nrows, ROWS_GRID_CAP)), dim3(256), 0, stream(), R.rowptr.as<uint32_t>(), allowm.as<uint8_t>(), R.nrows, lcnt.as<uint32_t>(), lrec.as<uint32_t>(), litem.as<uint32_t>());
   bool ran = dispatch_type(zcode, [&]<class T>() {
     if constexpr (sizeof(T) == 4 || sizeof(T) == 8) {
       auto go = [&](auto NSPc) {
         constexpr int N = decltype(NSPc)::value;
-        hipLaunchKernelGGL((k_spb_interleave<T, N>), dim3(grid_of(nin)), dim3(256), 0, stream(), (const T*)ab.val.p, ab.pres.as<uint8_t>(), nr, nin, (T*)ui.p, upm.as<uint8_t>());
+        hipLaunchKernelGGL((k_spb_interleave<T, N>), dim3(grid_1d(nin, ROWS_GRID_CAP)), dim3(256), 0, stream(), (const T*)ab.val.p, ab.pres.as<uint8_t>(), nr, nin, (T*)ui.p, upm.as<uint8_t>());
         with_semiring<T>(sd, [&](auto sr) {
           typedef decltype(sr) SR;
           if (R.derived.plan_nblocks) hipLaunchKernelGGL((k_spb_blocks<T, SR, N>), dim3(R.derived.plan_nblocks), dim3(SPMV_THREADS), 0, stream(), (const SpmvBlock*)R.derived.plan_blocks.p, R.rowptr.as<uint32_t>(), R.col.as<uint32_t>(),

@@ -17,7 +17,7 @@
 //  C  k_spmspv_push     frontier-driven scatter with atomics — the push step when u is sparse.
 // Algorithmic bytes per call: nnz*(sizeof(T)+4) + (nrows+1)*4 + ncols*T + nrows*T.
 #include "grb_api.hpp"
-#include "grb_device.hpp"
+#include "grb_compact.hpp"
 #include "grb_semiring.hpp"
 #include "grb_spmv.hpp"
 #include <vector>
@@ -90,28 +90,19 @@ bool spmspv_push_supported(const SemiringDesc& d) {
   return d.addop == B_PLUS || d.addop == B_MIN || d.addop == B_MAX;
 }
 
-// gather the indices of present entries of a bitmap vector (ascending) -> fidx, returns count
-__global__ void k_flag_to_u32(const uint8_t* __restrict__ pres, uint64_t n, uint32_t* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) out[i] = pres[i] ? 1u : 0u;
-}
-__global__ void k_compact_idx(const uint8_t* __restrict__ pres, const uint32_t* __restrict__ pos, uint64_t n, uint32_t* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) if (pres[i]) out[pos[i]] = (uint32_t)i;
-}
-
 void spmspv_push(const SpmvCall& c, const SemiringDesc& d, uint64_t u_nvals) {
   // c.M here is the CSR whose ROWS are indexed like u (i.e. the transpose of the pull operand)
   const DevCSR& M = *c.M; const uint64_t nu = M.nrows, nout = M.ncols;
-  auto grid_of = [](uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (unsigned)b; };
-  DevBuf flags, pos, fidx((u_nvals + 1) * 4), longlist((u_nvals + 2) * 4);
+  DevBuf pos, fidx((u_nvals + 1) * 4), longlist((u_nvals + 2) * 4);
   if (c.small_idx && c.small_n == u_nvals && u_nvals <= 64) {
     // the frontier is known on the host: its list travels as kernel arguments of run_push's first launch (k_push_init), which also clears
     // the presence bytes and the hub-row counter
   } else {
     GRB_HIP(hipMemsetAsync(longlist.p, 0, 4, stream()));
-    flags.alloc(nu * 4 + 4); pos.alloc(nu * 4 + 4);
-    hipLaunchKernelGGL(k_flag_to_u32, dim3(grid_of(nu)), dim3(256), 0, stream(), c.upres, nu, flags.as<uint32_t>());
-    exclusive_scan_u32(flags.as<uint32_t>(), pos.as<uint32_t>(), nu);
-    hipLaunchKernelGGL(k_compact_idx, dim3(grid_of(nu)), dim3(256), 0, stream(), c.upres, pos.as<uint32_t>(), nu, fidx.as<uint32_t>());
+    // the indices of u's present entries, ascending -> fidx; nothing is read back (u_nvals is known)
+    pos.alloc((nu + 1) * 4);
+    present_positions(c.upres, nu, pos.as<uint32_t>());
+    scatter_present(c.upres, pos.as<uint32_t>(), nu, 0, COMPACT_COL_INDEX, 0, fidx.as<uint32_t>(), 0, nullptr, nullptr);
     GRB_HIP(hipMemsetAsync(c.tpres, 0, nout ? nout : 1, stream()));
   }
   dispatch_type(d.zcode, [&]<class T>() { run_push<T>(c, d, fidx.as<uint32_t>(), u_nvals, longlist.as<uint32_t>()); });

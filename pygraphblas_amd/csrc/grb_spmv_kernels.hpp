@@ -18,7 +18,7 @@
 // Algorithmic bytes per call: nnz*(sizeof(T)+4) + (nrows+1)*4 + ncols*T + nrows*T.
 #pragma once
 #include "grb_api.hpp"
-#include "grb_device.hpp"
+#include "grb_index.hpp"
 #include "grb_semiring.hpp"
 #include "grb_spmv.hpp"
 
@@ -787,15 +787,14 @@ template <class T> __global__ void k_push_init(T* __restrict__ tval, uint8_t* __
 template <class T> void run_push(const SpmvCall& c, const SemiringDesc& d, const uint32_t* fidx, uint64_t u_nvals, uint32_t* longlist) {
   const DevCSR& M = *c.M; const uint64_t nout = M.ncols;
   uint32_t* const fidx_w = const_cast<uint32_t*>(fidx);
-  auto grid_of = [](uint64_t n) { uint64_t b = (n + 255) / 256; if (b < 1) b = 1; if (b > 4096) b = 4096; return (unsigned)b; };
   with_semiring<T>(d, [&](auto sr) {
     typedef decltype(sr) SR;
     // the accumulator starts at the identity with no entry; with the operand's list known on the host (<= 64 entries, SpmvCall::small_idx) the
     // same launch writes the list and clears the hub-row counter (round 5: six launches -> three for the first level of a BFS)
     if (c.small_idx && c.small_n == u_nvals && u_nvals <= 64) {
       SmallList64 sl; sl.n = (uint32_t)u_nvals; for (uint32_t q = 0; q < sl.n; q++) sl.idx[q] = c.small_idx[q];
-      hipLaunchKernelGGL((k_push_init<T>), dim3(grid_of(nout / 16 + 1)), dim3(256), 0, stream(), (T*)c.tval, c.tpres, nout, sr.identity, sl, (uint32_t*)fidx_w, longlist);
-    } else if (nout) hipLaunchKernelGGL((k_fill<T>), dim3(grid_of(nout)), dim3(256), 0, stream(), (T*)c.tval, nout, sr.identity);
+      hipLaunchKernelGGL((k_push_init<T>), dim3(grid_1d(nout / 16 + 1)), dim3(256), 0, stream(), (T*)c.tval, c.tpres, nout, sr.identity, sl, (uint32_t*)fidx_w, longlist);
+    } else if (nout) hipLaunchKernelGGL((k_fill<T>), dim3(grid_1d(nout)), dim3(256), 0, stream(), (T*)c.tval, nout, sr.identity);
     uint64_t nb = (u_nvals + 3) / 4; if (nb < 1) nb = 1; if (nb > 16384) nb = 16384;
     SmallList64 excl; excl.n = 0;
     if (c.excl_small && c.small_idx && c.small_n == u_nvals && u_nvals <= 64) { excl.n = (uint32_t)u_nvals; for (uint32_t q = 0; q < excl.n; q++) excl.idx[q] = c.small_idx[q]; }
