@@ -224,6 +224,7 @@ void exclusive_scan_u64(const uint64_t* in, uint64_t* out, uint64_t n);         
 void exclusive_scan_max_u64(const uint64_t* in, uint64_t* out, uint64_t n);        // out[i] = max(0, in[0..i))
 void sort_pairs_u32(const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t n, int end_bit);
 void segmented_sort_pairs_u32(const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t n, uint32_t nseg, const uint32_t* begins, const uint32_t* ends, int end_bit);   // every segment [begins[s], ends[s]) on its own
+void segmented_sort_pairs_u64(const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t n, uint32_t nseg, const uint32_t* begins, const uint32_t* ends, int end_bit);   // ... over 64-bit keys
 void sort_keys_u32(const uint32_t* kin, uint32_t* kout, uint64_t n, int end_bit);
 void sort_pairs_u64(const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t n, int end_bit);
 

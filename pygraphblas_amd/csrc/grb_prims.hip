@@ -62,5 +62,10 @@ void segmented_sort_pairs_u32(const uint32_t* kin, uint32_t* kout, const uint32_
   if (!n || !nseg) return;
   with_temp([&](void* t, size_t& bytes) { return rocprim::segmented_radix_sort_pairs(t, bytes, kin, kout, vin, vout, (unsigned)n, (unsigned)nseg, begins, ends, 0u, (unsigned)end_bit, stream()); });
 }
+// the same over 64-bit keys (the rows of a matrix sorted by 8-byte values: grb_sort.hip)
+void segmented_sort_pairs_u64(const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, uint64_t n, uint32_t nseg, const uint32_t* begins, const uint32_t* ends, int end_bit) {
+  if (!n || !nseg) return;
+  with_temp([&](void* t, size_t& bytes) { return rocprim::segmented_radix_sort_pairs(t, bytes, kin, kout, vin, vout, (unsigned)n, (unsigned)nseg, begins, ends, 0u, (unsigned)end_bit, stream()); });
+}
 
 }  // namespace grb

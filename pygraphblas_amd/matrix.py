@@ -694,6 +694,27 @@ class Matrix:
         check(lib.GxB_Vector_diag(out._h, self._h, C.c_int64(k), None), out)
         return out
 
+    def sort(self, op=None, desc=None, values=True, perm=True):
+        """`GxB_Matrix_sort`: `(C, P)` — row i of C holds the values of row i in sorted order at columns 0 .. len - 1, P (INT64) the column each came from;
+        under a descriptor with the first input transposed the columns are sorted (`C[k, j]` is the k-th value of column j, `P[k, j]` its row).  `op` is the
+        type's `LT` (ascending, the default) or `GT`; ties keep the smaller index first and NaNs come last under both.  The part not asked for is None."""
+        if op is None:
+            op = self.type.LT
+        Cm = Matrix.sparse(self.type, self.nrows, self.ncols) if values else None
+        Pm = Matrix.sparse(types.INT64, self.nrows, self.ncols) if perm else None
+        _, _, dh = get_args(None, None, desc)
+        check(lib.GxB_Matrix_sort(Cm._h if values else None, Pm._h if perm else None, C.c_void_p(op.get_op()), self._h, dh), Cm if values else Pm)
+        return Cm, Pm
+
+    def topk(self, k, largest=True, desc=None):
+        """`GrBX_Matrix_select_topk`: the k largest (`largest=False`: smallest) entries of every row, at their own coordinates — of every column under a
+        descriptor with the first input transposed.  Among equal values the smaller index is kept."""
+        out = Matrix.sparse(self.type, self.nrows, self.ncols)
+        op = self.type.GT if largest else self.type.LT
+        _, _, dh = get_args(None, None, desc)
+        check(lib.GrBX_Matrix_select_topk(out._h, C.c_void_p(op.get_op()), self._h, C.c_uint64(k), dh), out)
+        return out
+
     def kronecker(self, other, op=None, cast=None, out=None, mask=None, accum=None, desc=None):
         """Kronecker product (reference: matrix.py:2728-2805)."""
         if op is None:

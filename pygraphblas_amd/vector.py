@@ -405,6 +405,24 @@ class Vector:
     def nonzero(self):
         return self.select("NONZERO")
 
+    def sort(self, op=None, desc=None, values=True, perm=True):
+        """`GxB_Vector_sort`: `(w, p)` — `w[k]` is the k-th value in sorted order and `p[k]` (INT64) the index it came from, for k = 0 .. nvals - 1.  `op` is the
+        type's `LT` (ascending, the default) or `GT`; ties keep the smaller index first and NaNs come last under both.  The part not asked for is None."""
+        if op is None:
+            op = self.type.LT
+        w = Vector.sparse(self.type, self.size) if values else None
+        p = Vector.sparse(types.INT64, self.size) if perm else None
+        _, _, dh = get_args(None, None, desc)
+        check(lib.GxB_Vector_sort(w._h if values else None, p._h if perm else None, C.c_void_p(op.get_op()), self._h, dh), w if values else p)
+        return w, p
+
+    def topk(self, k, largest=True):
+        """`GrBX_Vector_select_topk`: the k largest (`largest=False`: smallest) entries at their own indices; among equal values the smaller index is kept."""
+        out = Vector.sparse(self.type, self.size)
+        op = self.type.GT if largest else self.type.LT
+        check(lib.GrBX_Vector_select_topk(out._h, C.c_void_p(op.get_op()), self._h, C.c_uint64(k), None), out)
+        return out
+
     def pattern(self, typ=types.BOOL):
         """The structure of the vector as a vector of ones (reference: pygraphblas/vector.py:1406-1425)."""
         out = Vector.sparse(typ, self.size)

@@ -550,6 +550,17 @@ GrB_Info GrBX_kron_fill_ms(float *milliseconds);   /* device time of k_kron_fill
 GrB_Info GxB_Matrix_diag(GrB_Matrix C, const GrB_Vector v, int64_t k, const GrB_Descriptor desc);   /* Matrix.from_diag, pygraphblas/matrix.py:333-375 */
 GrB_Info GxB_Vector_diag(GrB_Vector v, const GrB_Matrix A, int64_t k, const GrB_Descriptor desc);   /* Matrix.vector_diag, pygraphblas/matrix.py:2225-2277 */
 GrB_Info GrBX_diag_thresholds(uint64_t *matrix_min_entries, uint64_t *vector_min_entries);   /* entries of a host-resident operand from which GxB_Matrix_diag / GxB_Vector_diag take their device route (an operand that lives in HBM only always does) */
+/* Sorting by value (the SuiteSparse 6.1 entry points) and top-k selection.  Row i of C holds the values of A's row i in sorted order at columns 0 .. len - 1, P (GrB_INT64)
+   the column each came from; GrB_INP0 = GrB_TRAN sorts columns (C(k, j) is the k-th value of column j, P(k, j) its row).  C or P may be NULL, not both; C may be A;
+   no mask, no accumulator.  op is GrB_LT_<T> or GrB_GT_<T> of a real type (else GrB_DOMAIN_MISMATCH) and compares A's values cast to T.  The order is total: ties by
+   the smaller index, -0.0 ties +0.0, NaNs after every number under LT and GT alike.  select_topk keeps the first min(k, len) entries of every row (column under
+   GrB_TRAN; the whole vector) in that order, at their own coordinates.  The device route leaves "sort<on=matrix,by=row|col,op=lt|gt,key=32|64,wave=N,lds=N,prim=N> ..." or
+   "topk<...,k=K> ..." in GrBX_last_kernel_plan (the vector forms: on=vector,...,nvals=N). */
+GrB_Info GxB_Matrix_sort(GrB_Matrix C, GrB_Matrix P, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_sort(GrB_Vector w, GrB_Vector p, const GrB_BinaryOp op, const GrB_Vector u, const GrB_Descriptor desc);
+GrB_Info GrBX_Matrix_select_topk(GrB_Matrix C, const GrB_BinaryOp op, const GrB_Matrix A, GrB_Index k, const GrB_Descriptor desc);
+GrB_Info GrBX_Vector_select_topk(GrB_Vector w, const GrB_BinaryOp op, const GrB_Vector u, GrB_Index k, const GrB_Descriptor desc);
+GrB_Info GrBX_sort_thresholds(uint64_t *wave_max, uint64_t *lds_max);   /* the longest row one wave sorts in registers, the longest one workgroup sorts in LDS (longer rows: segmented radix sort) */
 /* build from tuples that may live in HBM: I / J are 64-bit indices, X holds values of the container's own type; location 0 = host arrays,
    1 = device arrays (read where they are on the device route, downloaded once for the host route).  Same outcomes as GrB_*_build_<T>. */
 GrB_Info GrBX_Matrix_build_at(GrB_Matrix C, const GrB_Index *I, const GrB_Index *J, const void *X, GrB_Index nvals, const GrB_BinaryOp dup, int location);
