@@ -397,7 +397,6 @@ static void build_tuples(GrB_Type type, const GrB_Index* I, const GrB_Index* J, 
 // GRB_MI355X_BUILD=0 forces the host route, =1 the device route wherever it is legal (read per call: a test hook).  Outcomes come in the host route's order —
 // OUTPUT_NOT_EMPTY (before the choice), INDEX_OUT_OF_BOUNDS, INVALID_VALUE — and the container is written only after the last of them is excluded: a refused
 // build leaves it as it was.  A run of duplicates beyond BUILD_RUN_SERIAL_MAX of an operator that is not exactly associative sends the whole call to the host route.
-static int build_env() { const char* e = getenv("GRB_MI355X_BUILD"); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }
 static bool build_dup_on_device(GrB_BinaryOp dup, int code) {
   if (!dup) return true;
   return dup->opcode < B_FIRSTI && !binop_needs_math(dup->opcode) && dup->xtype && dup->ytype && dup->ztype &&
@@ -405,7 +404,7 @@ static bool build_dup_on_device(GrB_BinaryOp dup, int code) {
 }
 static bool build_takes_device(GrB_Type type, bool iso, int xcode, GrB_Index n, GrB_Index nrows, GrB_Index ncols, GrB_BinaryOp dup) {
   const bool legal = build_route_legal(device_ok() && !iso, type->code <= T_FP64, xcode == type->code, build_dup_on_device(dup, type->code), nrows, ncols, n);
-  return build_route_taken(legal, build_env(), n);
+  return build_route_taken(legal, route_env("GRB_MI355X_BUILD"), n);
 }
 // "GrB_PLUS_FP64" of type "GrB_FP64" -> "PLUS"
 static std::string build_plan(GrB_Type type, GrB_BinaryOp dup, const BuildResult& r) {
@@ -583,6 +582,7 @@ GrB_Info GrB_Matrix_removeElement(GrB_Matrix A, GrB_Index i, GrB_Index j) {
     if (mat_edit_route(A)) { A->pending.push_back(p); A->bm.clear(); return; }      // it lives in HBM: queued for the device (the bitmap cache beside the CSR has its own readers: dropped now)
     mat_to_host(A); A->pending.push_back(p); mat_invalidate_device(A); });
 }
+double GxB_ALWAYS_HYPER = 1.0, GxB_NEVER_HYPER = -1.0, GxB_HYPER_DEFAULT = 0.0625;      // hyper_switch settings (stored options only)
 GrB_Info GxB_Matrix_Option_set(GrB_Matrix A, int field, ...) {
   CHECK_MAT(A); va_list ap; va_start(ap, field); GrB_Info info = GrB_SUCCESS;
   switch (field) {

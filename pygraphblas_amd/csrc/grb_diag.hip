@@ -1,5 +1,5 @@
 // grb_diag.hip — diagonals in HBM: a vector bitmap onto the k-th diagonal of a square CSR (behind GxB_Matrix_diag), and the k-th diagonal of a CSR as a
-// bitmap (behind GxB_Vector_diag); the routes are in grb_host_ops.cpp.  Both are streaming passes: no LDS, no atomics, every output position has one writer.
+// bitmap (behind GxB_Vector_diag); the routes are in grb_diag_ops.cpp.  Both are streaming passes: no LDS, no atomics, every output position has one writer.
 //
 //   diag_to_csr         T has at most one entry per row, so its row pointer IS the exclusive scan of v's presence bytes, shifted by the |k| rows before the
 //                       diagonal (k < 0, all 0) and followed by the |k| rows after it (k >= 0, all nnz(T)).  The scan (present_positions: rocPRIM, over the bytes widened to

@@ -1,5 +1,5 @@
 // grb_diag.hpp — host interface of the diagonal kernels (grb_diag.hip): a vector onto the k-th diagonal of a square CSR, and the k-th diagonal of a CSR as a bitmap;
-// and the geometry of a diagonal (host arithmetic only, shared by both routes of GxB_Matrix_diag / GxB_Vector_diag in grb_host_ops.cpp).
+// and the geometry of a diagonal (host arithmetic only, shared by both routes of GxB_Matrix_diag / GxB_Vector_diag in grb_diag_ops.cpp).
 #pragma once
 #include "grb_internal.hpp"
 

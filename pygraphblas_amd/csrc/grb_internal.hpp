@@ -18,6 +18,7 @@
 #include "grb_ops.hpp"
 #include "grb_vecfacts.hpp"
 #include "grb_devcsr.hpp"
+#include "grb_route.hpp"
 
 typedef uint64_t GrB_Index;
 
@@ -168,7 +169,7 @@ void hyper_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semir
 void hyper_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc);
 void hyper_vec_ewise(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v, GrB_Descriptor desc, bool is_union);
 void hyper_mat_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, bool is_union);
-// scalar into a region on the host mirror (grb_host_ops.cpp): for complex containers and for dimensions beyond the device layout
+// scalar into a region on the host mirror (grb_assign_ops.cpp): for complex containers and for dimensions beyond the device layout
 void host_assign_scalar(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, GrB_Descriptor desc);
 void host_assign_scalar(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, GrB_Descriptor desc);
 void vec_resolve(GrB_Vector v);           // complete deferred work that involves v (grb_lazy.cpp)
@@ -200,6 +201,22 @@ const DevCSR& mat_csc(GrB_Matrix A);      // cached CSR of A^T (device)
 
 bool check_obj(const void* p);            // magic check
 GrB_Type type_by_code(int code);
+
+// ---- what the route predicates read of a container (the policy and the thresholds: grb_route.hpp) ----
+inline int route_env(const char* name) { const char* e = getenv(name); return (e && *e) ? (atoi(e) != 0 ? 1 : 0) : -1; }      // a route's test hook: 0 host, 1 device, -1 not set
+// an HBM layout exists: not hypersparse, not complex, not a full one-valued container (nullptr: no such operand) ... and for mat_capable not a bitmap-only batch matrix
+inline bool dev_capable(GrB_Matrix A) { return !A || (!is_hyper(A) && A->type->code < T_FC32 && !A->iso_full); }
+inline bool dev_capable(GrB_Vector v) { return !v || (!is_hyper(v) && v->type->code < T_FC32 && !v->iso_full); }
+inline bool mat_capable(GrB_Matrix A) { return dev_capable(A) && !(A && mat_bitmap_only(A)); }
+inline bool hbm_only(GrB_Matrix A) { return A->dev_valid && !A->host_valid; }      // it lives in HBM: it is not downloaded to pick a route
+inline bool hbm_only(GrB_Vector v) { return v->dev_valid && !v->host_valid; }
+// (the count of a valid host mirror, or of the device CSR: no device work.  With element edits queued on an HBM-only matrix — grb_container.cpp — the CSR header is read
+//  WITHOUT a flush here: the count is off by at most the queue's length, and it only picks a route.)
+inline uint64_t entries_of(GrB_Matrix A) { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }
+inline uint64_t entries_known(GrB_Vector u) { return u->host_valid ? vec_nvals(u) : (u->facts.dnvals_known ? u->facts.dnvals : 0); }      // (no device work for a count)
+// the second stage for an operand whose count is taken from a valid host mirror only (extract, diag, sort)
+inline bool route_by_host_count(GrB_Matrix A, uint64_t min_entries) { return route_by_size(hbm_only(A), A->host_valid, A->host_valid ? mat_nvals(A) : 0, min_entries); }
+inline bool route_by_host_count(GrB_Vector u, uint64_t min_entries) { return route_by_size(hbm_only(u), u->host_valid, u->host_valid ? vec_nvals(u) : 0, min_entries); }
 
 // scalar conversion between any two built-in real types through host code
 void cast_scalar(int dst_code, void* dst, int src_code, const void* src);

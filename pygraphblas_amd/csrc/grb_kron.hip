@@ -1,4 +1,4 @@
-// grb_kron.hip — the Kronecker product in HBM: T = A (x)_op B, CSR in, CSR out (behind GrB_Matrix_kronecker_BinaryOp, grb_host_ops.cpp).
+// grb_kron.hip — the Kronecker product in HBM: T = A (x)_op B, CSR in, CSR out (behind GrB_Matrix_kronecker_BinaryOp, grb_kron_ops.cpp).
 //
 // Everything about T is known in closed form, so there is no count pass, no scan, no atomics, no sort and no size read back:
 //   nnz(T)                  = nnz(A) nnz(B)

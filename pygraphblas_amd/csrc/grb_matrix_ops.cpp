@@ -13,6 +13,7 @@
 #include "grb_matops.hpp"
 #include "grb_assign_scalar.hpp"
 #include "grb_lazy.hpp"
+#include "grb_hostmap.hpp"      // kind_name: the plan's word for an index argument
 
 using namespace grb;
 
@@ -68,7 +69,7 @@ void adopt(GrB_Matrix C, DevCSR& T, int tcode) {
 }
 
 }  // namespace
-// C<M,replace> = accum(C, T).  `t_masked`: T already has no entry the mask forbids.  (Declared in grb_extract.hpp: the extract entry points of grb_host_ops.cpp end in it too.)
+// C<M,replace> = accum(C, T).  `t_masked`: T already has no entry the mask forbids.  (Declared in grb_extract.hpp: the extract entry points of grb_extract_ops.cpp end in it too.)
 void grb::matrix_write_back(GrB_Matrix C, DevCSR& T, int tcode, GrB_Matrix M, const DescView& dv, GrB_BinaryOp accum, bool t_masked) {
   if (accum) check_binop(accum, "accum");
   if (nothing_to_write(C, M, dv)) return;
@@ -398,8 +399,6 @@ void do_reduce_vector(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Mon
 // A list that names an index twice, a list over more than ASSIGN_TABLE_MAX_DIM positions, a complex valued mask and GRB_MI355X_ASSIGN_SCALAR=0 (read per
 // call: a test hook, and the yardstick of tools/assign_scalar_probe.py) keep the host-built block below.  There is no size threshold: measured from 1e2 positions
 // up, the device block never loses to the host-built one by more than the spread between runs.
-const char* scalar_kind_name(const ExIdx& x) { return x.kind == EX_ALL ? "all" : x.kind == EX_LIST ? "list" : "range"; }
-
 // the write-back of every route: assign keeps the entries of C outside the region, and inside it T's replace C's — that is accum = SECOND on the union of
 // the patterns when the caller gave no accumulator
 void scalar_write_back(GrB_Matrix C, DevCSR& T, GrB_Matrix M, const DescView& dv, GrB_BinaryOp accum, bool t_masked) {
@@ -422,7 +421,7 @@ bool assign_scalar_device(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, const 
   DevCSR T;
   if (pattern) { mat_to_device(M); scalar_from_mask(M->csr, M->type->code, dv.mask_struct, ri, inv_i, ci, inv_j, s, ts, T); }      // (M may be C itself: T is complete before the write-back starts)
   else scalar_block((uint32_t)C->nrows, (uint32_t)C->ncols, ri, inv_i, ci, inv_j, s, ts, T);
-  g_last_plan = std::string("assign_scalar<rows=") + scalar_kind_name(ri) + ",cols=" + scalar_kind_name(ci) + ",mask=" + (pattern ? "pattern" : dv.mask_comp ? "comp" : "none") + ",accum=" + (accum ? accum->name : "none") + "> " +
+  g_last_plan = std::string("assign_scalar<rows=") + hostmap::kind_name(ri) + ",cols=" + hostmap::kind_name(ci) + ",mask=" + (pattern ? "pattern" : dv.mask_comp ? "comp" : "none") + ",accum=" + (accum ? accum->name : "none") + "> " +
                 (pattern ? "k_assign_scalar_flags csr_compact k_assign_scalar_fill<values> " : "k_assign_scalar_rowflag k_assign_scalar_rowptr k_assign_scalar_fill<block> ") + "entries=" + std::to_string(T.nnz) + " ";
   scalar_write_back(C, T, M, dv, accum, pattern);
   return true;

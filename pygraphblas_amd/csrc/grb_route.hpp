@@ -1,0 +1,37 @@
+// grb_route.hpp — host route or device route: the one policy of every container operation that has both (index-list extract and assign, kronecker, the two
+// diagonal forms, sort / top-k; build-from-tuples follows the same rule through grb_build_keys.hpp).  Plain integers only — no HIP types, no containers — so that
+// a stand-alone program can check it under the sanitizers (tests/route_policy_check.cpp).  The helpers that read containers (route_env, dev_capable, mat_capable,
+// hbm_only, entries_of, entries_known, route_by_host_count) are in grb_internal.hpp.
+//
+// THE RULE, in two stages so that a caller asks for an entry count (and completes deferred work on a vector) only when the first stage left it to the size:
+//   route_first    the test hook (0: host, 1: device wherever legal, -1 unset: go on), then legality — a HIP device, an HBM layout for every container of the
+//                  call — then `forced`: an index list of the call lies in HBM, and it is not downloaded to pick a route.
+//   route_by_size  an operand that lives in HBM only is not downloaded either: the device route, without asking for a count.  Otherwise a count that costs no
+//                  device work (`count_known`) against the entry point's threshold below.
+#pragma once
+#include <cstdint>
+
+namespace grb {
+
+enum RouteStep { ROUTE_HOST, ROUTE_DEVICE, ROUTE_BY_SIZE };
+constexpr RouteStep route_first(int env, bool have_device, bool all_capable, bool forced) {
+  if (env == 0 || !have_device || !all_capable) return ROUTE_HOST;
+  return (env == 1 || forced) ? ROUTE_DEVICE : ROUTE_BY_SIZE;
+}
+constexpr bool route_by_size(bool lives_in_hbm_only, bool count_known, uint64_t entries, uint64_t min_entries) {
+  return lives_in_hbm_only || (count_known && entries >= min_entries);
+}
+
+// THE THRESHOLDS: entries from which an operation takes the device route by itself, each against its own host route, upload included (DESIGN.md "Routes").
+// The tenth, BUILD_DEVICE_MIN_TUPLES, stays with the key arithmetic it is tested with (grb_build_keys.hpp).
+constexpr uint64_t EXTRACT_DEVICE_MIN_ENTRIES = 10000;           // the three extract forms: the measured crossover against the host route, upload included
+constexpr uint64_t ASSIGN_DEVICE_MIN_ENTRIES = 30000;            // GrB_Matrix_assign
+constexpr uint64_t ASSIGN_ROW_DEVICE_MIN_ENTRIES = 3000000;      // GrB_Row_assign: the host replaces the row's run of tuples in place, cheap up to ~1e6 entries
+constexpr uint64_t ASSIGN_COL_DEVICE_MIN_ENTRIES = 100000;       // GrB_Col_assign: the host's one merge pass
+constexpr uint64_t ASSIGN_VEC_DEVICE_MIN_ENTRIES = 500;          // GrB_Vector_assign: the host route is map-based for every shape (the smallest size measured; the device route won all)
+constexpr uint64_t KRON_DEVICE_MIN_ENTRIES = 1000;              // provisional: reasoned from the assign route's fixed cost, not yet measured
+constexpr uint64_t DIAG_MATRIX_DEVICE_MIN_ENTRIES = 1000;       // GxB_Matrix_diag: measured, the host route is one std::map insertion per entry (0.11 ms against 0.07 ms at 1e3 entries)
+constexpr uint64_t DIAG_VECTOR_DEVICE_MIN_ENTRIES = 10000;      // GxB_Vector_diag: measured, the host route is one pass over A's tuples (0.11 ms against 0.07 ms at 1e4 entries)
+constexpr uint64_t SORT_DEVICE_MIN_ENTRIES = EXTRACT_DEVICE_MIN_ENTRIES;      // sort and top-k borrow extract's value: not measured on their own
+
+}  // namespace grb

@@ -1,5 +1,5 @@
 // grb_sort.hip — sorting by value in HBM: the rows of a CSR (behind GxB_Matrix_sort and GrBX_Matrix_select_topk) and a bitmap vector (behind GxB_Vector_sort and
-// GrBX_Vector_select_topk); the routes are in grb_host_ops.cpp, the order in grb_sort_keys.hpp.  Nothing here rebuilds a value from its key: every kernel
+// GrBX_Vector_select_topk); the routes are in grb_sort_ops.cpp, the order in grb_sort_keys.hpp.  Nothing here rebuilds a value from its key: every kernel
 // sorts (key, place) pairs and hands the places on, the values are gathered through them afterwards.
 //
 //   csr_sort_positions  per entry place e of row r, i = e - rowptr[r]: perm[e] = the place of the row's i-th entry in sorted order, ocol[e] = i.

@@ -1,5 +1,5 @@
 // grb_sort.hpp — host interface of the sort kernels (grb_sort.hip): the rows of a CSR ordered by value, a bitmap vector ordered by value, and the flags of a
-// top-k selection.  The order is grb_sort_keys.hpp's; the routes (which operand, which transpose, the write-back) are in grb_host_ops.cpp.
+// top-k selection.  The order is grb_sort_keys.hpp's; the routes (which operand, which transpose, the write-back) are in grb_sort_ops.cpp.
 #pragma once
 #include "grb_internal.hpp"
 #include "grb_sort_keys.hpp"

@@ -620,7 +620,7 @@ class Matrix:
             return self.extract_col(j, i)
         return self.extract_matrix(i, j)
 
-    # ---- slices (grb_host_ops.cpp: extract and assign run in HBM for device-resident or large containers, grb_extract.hip / grb_assign.hip; small host-resident ones on the host mirror) ----
+    # ---- slices (grb_extract_ops.cpp, grb_assign_ops.cpp: extract and assign run in HBM for device-resident or large containers, grb_extract.hip / grb_assign.hip; small host-resident ones on the host mirror) ----
     def extract_matrix(self, row_index=None, col_index=None, out=None, mask=None, accum=None, desc=None):
         """`out<mask> = accum(out, op(self)(I, J))` (reference: matrix.py:2807-2900)."""
         t0 = desc is not None and _d.T0 in desc

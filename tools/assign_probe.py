@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurement harness: index-list assign, device route (grb_assign.hip) against the host route of grb_host_ops.cpp (GRB_MI355X_ASSIGN=0: what
+"""Measurement harness: index-list assign, device route (grb_assign.hip) against the host route of grb_assign_ops.cpp (GRB_MI355X_ASSIGN=0: what
 every call took before the device route existed), same binary, process-fresh inputs.
 
   --what big     R-MAT at --scales (default 20,22), device-only C, the four selections of tests/test_assign_gpu.py: S = C[I, I] is cut out, scaled

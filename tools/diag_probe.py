@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurement harness: diagonals, device route (grb_diag.hip) against the host route of grb_host_ops.cpp (GRB_MI355X_DIAG=0: what every call took before the
+"""Measurement harness: diagonals, device route (grb_diag.hip) against the host route of grb_diag_ops.cpp (GRB_MI355X_DIAG=0: what every call took before the
 device route existed), same binary, fresh inputs per call.
 
   --what sweep   the thresholds of the dispatch of GxB_Matrix_diag (Matrix.from_diag) and GxB_Vector_diag (Matrix.vector_diag): operands of 1e2 .. 1e6 FP32

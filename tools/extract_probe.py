@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurement harness: index-list extract, device route (grb_extract.hip) against the host route of grb_host_ops.cpp (GRB_MI355X_EXTRACT=0: what
+"""Measurement harness: index-list extract, device route (grb_extract.hip) against the host route of grb_extract_ops.cpp (GRB_MI355X_EXTRACT=0: what
 every call took before the device route existed), same binary, process-fresh inputs.
 
   --what big     R-MAT at --scales (default 20,22), device-only operand, the four selections of tests/test_extract_gpu.py: HIP-event and wall

@@ -1,4 +1,4 @@
-"""Differential fuzzing of the host-mirror index operations (grb_host_ops.cpp) against a Python model of the GraphBLAS
+"""Differential fuzzing of the host-mirror index operations (grb_extract_ops.cpp, grb_assign_ops.cpp, grb_kron_ops.cpp over grb_hostmap.hpp) against a Python model of the GraphBLAS
 semantics, driven through the UNMODIFIED reference package on top of shim/ — no GPU needed (these operations edit the host
 mirror).  Run under /opt/conda/bin/python3.9 with PYTHONPATH=<repo>/shim:<reference>:
 
@@ -183,7 +183,7 @@ for case in range(args.cases):
         exp = finish(c, Z, space, mm, struct, comp, replace, scope)
         assert mdict(C) == exp, (case, kind, f, Jarg, acc, replace, struct, comp, mdict(C), exp)
     elif kind in ("hvscalar", "hmscalar"):
-        # a scalar assigned into a hypersparse container (2^60 dimensions: host-side bookkeeping, grb_host_ops.cpp host_assign_scalar):
+        # a scalar assigned into a hypersparse container (2^60 dimensions: host-side bookkeeping, grb_assign_ops.cpp host_assign_scalar):
         # either everywhere under a non-complemented mask (the pattern is bounded by the mask's), or over a short index list
         IMAX = 1 << 60
         pool = sorted({rnd.randrange(IMAX) for _ in range(6)} | {0, IMAX - 1})

@@ -532,7 +532,7 @@ GrB_Info GrBX_Vector_iseq(bool *equal, const GrB_Vector u, const GrB_Vector v); 
 GrB_Info GrBX_xcd_mapping(char *buf, int len);      /* how workgroups of a full-chip launch map to XCDs ("roundrobin8", or what was observed) */
 /* The exchange steps of the row-partitioned path (one process per GPU; RCCL over xGMI; grb_dist.cpp).  The reference has no
  * distributed code: these replace nothing in it, they are what BASELINE.json's north star adds (SURVEY.md section 8e). */
-/* Index-list extract / assign, kronecker and apply with a GxB_Scalar operand: the element-wise container surface (grb_host_ops.cpp).
+/* Index-list extract / assign, kronecker and apply with a GxB_Scalar operand: the element-wise container surface (grb_extract_ops.cpp, grb_assign_ops.cpp, grb_kron_ops.cpp, grb_apply_scalar.cpp).
  * Small host-resident containers are computed on the host mirror like setElement; extract, assign and kronecker run in HBM
  * (grb_extract.hip, grb_assign.hip, grb_kron.hip) for device-resident and large ones. */
 GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Vector u, const GrB_Index *I, GrB_Index ni, const GrB_Descriptor desc);

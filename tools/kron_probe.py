@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurement harness: the Kronecker product, device route (grb_kron.hip) against the host route of grb_host_ops.cpp (GRB_MI355X_KRON=0: what every
+"""Measurement harness: the Kronecker product, device route (grb_kron.hip) against the host route of grb_kron_ops.cpp (GRB_MI355X_KRON=0: what every
 call took before the device route existed), same binary, fresh inputs per call.
 
   --what sweep   the threshold of GrB_Matrix_kronecker_BinaryOp's dispatch: uniform random FP32 operands whose only valid image is the HOST mirror,
