@@ -79,6 +79,11 @@ vp = C.c_void_p
 u64 = C.c_uint64
 NULL = None
 
+# the two entry points that take ARRAYS of handles: their signatures are spelled out, so that a handle array or a size array cannot be passed as a scalar
+if "GxB_Matrix_concat" not in missing and "GxB_Matrix_split" in functions and "GxB_Matrix_split" not in missing:
+    lib.GxB_Matrix_concat.argtypes = [vp, C.POINTER(vp), u64, u64, vp]                                    # C, Tiles[m * n], m, n, desc
+    lib.GxB_Matrix_split.argtypes = [C.POINTER(vp), u64, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]     # Tiles[m * n], m, n, Tile_nrows[m], Tile_ncols[n], A, desc
+
 
 def init():
     info = lib.GrB_init(C.c_int(constants["GrB_NONBLOCKING"]))

@@ -33,5 +33,7 @@ constexpr uint64_t KRON_DEVICE_MIN_ENTRIES = 1000;              // provisional: 
 constexpr uint64_t DIAG_MATRIX_DEVICE_MIN_ENTRIES = 1000;       // GxB_Matrix_diag: measured, the host route is one std::map insertion per entry (0.11 ms against 0.07 ms at 1e3 entries)
 constexpr uint64_t DIAG_VECTOR_DEVICE_MIN_ENTRIES = 10000;      // GxB_Vector_diag: measured, the host route is one pass over A's tuples (0.11 ms against 0.07 ms at 1e4 entries)
 constexpr uint64_t SORT_DEVICE_MIN_ENTRIES = EXTRACT_DEVICE_MIN_ENTRIES;      // sort and top-k borrow extract's value: not measured on their own
+constexpr uint64_t CONCAT_DEVICE_MIN_ENTRIES = EXTRACT_DEVICE_MIN_ENTRIES;    // GxB_Matrix_concat, on the sum of the tiles' entries: provisional, extract's value, not measured
+constexpr uint64_t SPLIT_DEVICE_MIN_ENTRIES = EXTRACT_DEVICE_MIN_ENTRIES;     // GxB_Matrix_split, on A's entries: provisional, extract's value, not measured
 
 }  // namespace grb

@@ -715,6 +715,38 @@ class Matrix:
         check(lib.GrBX_Matrix_select_topk(out._h, C.c_void_p(op.get_op()), self._h, C.c_uint64(k), dh), out)
         return out
 
+    # ---- tiles (grb_tile_ops.cpp: in HBM for device-resident or large operands, grb_tile.hip; small host-resident ones on the host mirror) ----
+    @classmethod
+    def concat(cls, tiles, typ=None):
+        """`GxB_Matrix_concat`: the matrix made of the grid `tiles` (a list of rows, each a list of matrices): tiles of one grid row share their height, tiles
+        of one grid column their width; values are typecast to `typ` (default: the first tile's type).  The same matrix may stand at several positions."""
+        m = len(tiles); n = len(tiles[0]) if m else 0
+        if any(len(row) != n for row in tiles):
+            raise ValueError("concat: every row of the grid holds the same number of tiles")
+        if typ is None:
+            typ = tiles[0][0].type if m and n else types.BOOL
+        out = cls.sparse(typ, sum(row[0].nrows for row in tiles) if n else 0, sum(t.ncols for t in tiles[0]) if m else 0)
+        handles = (C.c_void_p * max(m * n, 1))(*[t._h.value for row in tiles for t in row])
+        check(lib.GxB_Matrix_concat(out._h, handles, u64(m), u64(n), None), out)
+        return out
+
+    def split(self, row_sizes, col_sizes):
+        """`GxB_Matrix_split`: the grid of tiles (a list of rows) that `row_sizes` x `col_sizes` cut this matrix into; the sizes add up to its shape and none
+        is 0.  `Matrix.concat(A.split(r, c))` is A again."""
+        m, n = len(row_sizes), len(col_sizes)
+        handles = (C.c_void_p * max(m * n, 1))()
+        rs, cs = (u64 * max(m, 1))(*row_sizes), (u64 * max(n, 1))(*col_sizes)
+        check(lib.GxB_Matrix_split(handles, u64(m), u64(n), rs, cs, self._h, None), self)
+        return [[Matrix(C.c_void_p(handles[a * n + b]), self.type) for b in range(n)] for a in range(m)]
+
+    @classmethod
+    def hstack(cls, tiles, typ=None):
+        return cls.concat([list(tiles)], typ)
+
+    @classmethod
+    def vstack(cls, tiles, typ=None):
+        return cls.concat([[t] for t in tiles], typ)
+
     def kronecker(self, other, op=None, cast=None, out=None, mask=None, accum=None, desc=None):
         """Kronecker product (reference: matrix.py:2728-2805)."""
         if op is None:

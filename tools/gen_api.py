@@ -561,6 +561,18 @@ GrB_Info GxB_Vector_sort(GrB_Vector w, GrB_Vector p, const GrB_BinaryOp op, cons
 GrB_Info GrBX_Matrix_select_topk(GrB_Matrix C, const GrB_BinaryOp op, const GrB_Matrix A, GrB_Index k, const GrB_Descriptor desc);
 GrB_Info GrBX_Vector_select_topk(GrB_Vector w, const GrB_BinaryOp op, const GrB_Vector u, GrB_Index k, const GrB_Descriptor desc);
 GrB_Info GrBX_sort_thresholds(uint64_t *wave_max, uint64_t *lds_max);   /* the longest row one wave sorts in registers, the longest one workgroup sorts in LDS (longer rows: segmented radix sort) */
+/* Tiling (the SuiteSparse 5.1 entry points).  Tiles is an m x n grid, row-major: tile (a, b) is Tiles[a*n + b].
+   concat: C exists (any real built-in type); its previous content is discarded.  Tiles of a tile-row share nrows, tiles of a tile-column ncols, the sums are C's
+   shape (else GrB_DIMENSION_MISMATCH); m == 0, n == 0 or C among the tiles is GrB_INVALID_VALUE; a NULL array or tile GrB_NULL_POINTER.  The same tile may stand
+   at several positions.  Values are typecast to C's type.  No mask, no accumulator; the descriptor may be NULL and is ignored.
+   split: creates m n new matrices of A's type, Tile_nrows[a] x Tile_ncols[b]; the sizes add up to A's shape (else GrB_DIMENSION_MISMATCH); a size of 0, m == 0 or
+   n == 0 is GrB_INVALID_VALUE.  On any failure no handle stays allocated and Tiles[] is left as it was.  A is only read.
+   The device route (GRB_MI355X_TILE: 0 host, 1 device) leaves "concat<m=M,n=N,cast=K> k_concat_count k_concat_fill" or "split<m=M,n=N> k_split_count k_split_totals
+   k_split_rowptr k_split_scatter" in GrBX_last_kernel_plan; its results live in HBM only. */
+GrB_Info GxB_Matrix_concat(GrB_Matrix C, const GrB_Matrix *Tiles, const GrB_Index m, const GrB_Index n, const GrB_Descriptor desc);
+GrB_Info GxB_Matrix_split(GrB_Matrix *Tiles, const GrB_Index m, const GrB_Index n, const GrB_Index *Tile_nrows, const GrB_Index *Tile_ncols, const GrB_Matrix A, const GrB_Descriptor desc);
+GrB_Info GrBX_tile_thresholds(uint64_t *concat_min_entries, uint64_t *split_min_entries);   /* entries (the sum over the tiles / of A) from which host-resident operands take the device route (an operand that lives in HBM only always does) */
+GrB_Info GrBX_tile_geometry(uint64_t *out);   /* out[0] entries per chunk of the two fill kernels, out[1] their grid cap in workgroups, out[2] consecutive entries one lane of the concat fill stores: what the tests take their edges from */
 /* build from tuples that may live in HBM: I / J are 64-bit indices, X holds values of the container's own type; location 0 = host arrays,
    1 = device arrays (read where they are on the device route, downloaded once for the host route).  Same outcomes as GrB_*_build_<T>. */
 GrB_Info GrBX_Matrix_build_at(GrB_Matrix C, const GrB_Index *I, const GrB_Index *J, const void *X, GrB_Index nvals, const GrB_BinaryOp dup, int location);
