@@ -1,7 +1,7 @@
 // grb_build.hip — GrB_Matrix_build / GrB_Vector_build in HBM: tuples (I, J, X) in any order, duplicates included, to the sorted distinct positions with the
-// duplicates folded LEFT TO RIGHT IN INPUT ORDER — z = dup(dup(dup(x0, x1), x2), ...), the order SuiteSparse and the host route (build_tuples, grb_container.cpp)
+// duplicates folded LEFT TO RIGHT IN INPUT ORDER — z = dup(dup(dup(x0, x1), x2), ...), the order SuiteSparse and the host route (build_tuples, grb_build_ops.cpp)
 // define; FP PLUS / TIMES are not bit-associative and FIRST / SECOND / MINUS are not commutative, so the order is part of the result.  The routes are in
-// grb_container.cpp, the key arithmetic and the thresholds in grb_build_keys.hpp.  All kernels are streaming or gather passes: wave64, 256 threads, grid-stride
+// grb_build_ops.cpp, the key arithmetic and the thresholds in grb_build_keys.hpp.  All kernels are streaming or gather passes: wave64, 256 threads, grid-stride
 // (grid_1d), no LDS, plain vector stores; the only atomic is one max per wave of k_build_runmax.
 //
 //   k_build_keys     one pass over I, J as 64-bit values: the bounds test (on the full values, before anything is truncated), key = (i << cbits) | j as a 32- or

@@ -1,4 +1,4 @@
-// grb_build.hpp — host interface of build-from-tuples in HBM (grb_build.hip); the routes are mat_build / vec_build in grb_container.cpp, the key arithmetic and the
+// grb_build.hpp — host interface of build-from-tuples in HBM (grb_build.hip); the routes are mat_build / vec_build in grb_build_ops.cpp, the key arithmetic and the
 // thresholds are in grb_build_keys.hpp.
 #pragma once
 #include "grb_internal.hpp"

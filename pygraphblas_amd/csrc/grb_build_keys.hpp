@@ -1,4 +1,4 @@
-// grb_build_keys.hpp — the integer side of build-from-tuples on the device (grb_build.hip, mat_build / vec_build in grb_container.cpp): how a tuple's
+// grb_build_keys.hpp — the integer side of build-from-tuples on the device (grb_build.hip, mat_build / vec_build in grb_build_ops.cpp): how a tuple's
 // (i, j) packs into one sort key, which key width a pair of dimensions needs, the bounds test on the 64-bit indices as the C ABI hands them over, the three
 // thresholds, and the route predicate.  Plain integers only — no HIP types, no containers — so that a stand-alone program can check it under the sanitizers
 // (tests/build_keys_check.cpp).  Every function is constexpr: host code and the kernels call the same text.

@@ -2,7 +2,7 @@
 // that the reference's type registry (pygraphblas/types.py:87-110 resolves 17 typed functions for each of its 13
 // types) can import; complex arithmetic is out of scope for the MI355X backend and each reports GrB_DOMAIN_MISMATCH.
 // (Storing complex entries — build / setElement / extractElement / extractTuples / assign of a scalar — is host-side
-// container work and lives in grb_container.cpp and grb_assign_ops.cpp.)
+// container work and lives behind the typed families of grb_container.cpp (grb_build_ops.cpp, grb_edit_ops.cpp, grb_tuples_ops.cpp) and in grb_assign_ops.cpp.)
 #include "grb_api.hpp"
 
 typedef struct { float re; float im; } GxB_FC32_t;

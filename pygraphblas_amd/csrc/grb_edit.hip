@@ -1,4 +1,4 @@
-// grb_edit.hip — element edits applied to a container in HBM (the flush of the edit queue, grb_container.cpp), and the pieces of a resize that stays there.
+// grb_edit.hip — element edits applied to a container in HBM (the flush of the edit queue, grb_edit_ops.cpp), and the pieces of a resize that stays there.
 // The list arithmetic (classes, prefix arrays, destinations) is grb_edit_list.hpp's, shared with the host check of tests/edit_list_check.cpp.
 //
 //   csr_apply_edits   k edits in (row, column) order, one per coordinate.

@@ -1,5 +1,5 @@
 // grb_edit.hpp — host interface of the in-place edit kernels (grb_edit.hip): a normalised list of element edits applied to a CSR or a vector bitmap in HBM,
-// and the pieces of a resize that stays in HBM.  The list arithmetic is in grb_edit_list.hpp; the queue and its flush points are in grb_container.cpp.
+// and the pieces of a resize that stays in HBM.  The list arithmetic is in grb_edit_list.hpp; the queue and its flushes are in grb_edit_ops.cpp.
 #pragma once
 #include "grb_internal.hpp"
 

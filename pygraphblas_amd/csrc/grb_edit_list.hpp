@@ -10,9 +10,11 @@
 //                    stored entry whose coordinate is not below edit e's (non-decreasing in e), so "edits before the coordinate of p" is an upper bound of p
 //                    in pos[], less the one edit that names p's own coordinate (the last with pos == p, an overwrite or a delete).
 //   edit_lookup      the answer of the queue to a read of one coordinate: the last record that names it.
+//   edit_merge_host  the same queue applied to a HOST mirror (tuples sorted by coordinate, values packed): the merge of mat_host_assemble / vec_host_assemble.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include <string.h>
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -73,6 +75,49 @@ GRB_EDIT_HD uint32_t edit_own_dest(const uint32_t* pos, const uint32_t* insb, co
 template <class P, class Same> inline const P* edit_lookup(const std::vector<P>& q, Same names) {
   for (size_t k = q.size(); k-- > 0;) if (names(q[k])) return &q[k];
   return nullptr;
+}
+
+// ---- the queue applied to a host mirror --------------------------------------------------------------------------------------------------------------
+// Sorted tuples: `hi`, with `hj` for a matrix (nullptr: a vector, every column reads 0), values in `hx` at `ts` bytes each.
+// the first position whose coordinate is not below (i, j) ...
+inline size_t tuples_lower_bound(const std::vector<uint64_t>& hi, const std::vector<uint64_t>* hj, uint64_t i, uint64_t j) {
+  size_t lo = 0, end = hi.size();
+  while (lo < end) { const size_t m = lo + (end - lo) / 2; if (hi[m] < i || (hj && hi[m] == i && (*hj)[m] < j)) lo = m + 1; else end = m; }
+  return lo;
+}
+// ... and whether position p holds exactly (i, j)
+inline bool tuples_hold(const std::vector<uint64_t>& hi, const std::vector<uint64_t>* hj, size_t p, uint64_t i, uint64_t j) {
+  return p < hi.size() && hi[p] == i && (!hj || (*hj)[p] == j);
+}
+constexpr size_t EDIT_IN_PLACE_MAX = 8;      // a queue this short edits the arrays where they are
+// Applies the queue in program order: per coordinate the last record wins, a delete of an absent entry does nothing.  The queue itself is left as it was.
+template <class P>
+inline void edit_merge_host(std::vector<uint64_t>& hi, std::vector<uint64_t>* hj, std::vector<uint8_t>& hx, size_t ts, const std::vector<P>& q) {
+  constexpr bool has_j = requires(const P& r) { r.j; };
+  auto col = [](const P& r) -> uint64_t { if constexpr (has_j) return r.j; else return 0; };
+  if (q.size() <= EDIT_IN_PLACE_MAX) {      // a few edits (`M[i, j] = x` then a read): one memmove each, instead of rebuilding the tuple arrays
+    for (const P& e : q) {
+      const size_t p = tuples_lower_bound(hi, hj, e.i, col(e)); const bool found = tuples_hold(hi, hj, p, e.i, col(e));
+      if (e.del) { if (found) { hi.erase(hi.begin() + p); if (hj) hj->erase(hj->begin() + p); hx.erase(hx.begin() + p * ts, hx.begin() + (p + 1) * ts); } }
+      else if (found) memcpy(&hx[p * ts], e.x, ts);
+      else { hi.insert(hi.begin() + p, e.i); if (hj) hj->insert(hj->begin() + p, col(e)); hx.insert(hx.begin() + p * ts, e.x, e.x + ts); }
+    }
+    return;
+  }
+  std::vector<uint32_t> ord;
+  if constexpr (has_j) ord = edit_normalise_ij(q); else ord = edit_normalise_i(q);
+  const size_t nb = hi.size(); size_t b = 0;
+  std::vector<uint64_t> ni, nj; std::vector<uint8_t> nx;
+  ni.reserve(nb + ord.size()); if (hj) nj.reserve(nb + ord.size()); nx.reserve((nb + ord.size()) * ts);
+  auto push_base = [&](size_t s) { ni.push_back(hi[s]); if (hj) nj.push_back((*hj)[s]); nx.insert(nx.end(), &hx[s * ts], &hx[s * ts] + ts); };
+  for (const uint32_t o : ord) {
+    const P& e = q[o];
+    while (b < nb && (hi[b] < e.i || (hj && hi[b] == e.i && (*hj)[b] < col(e)))) push_base(b++);
+    if (tuples_hold(hi, hj, b, e.i, col(e))) b++;      // replaced or deleted
+    if (!e.del) { ni.push_back(e.i); if (hj) nj.push_back(col(e)); nx.insert(nx.end(), e.x, e.x + ts); }
+  }
+  while (b < nb) push_base(b++);
+  hi.swap(ni); if (hj) hj->swap(nj); hx.swap(nx);
 }
 
 }  // namespace grb

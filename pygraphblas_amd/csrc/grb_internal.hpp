@@ -101,7 +101,7 @@ struct GrB_Matrix_opaque {
   bool iso_full = false; uint8_t iso_val[16] = {0};
   // device
   bool dev_valid = false;
-  uint32_t dev_elem_ops = 0; // element reads / writes served on the device in a row (grb_container.cpp: after a few dozen the host mirror takes over)
+  uint32_t dev_elem_ops = 0; // element reads / writes served on the device in a row (grb_edit_ops.cpp: after a few dozen the host mirror takes over)
   grb::DevCSR csr;          // by-row
   grb::DevCSR csc;          // CSR of the transpose (cached; invalidated with csr)
   grb::DevBitmap bm;        // the bitmap form of a batch matrix (cached beside the CSR, or the only valid form)
@@ -130,10 +130,10 @@ struct GrB_Vector_opaque {
   //            accumulates into w with its monoid's operator folds the fill into its own store; anything else materialises it.
   // lazy == 2: w is the output of queued element-wise operations (its stored value, if any, is the old one).
   // q_reads:   queued operations that read this vector's stored value — it must not change before they ran.
-  // Every access goes through vec_gate() (vec_to_device / vec_to_host / vec_nvals / the entry points of grb_container.cpp).
+  // Every access goes through vec_gate() (vec_to_device / vec_to_host / vec_nvals in grb_mirror.cpp / the entry points of grb_container.cpp).
   int lazy = 0; uint8_t lazy_fill[16] = {0}; int q_reads = 0;
   grb::DevBuf dcode;   // the buffer of the code bytes (facts.code_valid): a buffer, not a fact — kept across the transitions and reused
-  uint32_t dev_elem_ops = 0;   // element reads served on the device in a row (grb_container.cpp: after a few dozen the host mirror takes over)
+  uint32_t dev_elem_ops = 0;   // element reads served on the device in a row (grb_edit_ops.cpp: after a few dozen the host mirror takes over)
   int sparsity_control = 15;
   std::string err;
 };
@@ -150,7 +150,7 @@ typedef GxB_Scalar_opaque* GxB_Scalar;
 
 namespace grb {
 
-// ---- containers (grb_container.cpp) ----------------------------------------------------------
+// ---- containers (the images and their transitions: grb_mirror.cpp; what only the object-model files share: grb_container.hpp) ----
 void mat_host_assemble(GrB_Matrix A);     // apply pending edits to the host mirror
 void mat_to_host(GrB_Matrix A);           // ensure host mirror valid (downloads if needed)
 void mat_to_device(GrB_Matrix A);         // ensure device CSR valid (assembles + uploads)
@@ -173,7 +173,7 @@ void hyper_mat_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryO
 void host_assign_scalar(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, GrB_Descriptor desc);
 void host_assign_scalar(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, GrB_Descriptor desc);
 void vec_resolve(GrB_Vector v);           // complete deferred work that involves v (grb_lazy.cpp)
-// the edit queue of a container that lives in HBM only (grb_container.cpp): `pending` with host_valid == false holds setElement / removeElement records that the
+// the edit queue of a container that lives in HBM only (grb_edit_ops.cpp): `pending` with host_valid == false holds setElement / removeElement records that the
 // device image has not seen yet; they are applied there (grb_edit.hip) before anything reads or replaces that image
 inline bool mat_edits_queued(const GrB_Matrix_opaque* A) { return !A->pending.empty() && !A->host_valid; }
 inline bool vec_edits_queued(const GrB_Vector_opaque* v) { return !v->pending.empty() && !v->host_valid; }
@@ -181,7 +181,7 @@ void mat_edit_flush(GrB_Matrix A);
 void vec_edit_flush(GrB_Vector v);
 inline void vec_gate(GrB_Vector v) { if (v->lazy | v->q_reads) vec_resolve(v); if (vec_edits_queued(v)) vec_edit_flush(v); }
 void vec_overwritten(GrB_Vector v);       // v's value is about to be replaced as a whole: deferred work that only produced it is dropped
-uint32_t* any_true_acquire(uint32_t* tag);        // a device word a BOOL product kernel sets to the (fresh, non-zero) tag when it writes a true value (see VecFacts::lor_state)
+uint32_t* any_true_acquire(uint32_t* tag);        // (grb_any_true.cpp) a device word a BOOL product kernel sets to the (fresh, non-zero) tag when it writes a true value (see VecFacts::lor_state)
 void any_true_written(GrB_Vector w_or_null, const void* key, uint32_t tag, uint64_t fe_key = 0, uint32_t fe_nblocks = 0);    // a kernel honoured it; w's device buffers `key` are the result it describes (nullptr: nobody's); fe_key != 0: the kernel also filled the edge summary (counted in the row pointers with that serial)
 bool dist_exchange_pending();                   // grb_dist.cpp: GrBX_Vector_allgatherv_start without its GrBX_dist_wait yet
 // GRB_MI355X_DETERMINISTIC=1: floating-point PLUS results are the same bits in every run (mxm: grb_matrix_ops.cpp; vxm / mxv: no push step, whose atomics land in any order)
@@ -210,7 +210,7 @@ inline bool dev_capable(GrB_Vector v) { return !v || (!is_hyper(v) && v->type->c
 inline bool mat_capable(GrB_Matrix A) { return dev_capable(A) && !(A && mat_bitmap_only(A)); }
 inline bool hbm_only(GrB_Matrix A) { return A->dev_valid && !A->host_valid; }      // it lives in HBM: it is not downloaded to pick a route
 inline bool hbm_only(GrB_Vector v) { return v->dev_valid && !v->host_valid; }
-// (the count of a valid host mirror, or of the device CSR: no device work.  With element edits queued on an HBM-only matrix — grb_container.cpp — the CSR header is read
+// (the count of a valid host mirror, or of the device CSR: no device work.  With element edits queued on an HBM-only matrix — grb_edit_ops.cpp — the CSR header is read
 //  WITHOUT a flush here: the count is off by at most the queue's length, and it only picks a route.)
 inline uint64_t entries_of(GrB_Matrix A) { return A->host_valid ? mat_nvals(A) : (uint64_t)A->csr.nnz; }
 inline uint64_t entries_known(GrB_Vector u) { return u->host_valid ? vec_nvals(u) : (u->facts.dnvals_known ? u->facts.dnvals : 0); }      // (no device work for a count)

@@ -10,7 +10,7 @@
 //   * eWiseAdd / eWiseMult / apply without mask and accumulator, every operand of the operator's type
 //        -> a node of a short queue (<= 4 steps over <= 4 stored operands, each step reading stored vectors or the result of
 //        the step before it).  The queue runs as ONE kernel (k_vec_chain, grb_lazy_kernels.hip) when any vector it involves
-//        is next accessed (vec_gate in grb_container.cpp) — `t -= r; t = abs(t); t.reduce_float()` is one pass that also
+//        is next accessed (vec_gate in grb_internal.hpp) — `t -= r; t = abs(t); t.reduce_float()` is one pass that also
 //        produces the reduction, `w = t / d` writes zeros into the positions without an entry so that the product can gather
 //        from it without a cast-and-fill pass.
 //

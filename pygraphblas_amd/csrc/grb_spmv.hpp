@@ -10,6 +10,7 @@ constexpr int SPMV_NNZ = 2048;          // entries per stream block  (LDS: 2048 
 constexpr int SPMV_UNROLL = SPMV_NNZ / SPMV_THREADS;
 constexpr int SPMV_LONG_CHUNK = 8192;   // entries per part of a long row
 constexpr int SPMV_MAX_ROWS = 1024;     // rows per stream block (bounds runs of empty rows)
+constexpr uint32_t FE_MAX_BLOCKS = 2048; // workgroups that report into the result summary of a BOOL product (SpmvCall::fe_host; grb_any_true.cpp allocates a host word for each)
 
 struct SpmvBlock { uint32_t row, aux, nparts, slot; };
 // stream block : rows [row, aux), nparts == 0

@@ -333,7 +333,6 @@ __global__ __launch_bounds__(1024) void k_spmv_rowlane(const SpmvKArgs<T> a, con
 
 
 constexpr int SPMV_LANE_K = 4;
-constexpr uint32_t FE_MAX_BLOCKS = 2048;      // pairs of host words of the result summary (grb_container.cpp allocates them)
 // Round 5: a lane owns SPMV_LANE_K rows at once (rows r, r + 64, r + 128, r + 192 of the wave's 256).  A row is a chain of four dependent
 // loads — mask byte / row pointers, column, operand byte — and with one row per lane a wave had 64 chains in flight and nothing to do
 // while they were: the level-2 pull of the R-MAT-22 BFS took 54 us for 64 MB, the late levels 17 us each for a handful of vertices

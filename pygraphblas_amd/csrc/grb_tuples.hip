@@ -1,6 +1,6 @@
 // grb_tuples.hip — extractTuples in HBM: a device CSR to the lists (I, J, X), a bitmap vector to the ordered lists (I, X), the outputs 64-bit indices and values
 // of the container's own type in arrays the caller owns (torch tensors, usually).  The entry points and what they do before the kernels run (the flush, the
-// upload of a host-resident container, the capacity test) are GrBX_*_extractTuples_at in grb_container.cpp; the tile arithmetic is grb_tuples_geom.hpp.
+// upload of a host-resident container, the capacity test) are GrBX_*_extractTuples_at in grb_tuples_ops.cpp; the tile arithmetic is grb_tuples_geom.hpp.
 // All kernels: wave64, 256 threads, a capped grid with a loop past the cap, no LDS, no atomics, plain vector stores.
 //
 //   k_tuples_csr<TS>    one pass over tiles of TUPLES_TILE consecutive ENTRIES.  Per entry it reads col (4 B) and val (TS B) and writes I (8 B), J (8 B, the

@@ -1,5 +1,5 @@
 // grb_tuples.hpp — host interface of extractTuples in HBM (grb_tuples.hip); the entry points are GrBX_Matrix_extractTuples_at / GrBX_Vector_extractTuples_at in
-// grb_container.cpp, the tile arithmetic is in grb_tuples_geom.hpp.
+// grb_tuples_ops.cpp, the tile arithmetic is in grb_tuples_geom.hpp.
 #pragma once
 #include "grb_internal.hpp"
 #include "grb_tuples_geom.hpp"

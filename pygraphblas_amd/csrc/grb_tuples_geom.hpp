@@ -1,4 +1,4 @@
-// grb_tuples_geom.hpp — the integer side of extractTuples in HBM (grb_tuples.hip, GrBX_*_extractTuples_at in grb_container.cpp): the tile sizes, the grid, which
+// grb_tuples_geom.hpp — the integer side of extractTuples in HBM (grb_tuples.hip, GrBX_*_extractTuples_at in grb_tuples_ops.cpp): the tile sizes, the grid, which
 // entries and positions a tile holds, the row of an entry by bisection of the row pointer, and the 16-byte alignment test of the output streams.  Plain integers
 // only — no HIP types, no containers — so that a stand-alone program can check it under the sanitizers (tests/tuples_geometry_check.cpp).  Every function is
 // constexpr: host code and the kernels call the same text.

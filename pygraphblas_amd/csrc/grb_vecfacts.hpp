@@ -23,7 +23,7 @@ struct VecFacts {
   bool holes_zero = false;     // the device values of absent positions are all-zero bits (written so by the element-wise chain kernel)
   bool holes_big = false; uint8_t holes_big_val[16] = {0};      // ... or all hold this value of the vector's type (the BIG fill of a MIN_PLUS / MAX_PLUS sweep, grb_mxv.cpp)
   // BOOL vectors: "is any stored value true", recorded by the product kernel that wrote the device buffers `lor_key`
-  // (0 unknown, 1 in the device word of grb_container.cpp's any_true_*, 2 false, 3 true) — `while q.reduce_bool()` of a BFS loop
+  // (0 unknown, 1 in the device word of grb_any_true.cpp, 2 false, 3 true) — `while q.reduce_bool()` of a BFS loop
   uint8_t lor_state = 0; uint32_t lor_tag = 0; const void* lor_key = nullptr;
   // an upper bound of |value| over the stored entries, left behind by the "big holes" product that wrote them (grb_mxv.cpp: the next
   // sweep of a shortest-path loop needs no range kernel and no read-back); < 0 = unknown

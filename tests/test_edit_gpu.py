@@ -1,4 +1,4 @@
-"""Element edits and resize of containers that live in HBM only (grb_edit.hip behind setElement / removeElement / resize, the queue in grb_container.cpp).
+"""Element edits and resize of containers that live in HBM only (grb_edit.hip behind setElement / removeElement / resize, the queue in grb_edit_ops.cpp).
 
 The model is a Python dict replayed edit by edit; values are small integers, so every comparison is exact.  Containers are imported straight into HBM
 (`from_csr` / `from_dense_array` copy host arrays into fresh device allocations: no host mirror) or are the output of an operation, and residency 2 is asserted

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measurement harness: build from tuples, device route (grb_build.hip) against the host route of grb_container.cpp (GRB_MI355X_BUILD=0: the stable sort of an
+"""Measurement harness: build from tuples, device route (grb_build.hip) against the host route of grb_build_ops.cpp (GRB_MI355X_BUILD=0: the stable sort of an
 index permutation on one thread that every call took before the device route existed), same binary, same tuples.
 
   --what sweep   BUILD_DEVICE_MIN_TUPLES: Matrix.from_arrays of 1e2 .. 1e7 FP64 tuples with ~5 % duplicates and dup = PLUS, from host arrays, one call on each
