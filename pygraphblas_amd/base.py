@@ -83,3 +83,20 @@ def check(info, obj=None):
         if fn(C.byref(s), obj._h) == 0 and s.value:
             msg = s.value.decode()
     raise _error_codes.get(info, GraphBLASException)(msg or f"GrB_Info {info}")
+
+
+def eunion(fn, out, mh, ah, op, left, alpha, right, beta, dh, typ):
+    """`GxB_*_eWiseUnion` (`fn`) with the Python numbers `alpha` / `beta` in two `GxB_Scalar`s of type `typ`, made for the call and freed after it (as `select`
+    makes its thunk): what `Matrix.eunion` and `Vector.eunion` share."""
+    scalars = []
+    try:
+        for value in (alpha, beta):
+            s = C.c_void_p()
+            check(lib.GxB_Scalar_new(C.byref(s), C.c_void_p(typ._h)))
+            scalars.append(s)
+            check(getattr(lib, "GxB_Scalar_setElement_" + typ.__name__)(s, typ._c(value)))
+        check(fn(out._h, mh, ah, C.c_void_p(op.get_op()), left._h, scalars[0], right._h, scalars[1], dh), out)
+    finally:
+        for s in scalars:
+            lib.GxB_Scalar_free(C.byref(s))
+    return out

@@ -49,7 +49,7 @@ void region_replace(GrB_Matrix C, GrB_Matrix Mask, const DescView& dv, DevCSR& T
   if (!Rest.nnz) { matrix_write_back(C, T, tcode, Mask, dv, nullptr, false); return; }
   if (!T.nnz) { matrix_write_back(C, Rest, ccode, Mask, dv, nullptr, false); return; }
   DevBuf tc; const void* tv = cast_values(ccode, tcode, T.val.p, T.nnz, tc);
-  DevCSR Z; csr_ewise(ccode, Rest, Rest.val.p, T, tv, B_SECOND, true, Z);
+  DevCSR Z; csr_ewise(ccode, Rest, Rest.val.p, T, tv, B_SECOND, EW_ADD, Z);
   matrix_write_back(C, Z, ccode, Mask, dv, nullptr, false);
 }
 

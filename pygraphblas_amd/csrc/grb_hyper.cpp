@@ -13,7 +13,7 @@
 //     4. the output's indices mapped back.
 //
 // Steps 1, 2 and 4 are host-side bookkeeping over the entries of the operands (hypersparse containers live on the host
-// mirror anyway); the arithmetic is the device's.  Covered: GrB_mxm, GrB_mxv, GrB_vxm and the eWiseAdd / eWiseMult of
+// mirror anyway); the arithmetic is the device's.  Covered: GrB_mxm, GrB_mxv, GrB_vxm and the eWiseAdd / eWiseMult / eWiseUnion of
 // vectors and matrices (what the reference's loops wrap around the products: `w.iseq(v)`, `v @= M`).
 #include "grb_opcommon.hpp"
 #include <algorithm>
@@ -26,6 +26,8 @@ GrB_Info GrB_Vector_eWiseAdd_BinaryOp(GrB_Vector, const GrB_Vector, const GrB_Bi
 GrB_Info GrB_Vector_eWiseMult_BinaryOp(GrB_Vector, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Vector, const GrB_Vector, const GrB_Descriptor);
 GrB_Info GrB_Matrix_eWiseAdd_BinaryOp(GrB_Matrix, const GrB_Matrix, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, const GrB_Matrix, const GrB_Descriptor);
 GrB_Info GrB_Matrix_eWiseMult_BinaryOp(GrB_Matrix, const GrB_Matrix, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, const GrB_Matrix, const GrB_Descriptor);
+GrB_Info GxB_Vector_eWiseUnion(GrB_Vector, const GrB_Vector, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Vector, const GxB_Scalar, const GrB_Vector, const GxB_Scalar, const GrB_Descriptor);
+GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix, const GrB_Matrix, const GrB_BinaryOp, const GrB_BinaryOp, const GrB_Matrix, const GxB_Scalar, const GrB_Matrix, const GxB_Scalar, const GrB_Descriptor);
 GrB_Info GrB_Matrix_new(GrB_Matrix*, GrB_Type, GrB_Index, GrB_Index);
 GrB_Info GrB_Vector_new(GrB_Vector*, GrB_Type, GrB_Index);
 GrB_Info GrB_Matrix_free(GrB_Matrix*);
@@ -140,18 +142,19 @@ void hyper_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semi
   g_last_plan = "hypersparse<" + std::to_string(R.ids.size()) + "x" + std::to_string(K.ids.size()) + "x" + std::to_string(Cc.ids.size()) + "> " + g_last_plan;
 }
 
-void hyper_vec_ewise(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v, GrB_Descriptor desc, bool is_union) {
+void hyper_vec_ewise(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v, GrB_Descriptor desc, const EwiseMode& mode) {
   if (!check_obj(u) || !check_obj(v) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "eWise: uninitialised operand");
   const uint64_t n = w->n;
   if (u->n != n || v->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "eWise: vector sizes differ");
   Universe U; indices(w, U); indices(mask, U); indices(u, U); indices(v, U); U.seal();
   TempV w2, m2, u2, v2;
   compact(w2, w, U); compact(m2, mask, U); compact(u2, u, U); compact(v2, v, U);
-  relay(is_union ? GrB_Vector_eWiseAdd_BinaryOp(w2.v, m2.v, accum, op, u2.v, v2.v, desc) : GrB_Vector_eWiseMult_BinaryOp(w2.v, m2.v, accum, op, u2.v, v2.v, desc), w2.v->err, "eWise");
+  relay(mode.fills() ? GxB_Vector_eWiseUnion(w2.v, m2.v, accum, op, u2.v, mode.alpha, v2.v, mode.beta, desc)      // (the relabelling is that of a union: the scalars pass through)
+        : mode.whole() ? GrB_Vector_eWiseAdd_BinaryOp(w2.v, m2.v, accum, op, u2.v, v2.v, desc) : GrB_Vector_eWiseMult_BinaryOp(w2.v, m2.v, accum, op, u2.v, v2.v, desc), w2.v->err, "eWise");
   expand(w, w2.v, U);
 }
 
-void hyper_mat_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, bool is_union) {
+void hyper_mat_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, const EwiseMode& mode) {
   check_mat(A, "eWise"); check_mat(B, "eWise"); if (M) check_mat(M, "eWise");
   const DescView dv(desc);
   const uint64_t ar = dv.tran0 ? A->ncols : A->nrows, ac = dv.tran0 ? A->nrows : A->ncols;
@@ -164,7 +167,8 @@ void hyper_mat_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryO
   if (dv.tran0) compact(a, A, Cc, R); else compact(a, A, R, Cc);
   if (dv.tran1) compact(b, B, Cc, R); else compact(b, B, R, Cc);
   compact(c, C, R, Cc); compact(m, M, R, Cc);
-  relay(is_union ? GrB_Matrix_eWiseAdd_BinaryOp(c.m, m.m, accum, op, a.m, b.m, desc) : GrB_Matrix_eWiseMult_BinaryOp(c.m, m.m, accum, op, a.m, b.m, desc), c.m->err, "eWise");
+  relay(mode.fills() ? GxB_Matrix_eWiseUnion(c.m, m.m, accum, op, a.m, mode.alpha, b.m, mode.beta, desc)
+        : mode.whole() ? GrB_Matrix_eWiseAdd_BinaryOp(c.m, m.m, accum, op, a.m, b.m, desc) : GrB_Matrix_eWiseMult_BinaryOp(c.m, m.m, accum, op, a.m, b.m, desc), c.m->err, "eWise");
   expand(C, c.m, R, Cc);
 }
 

@@ -167,8 +167,18 @@ inline bool mat_bitmap_only(GrB_Matrix A) { return A->bm.valid && !A->dev_valid 
 bool is_hyper(const GrB_Matrix_opaque* A); bool is_hyper(const GrB_Vector_opaque* v);
 void hyper_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u, GrB_Descriptor desc, bool is_vxm);
 void hyper_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc);
-void hyper_vec_ewise(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v, GrB_Descriptor desc, bool is_union);
-void hyper_mat_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, bool is_union);
+// What an element-wise operation makes of a position only ONE operand holds: eWiseMult has no entry there, eWiseAdd copies the operand's (the operator is not
+// called), GxB_eWiseUnion calls the operator with a scalar in the missing operand's place — op(a, beta) / op(alpha, b).  (0 / 1: what `bool is_union` was.)
+enum EwiseKind { EW_MULT = 0, EW_ADD = 1, EW_UNION = 2 };
+struct EwiseMode {
+  int kind; GxB_Scalar alpha = nullptr, beta = nullptr;      // the union's scalars as the caller gave them (checked: initialised, with an entry, not complex)
+  bool whole() const { return kind != EW_MULT; }              // T's pattern is the union of the operands' patterns (else the intersection)
+  bool fills() const { return kind == EW_UNION; }
+  // alpha in the operator's x type, beta in its y type (16 bytes each), as the bound scalar of apply_BinaryOp1st / 2nd is cast
+  void cast_fill(int xcode, int ycode, uint8_t* a16, uint8_t* b16) const;
+};
+void hyper_vec_ewise(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v, GrB_Descriptor desc, const EwiseMode& mode);
+void hyper_mat_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, const EwiseMode& mode);
 // scalar into a region on the host mirror (grb_assign_ops.cpp): for complex containers and for dimensions beyond the device layout
 void host_assign_scalar(GrB_Matrix C, GrB_Matrix Mask, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, const GrB_Index* J, GrB_Index nj, GrB_Descriptor desc);
 void host_assign_scalar(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const void* x, int xcode, const GrB_Index* I, GrB_Index ni, GrB_Descriptor desc);

@@ -151,35 +151,39 @@ static __global__ void k_merge_emit(uint64_t n, const unsigned long long* __rest
 static __global__ void k_merge_rowptr(const uint32_t* __restrict__ arp, const uint32_t* __restrict__ brp, uint32_t nrows, const uint32_t* __restrict__ pos, uint32_t* __restrict__ orp) {
   for (uint64_t r = blockIdx.x * 256ull + threadIdx.x; r <= nrows; r += (uint64_t)gridDim.x * 256ull) orp[r] = pos[(uint64_t)arp[r] + brp[r]];
 }
+// `fills` (GxB_eWiseUnion, wave-uniform): an entry of one operand alone is op(a, beta) / op(alpha, b) — the tag bit of idx says whose it is — where eWiseAdd copies it.
 template <class T, bool MATH> __global__ void k_merge_fill(uint64_t n, const unsigned long long* __restrict__ key, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ e,
-                                                           const uint32_t* __restrict__ pos, const T* __restrict__ aval, const T* __restrict__ bval, int op, uint32_t* __restrict__ ocol, T* __restrict__ oval) {
+                                                           const uint32_t* __restrict__ pos, const T* __restrict__ aval, const T* __restrict__ bval, int op, bool fills, T alpha, T beta,
+                                                           uint32_t* __restrict__ ocol, T* __restrict__ oval) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) if (e[i]) {
     const uint32_t w = pos[i]; const unsigned long long k = key[i]; const uint32_t x = idx[i];
-    const bool both = i + 1 < n && key[i + 1] == k;
-    T v;
-    if (both) { const uint32_t x2 = idx[i + 1]; const uint32_t xa = (x & 0x80000000u) ? x2 : x, xb = (x & 0x80000000u) ? x : x2;     // (whichever of the two came first)
-                v = apply_binop<T, true, MATH>(op, aval[xa & 0x7FFFFFFFu], bval[xb & 0x7FFFFFFFu]); }
-    else v = (x & 0x80000000u) ? bval[x & 0x7FFFFFFFu] : aval[x];
-    ocol[w] = (uint32_t)k; oval[w] = v;
+    const bool both = i + 1 < n && key[i + 1] == k, from_b = (x & 0x80000000u) != 0;
+    T a = alpha, b = beta;
+    if (both) { const uint32_t x2 = idx[i + 1]; const uint32_t xa = from_b ? x2 : x, xb = from_b ? x : x2;     // (whichever of the two came first)
+                a = aval[xa & 0x7FFFFFFFu]; b = bval[xb & 0x7FFFFFFFu]; }
+    else if (from_b) b = bval[x & 0x7FFFFFFFu];
+    else a = aval[x];
+    ocol[w] = (uint32_t)k; oval[w] = (both || fills) ? apply_binop<T, true, MATH>(op, a, b) : (from_b ? b : a);
   }
 }
 // the aligned form of the fill: no operator, both operands' values at the output's positions and a flag "both present" (csr_ewise_aligned)
 template <class W> __global__ void k_merge_align(uint64_t n, const unsigned long long* __restrict__ key, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ e,
-                                                 const uint32_t* __restrict__ pos, const W* __restrict__ aval, const W* __restrict__ bval, uint32_t* __restrict__ ocol, W* __restrict__ xval,
-                                                 W* __restrict__ yval, uint8_t* __restrict__ bothf) {
+                                                 const uint32_t* __restrict__ pos, const W* __restrict__ aval, const W* __restrict__ bval, bool fills, W alpha, W beta, uint32_t* __restrict__ ocol,
+                                                 W* __restrict__ xval, W* __restrict__ yval, uint8_t* __restrict__ bothf) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) if (e[i]) {
     const uint32_t w = pos[i]; const unsigned long long k = key[i]; const uint32_t x = idx[i];
-    const bool both = i + 1 < n && key[i + 1] == k;
+    const bool both = i + 1 < n && key[i + 1] == k, from_b = (x & 0x80000000u) != 0;
     W xv, yv;
-    if (both) { const uint32_t x2 = idx[i + 1]; const uint32_t xa = (x & 0x80000000u) ? x2 : x, xb = (x & 0x80000000u) ? x : x2;
+    if (both) { const uint32_t x2 = idx[i + 1]; const uint32_t xa = from_b ? x2 : x, xb = from_b ? x : x2;
                 xv = aval[xa & 0x7FFFFFFFu]; yv = bval[xb & 0x7FFFFFFFu]; }
-    else xv = yv = (x & 0x80000000u) ? bval[x & 0x7FFFFFFFu] : aval[x];
-    ocol[w] = (uint32_t)k; xval[w] = xv; yval[w] = yv; bothf[w] = both ? 1 : 0;
+    else if (fills) { xv = from_b ? alpha : aval[x]; yv = from_b ? bval[x & 0x7FFFFFFFu] : beta; }      // (a, beta) / (alpha, b): the operator is called on every entry
+    else xv = yv = from_b ? bval[x & 0x7FFFFFFFu] : aval[x];
+    ocol[w] = (uint32_t)k; xval[w] = xv; yval[w] = yv; bothf[w] = (both || fills) ? 1 : 0;
   }
 }
 // the merge of the two patterns up to the output's row pointers and entry count; km / im / e / pos describe the merged sequence for the fill kernels
 struct EwiseMerge { DevBuf km, im, e, pos; uint64_t n = 0; };
-static bool ewise_merge(const DevCSR& A, const DevCSR& B, bool is_union, DevCSR& out, EwiseMerge& mg) {
+static bool ewise_merge(const DevCSR& A, const DevCSR& B, bool whole, DevCSR& out, EwiseMerge& mg) {
   const uint32_t nrows = A.nrows; const uint64_t na = A.nnz, nb = B.nnz, n = na + nb;
   if (na >= 0x7FFFFFF0ull || nb >= 0x7FFFFFF0ull) fail(GrB_INSUFFICIENT_SPACE, "eWise: more than 2^31 entries in one operand");
   out.clear(); out.nrows = nrows; out.ncols = A.ncols;
@@ -193,7 +197,7 @@ static bool ewise_merge(const DevCSR& A, const DevCSR& B, bool is_union, DevCSR&
     if (nb) { csr_row_indices(B, rowidx.as<uint32_t>()); hipLaunchKernelGGL(k_entry_keys, dim3(grid_1d(nb)), dim3(256), 0, stream(), nb, rowidx.as<uint32_t>(), B.col.as<uint32_t>(), 0x80000000u, (unsigned long long*)kb.p, ib.as<uint32_t>()); }
     GRB_HIP(hipStreamSynchronize(stream())); }
   merge_pairs_u64((const uint64_t*)ka.p, (const uint64_t*)kb.p, (uint64_t*)mg.km.p, ia.as<uint32_t>(), ib.as<uint32_t>(), mg.im.as<uint32_t>(), na, nb);
-  hipLaunchKernelGGL(k_merge_emit, dim3(grid_1d(n + 1)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, is_union, mg.e.as<uint32_t>());
+  hipLaunchKernelGGL(k_merge_emit, dim3(grid_1d(n + 1)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, whole, mg.e.as<uint32_t>());
   exclusive_scan_u32(mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), n + 1);
   hipLaunchKernelGGL(k_merge_rowptr, dim3(grid_1d((uint64_t)nrows + 1)), dim3(256), 0, stream(), A.rowptr.as<uint32_t>(), B.rowptr.as<uint32_t>(), nrows, mg.pos.as<uint32_t>(), out.rowptr.as<uint32_t>());
   uint32_t total = 0;
@@ -201,14 +205,15 @@ static bool ewise_merge(const DevCSR& A, const DevCSR& B, bool is_union, DevCSR&
   out.nnz = total;
   return true;
 }
-void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int op, bool is_union, DevCSR& out) {
+void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int op, int mode, DevCSR& out, const void* alpha, const void* beta) {
   EwiseMerge mg;
-  if (!ewise_merge(A, B, is_union, out, mg)) return;
+  if (!ewise_merge(A, B, mode != EW_MULT, out, mg)) return;
   const uint64_t n = mg.n, total = out.nnz;
   dispatch_type(code, [&]<class T>() {
     out.col.alloc((size_t)total * 4 + 4); out.val.alloc((size_t)total * sizeof(T) + 8);
+    const bool fills = mode == EW_UNION; T fa{}, fb{}; if (fills) { memcpy(&fa, alpha, sizeof(T)); memcpy(&fb, beta, sizeof(T)); }
 #define GRB_EW_FILL(MATH) hipLaunchKernelGGL((k_merge_fill<T, MATH>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
-                                             (const T*)aval, (const T*)bval, op, out.col.as<uint32_t>(), out.val.as<T>())
+                                             (const T*)aval, (const T*)bval, op, fills, fa, fb, out.col.as<uint32_t>(), out.val.as<T>())
     if (binop_needs_math(op)) GRB_EW_FILL(true); else GRB_EW_FILL(false);
 #undef GRB_EW_FILL
   });
@@ -216,16 +221,18 @@ void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, con
   GRB_HIP(hipStreamSynchronize(stream()));       // the temporaries return to the pool
   out.valid = true;
 }
-void csr_ewise_aligned(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, bool is_union, DevCSR& out, DevBuf& xval, DevBuf& yval, DevBuf& both) {
+void csr_ewise_aligned(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int mode, DevCSR& out, DevBuf& xval, DevBuf& yval, DevBuf& both, const void* alpha,
+                       const void* beta) {
   EwiseMerge mg;
   const size_t ts = (size_t)type_size(code);
-  if (!ewise_merge(A, B, is_union, out, mg)) { xval.alloc(16); yval.alloc(16); both.alloc(16); return; }
+  const bool fills = mode == EW_UNION;
+  if (!ewise_merge(A, B, mode != EW_MULT, out, mg)) { xval.alloc(16); yval.alloc(16); both.alloc(16); return; }
   const uint64_t n = mg.n, total = out.nnz;
   out.col.alloc((size_t)total * 4 + 4); out.val.alloc((size_t)total * ts + 16);
   xval.alloc((size_t)total * ts + 16); yval.alloc((size_t)total * ts + 16); both.alloc((size_t)total + 16);
-#define GRB_EW_ALIGN(W) hipLaunchKernelGGL((k_merge_align<W>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
-                                           (const W*)aval, (const W*)bval, out.col.as<uint32_t>(), xval.as<W>(), yval.as<W>(), both.as<uint8_t>())
-  switch (ts) { case 1: GRB_EW_ALIGN(uint8_t); break; case 2: GRB_EW_ALIGN(uint16_t); break; case 4: GRB_EW_ALIGN(uint32_t); break; default: GRB_EW_ALIGN(uint64_t); break; }
+#define GRB_EW_ALIGN(W) W fa{}, fb{}; if (fills) { memcpy(&fa, alpha, sizeof(W)); memcpy(&fb, beta, sizeof(W)); } hipLaunchKernelGGL((k_merge_align<W>), dim3(grid_1d(n)), dim3(256), 0, stream(), n, (const unsigned long long*)mg.km.p, mg.im.as<uint32_t>(), mg.e.as<uint32_t>(), mg.pos.as<uint32_t>(), \
+                                           (const W*)aval, (const W*)bval, fills, fa, fb, out.col.as<uint32_t>(), xval.as<W>(), yval.as<W>(), both.as<uint8_t>())
+  switch (ts) { case 1: { GRB_EW_ALIGN(uint8_t); break; } case 2: { GRB_EW_ALIGN(uint16_t); break; } case 4: { GRB_EW_ALIGN(uint32_t); break; } default: { GRB_EW_ALIGN(uint64_t); break; } }
 #undef GRB_EW_ALIGN
   GRB_HIP(hipGetLastError());
   GRB_HIP(hipStreamSynchronize(stream()));       // the temporaries return to the pool
@@ -245,7 +252,7 @@ void csr_writeback(int code, uint32_t nrows, const DevCSR& C, const DevCSR& Tm, 
   (void)nrows;
   const size_t ts = (size_t)type_size(code);
   DevCSR Zacc; const DevCSR* Z = &Tm;
-  if (accum >= 0) { csr_ewise(code, C, C.val.p, Tm, Tm.val.p, accum, true, Zacc); Z = &Zacc; }       // Z = accum(C, T) on the union of the patterns
+  if (accum >= 0) { csr_ewise(code, C, C.val.p, Tm, Tm.val.p, accum, EW_ADD, Zacc); Z = &Zacc; }       // Z = accum(C, T) on the union of the patterns
   if (!M) {                                         // no mask: everything is allowed (the complemented no-mask case never gets here)
     if (Z == &Zacc) out = std::move(Zacc); else csr_copy(Tm, ts, out);
     return;
@@ -255,7 +262,7 @@ void csr_writeback(int code, uint32_t nrows, const DevCSR& C, const DevCSR& Tm, 
   if (replace || !C.nnz) { out = std::move(Zk); return; }
   DevCSR Ck;
   { DevBuf keep(C.nnz + 8); mask_flags_ex(C, *M, mcode, mstruct, mcomp, true, keep.as<uint8_t>()); csr_compact(C, C.val.p, ts, keep.as<uint8_t>(), Ck); }
-  csr_ewise(code, Zk, Zk.val.p, Ck, Ck.val.p, B_FIRST, true, out);              // disjoint patterns: a plain merge
+  csr_ewise(code, Zk, Zk.val.p, Ck, Ck.val.p, B_FIRST, EW_ADD, out);              // disjoint patterns: a plain merge
 }
 
 // ---- reduce each row with a monoid -> bitmap vector ------------------------------------------------------------------------

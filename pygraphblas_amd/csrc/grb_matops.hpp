@@ -8,10 +8,13 @@ namespace grb {
 // out = C<M,replace> (+accum) T  — all three in one value type `code`; M may be nullptr
 void csr_writeback(int code, uint32_t nrows, const DevCSR& C, const DevCSR& Tm, const DevCSR* M, int mcode, bool mstruct, bool mcomp,
                    bool replace, int accum, DevCSR& out);
-void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int op, bool is_union, DevCSR& out);
+// `mode`: an EwiseKind; EW_UNION takes `alpha` / `beta`, values of the type `code`
+void csr_ewise(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int op, int mode, DevCSR& out, const void* alpha = nullptr, const void* beta = nullptr);
 // the pattern of the union / intersection alone, with both operands' values moved to the output's positions (grb_userop.cpp evaluates a user-defined operator over
-// them): xval[w] / yval[w] hold A's / B's value of output entry w; where only one operand has the entry (union) both hold that value and both[w] = 0.
-void csr_ewise_aligned(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, bool is_union, DevCSR& out, DevBuf& xval, DevBuf& yval, DevBuf& both);
+// them): xval[w] / yval[w] hold A's / B's value of output entry w; where only one operand has the entry, EW_ADD: both hold that value and both[w] = 0;
+// EW_UNION: they hold (a, beta) / (alpha, b) and both[w] = 1 — the operator is to be called on every entry.
+void csr_ewise_aligned(int code, const DevCSR& A, const void* aval, const DevCSR& B, const void* bval, int mode, DevCSR& out, DevBuf& xval, DevBuf& yval, DevBuf& both, const void* alpha = nullptr,
+                       const void* beta = nullptr);
 void csr_compact(const DevCSR& A, const void* aval, size_t ts, const uint8_t* keep, DevCSR& out);
 void select_positional_flags(const DevCSR& A, int sel, int64_t k, uint8_t* keep);
 void mask_flags(const DevCSR& Tm, const DevCSR& M, int mcode, bool mstruct, bool mcomp, uint8_t* keep);

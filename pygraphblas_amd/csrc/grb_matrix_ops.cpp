@@ -3,6 +3,7 @@
 //   GrB_mxm                 <- lib.GrB_mxm, pygraphblas/matrix.py:2572-2583 (Matrix.mxm)       THE HOT PATH
 //   GrB_transpose           <- Matrix.transpose                 (pygraphblas/matrix.py:1003-1062)
 //   GrB_Matrix_eWiseAdd/Mult_* <- Matrix.eadd / emult           (pygraphblas/matrix.py:1103-1413)
+//   GxB_Matrix_eWiseUnion   <- Matrix.eunion                    (SuiteSparse 6: the union with fill values; not in the reference package)
 //   GrB_Matrix_apply, GxB_Matrix_apply_BinaryOp1st/2nd          (pygraphblas/matrix.py:1934-2040)
 //   GxB_Matrix_select       <- Matrix.select / tril / triu      (pygraphblas/matrix.py:2042-2200)
 //   GrB_Matrix_reduce_Monoid <- Matrix.reduce_vector            (pygraphblas/matrix.py:1861-1932)
@@ -21,10 +22,10 @@ namespace grb {
 bool mxm_few_rows_wanted(const DevCSR& Ad, const DevCSR& Bd);
 void mxm_few_rows(const DevCSR& Ad, GrB_Type atype, GrB_Matrix Mmask, const DescView& dv, GrB_Semiring semiring, GrB_Matrix B, int zcode, DevCSR& T);
 bool few_long_rows(uint64_t nrows, uint64_t ncols, uint64_t nnz);
-void ewise_few_rows(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_BinaryOp op, const DevCSR& Ad, GrB_Type atype, const DevCSR& Bd, GrB_Type btype, bool is_union, DevCSR& T);
+void ewise_few_rows(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_BinaryOp op, const DevCSR& Ad, GrB_Type atype, const DevCSR& Bd, GrB_Type btype, const EwiseMode& mode, DevCSR& T);
 // round 6: the same batches as bitmaps, all rows in one kernel (grb_mxm_rows.cpp)
 bool batch_wanted(GrB_Matrix C, uint64_t work);
-void ewise_batch(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, bool is_union);
+void ewise_batch(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, const EwiseMode& mode);
 void apply_batch(GrB_Matrix C, int mode, int opcode, int xcode, const uint8_t* scalar16, GrB_Matrix A);
 bool mxm_batch(GrB_Matrix C, GrB_Matrix A, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix B, int zcode, DevCSR& T);
 }
@@ -221,7 +222,9 @@ void do_transpose(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Matrix A, 
 // eWiseAdd / eWiseMult.  A user-defined operator (grb_userop.cpp) has no HBM-less route — hypersparse and complex containers are refused, naming it — and no
 // batch routes: the merge of the two patterns moves both operands' values to the output's positions (csr_ewise_aligned) and its compiled kernel streams over
 // them, where a built-in operator's csr_ewise merges and computes in one pass.
-void do_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, bool is_union) {
+// GxB_eWiseUnion (mode.fills()) takes every route of eWiseAdd with its two scalars beside the operator: the fill kernels call the operator where eWiseAdd copies.
+// Its plan string names it: "ewise_union<on=matrix,op=...> k_merge_fill<union> ", or "union" inside the batch routes' and the user operator's own strings.
+void do_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc, const EwiseMode& mode) {
   need_device(); check_mat(A, "eWise"); check_mat(B, "eWise"); if (M) check_mat(M, "eWise");
   const bool user = check_obj(op) && is_user(op);
   if (user) {
@@ -230,33 +233,38 @@ void do_ewise(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_BinaryOp op, G
     if (accum) check_binop(accum, "accum");
   } else {
     check_binop(op, "eWise");
-    if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mat_ewise(C, M, accum, op, A, B, desc, is_union); return; }
+    if (is_hyper(C) || is_hyper(M) || is_hyper(A) || is_hyper(B)) { hyper_mat_ewise(C, M, accum, op, A, B, desc, mode); return; }
   }
   const DescView dv(desc);
   const Dims a = op_dims(A, dv.tran0), b = op_dims(B, dv.tran1);
   if (a.r != b.r || a.c != b.c) fail(GrB_DIMENSION_MISMATCH, "eWise: dimensions do not conform");
   conform(C, M, a, "eWise: dimensions do not conform");
+  if (mode.fills()) g_last_plan.clear();
   if (nothing_to_write(C, M, dv)) return;
   if (!user && !dv.tran0 && !dv.tran1 && batch_wanted(C, mat_nvals(A) + mat_nvals(B)) && A->type->code < T_FC32 && B->type->code < T_FC32 && (!M || M->type->code < T_FC32)) {
     if (accum) check_binop(accum, "accum");
-    ewise_batch(C, M, dv, accum, op, A, B, is_union); return;      // a batch of a few very long rows (BC sweeps): its bitmap as ONE vector through the vector kernel
+    ewise_batch(C, M, dv, accum, op, A, B, mode); return;      // a batch of a few very long rows (BC sweeps): its bitmap as ONE vector through the vector kernel
   }
   const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);
   if (!user && few_long_rows(C->nrows, C->ncols, Ad.nnz + Bd.nnz)) {          // a batch of a few very long rows (BC sweeps): row by row through the vector kernels
-    DevCSR T; ewise_few_rows(C, M, dv, accum, op, Ad, A->type, Bd, B->type, is_union, T);
+    DevCSR T; ewise_few_rows(C, M, dv, accum, op, Ad, A->type, Bd, B->type, mode, T);
     adopt(C, T, C->type->code); return;
   }
   const int xc = op->xtype->code;
+  uint8_t alpha[16] = {0}, beta[16] = {0}; if (mode.fills()) mode.cast_fill(xc, op->ytype->code, alpha, beta);
   DevBuf acast, bcast;
   const void* av = cast_values(xc, A->type->code, Ad.val.p, Ad.nnz, acast);
   const void* bv = cast_values(xc, B->type->code, Bd.val.p, Bd.nnz, bcast);
   DevCSR T;
   if (user) {
     DevBuf xv, yv, both;
-    csr_ewise_aligned(xc, Ad, av, Bd, bv, is_union, T, xv, yv, both);
-    userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, T.nnz, xv.p, nullptr, yv.p, nullptr, is_union ? both.as<uint8_t>() : nullptr, nullptr, T.val.p, nullptr);
+    csr_ewise_aligned(xc, Ad, av, Bd, bv, mode.kind, T, xv, yv, both, alpha, beta);
+    // (a union: the aligned values are (a, beta) / (alpha, b) where one operand alone has the entry — the compiled kernel calls the operator on every entry)
+    if (mode.fills()) userop_run(UK_EUNION, op->name, op->defn, xc, T.nnz, xv.p, nullptr, yv.p, nullptr, nullptr, alpha, T.val.p, nullptr, beta);
+    else userop_run(mode.whole() ? UK_EADD : UK_EMULT, op->name, op->defn, xc, T.nnz, xv.p, nullptr, yv.p, nullptr, mode.whole() ? both.as<uint8_t>() : nullptr, nullptr, T.val.p, nullptr);
   } else {
-    csr_ewise(xc, Ad, av, Bd, bv, op->opcode, is_union, T);
+    csr_ewise(xc, Ad, av, Bd, bv, op->opcode, mode.kind, T, alpha, beta);
+    if (mode.fills()) g_last_plan = std::string("ewise_union<on=matrix,op=") + op->name + "> k_merge_fill<union> ";
   }
   matrix_write_back(C, T, xc, M, dv, accum, false);
 }
@@ -481,17 +489,22 @@ GrB_Info GrB_transpose(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp a
   MAT_GUARD(C); if (!A) return GrB_NULL_POINTER; return guarded(C, [&] { do_transpose(C, Mask, accum, A, desc); });
 }
 GrB_Info GrB_Matrix_eWiseAdd_BinaryOp(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
-  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; return guarded(C, [&] { do_ewise(C, M, accum, op, A, B, desc, true); }); }
+  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; return guarded(C, [&] { do_ewise(C, M, accum, op, A, B, desc, {EW_ADD}); }); }
 GrB_Info GrB_Matrix_eWiseAdd_Monoid(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
-  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->op, A, B, desc, true); }); }
+  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->op, A, B, desc, {EW_ADD}); }); }
 GrB_Info GrB_Matrix_eWiseAdd_Semiring(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
-  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { possr_refuse_elementwise(op, "eWiseAdd"); do_ewise(C, M, accum, op->add->op, A, B, desc, true); }); }
+  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { possr_refuse_elementwise(op, "eWiseAdd"); do_ewise(C, M, accum, op->add->op, A, B, desc, {EW_ADD}); }); }
 GrB_Info GrB_Matrix_eWiseMult_BinaryOp(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
-  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; return guarded(C, [&] { do_ewise(C, M, accum, op, A, B, desc, false); }); }
+  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; return guarded(C, [&] { do_ewise(C, M, accum, op, A, B, desc, {EW_MULT}); }); }
 GrB_Info GrB_Matrix_eWiseMult_Monoid(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
-  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->op, A, B, desc, false); }); }
+  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { do_ewise(C, M, accum, op->op, A, B, desc, {EW_MULT}); }); }
 GrB_Info GrB_Matrix_eWiseMult_Semiring(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B, const GrB_Descriptor desc) {
-  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { possr_refuse_elementwise(op, "eWiseMult"); do_ewise(C, M, accum, op->mul, A, B, desc, false); }); }
+  MAT_GUARD(C); if (!op || !A || !B) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(C, [&] { possr_refuse_elementwise(op, "eWiseMult"); do_ewise(C, M, accum, op->mul, A, B, desc, {EW_MULT}); }); }
+GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GxB_Scalar alpha, const GrB_Matrix B, const GxB_Scalar beta,
+                               const GrB_Descriptor desc) {
+  GRB_UNION_ARGS(C, M, op, A, B, alpha, beta);
+  return guarded(C, [&] { union_refuse_complex(no_layout(C, M, A, B), alpha, beta); do_ewise(C, M, accum, op, A, B, desc, {EW_UNION, alpha, beta}); });
+}
 GrB_Info GrB_Matrix_apply(GrB_Matrix C, const GrB_Matrix M, const GrB_BinaryOp accum, const GrB_UnaryOp op, const GrB_Matrix A, const GrB_Descriptor desc) {
   MAT_GUARD(C); if (!op || !A) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT;
   return guarded(C, [&] { do_apply(C, M, accum, elem_op(op), nullptr, 0, A, desc); });

@@ -19,10 +19,17 @@ extern "C" GrB_Info GrB_vxm(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
                             const GrB_Descriptor desc);
 extern "C" GrB_Info GrB_Vector_eWiseAdd_BinaryOp(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc);
 extern "C" GrB_Info GrB_Vector_eWiseMult_BinaryOp(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc);
+extern "C" GrB_Info GxB_Vector_eWiseUnion(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, const GxB_Scalar alpha, const GrB_Vector v,
+                                          const GxB_Scalar beta, const GrB_Descriptor desc);
 
 namespace grb {
 
 namespace {
+// the vector entry point of an element-wise mode: what the batch routes below send their rows (or their one flattened vector) through
+GrB_Info vector_ewise_call(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v, GrB_Descriptor d, const EwiseMode& mode) {
+  if (mode.fills()) return GxB_Vector_eWiseUnion(w, mask, accum, op, u, mode.alpha, v, mode.beta, d);
+  return mode.whole() ? GrB_Vector_eWiseAdd_BinaryOp(w, mask, accum, op, u, v, d) : GrB_Vector_eWiseMult_BinaryOp(w, mask, accum, op, u, v, d);
+}
 constexpr uint64_t ROWS_GRID_CAP = 8192;                                     // the grid cap of this file's streaming kernels (grid_1d's second argument)
 // entries of one CSR row -> bitmap (values are moved as raw bytes of the element size)
 template <int TS> __global__ void k_row_to_bitmap(const uint32_t* __restrict__ col, const uint8_t* __restrict__ val, uint32_t cnt, uint8_t* __restrict__ dval, uint8_t* __restrict__ dpres) {
@@ -122,7 +129,7 @@ bool few_long_rows(uint64_t nrows, uint64_t ncols, uint64_t nnz) {
   return nrows <= 64 && ncols >= 65536u && nnz >= (1u << 18);
 }
 
-void ewise_few_rows(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_BinaryOp op, const DevCSR& Ad, GrB_Type atype, const DevCSR& Bd, GrB_Type btype, bool is_union,
+void ewise_few_rows(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_BinaryOp op, const DevCSR& Ad, GrB_Type atype, const DevCSR& Bd, GrB_Type btype, const EwiseMode& mode,
                     DevCSR& T) {
   const uint32_t nr = (uint32_t)C->nrows; const uint64_t n = C->ncols;
   const size_t cs = C->type->size;
@@ -137,11 +144,11 @@ void ewise_few_rows(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_Bina
     GrB_Vector va = row_vector(Ad, atype, s, arp, n), vb = row_vector(Bd, btype, s, brp, n); tmp.v.push_back(va); tmp.v.push_back(vb);
     GrB_Vector vm = nullptr; if (Mmask) { vm = row_vector(Mmask->csr, Mmask->type, s, mrp, n); tmp.v.push_back(vm); }
     GrB_Vector vc = row_vector(C->csr, C->type, s, crp, n); outs.v[s] = vc;
-    const GrB_Info info = is_union ? GrB_Vector_eWiseAdd_BinaryOp(vc, vm, accum, op, va, vb, &d) : GrB_Vector_eWiseMult_BinaryOp(vc, vm, accum, op, va, vb, &d);
+    const GrB_Info info = vector_ewise_call(vc, vm, accum, op, va, vb, &d, mode);
     if (info != GrB_SUCCESS) fail(info, "eWise (row-wise): " + vc->err);
   }
   rows_to_csr(outs.v, n, cs, "eWise", T);
-  g_last_plan = "ewise_rows<" + std::to_string(nr) + " x vector eWise> ";
+  g_last_plan = "ewise_rows<" + std::to_string(nr) + (mode.fills() ? " x vector eWise union> " : " x vector eWise> ");
 }
 
 
@@ -224,7 +231,7 @@ bool batch_wanted(GrB_Matrix C, uint64_t work) {
 }
 
 // C<M, replace> = accum(C, A op B) on batch matrices, element-wise: ONE vector kernel over the nrows * ncols positions
-void ewise_batch(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, bool is_union) {
+void ewise_batch(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Matrix A, GrB_Matrix B, const EwiseMode& mode) {
   const uint64_t np = (uint64_t)C->nrows * C->ncols;
   if (A != C) mat_bitmap(A); if (B != C) mat_bitmap(B); if (Mmask && Mmask != C) mat_bitmap(Mmask);
   DevBitmap& cb = mat_bitmap(C);                                      // (an empty C: a cleared presence array)
@@ -243,12 +250,12 @@ void ewise_batch(GrB_Matrix C, GrB_Matrix Mmask, const DescView& dv, GrB_BinaryO
   //  error, not the object)
   auto c_left_empty = [&] { C->hi.clear(); C->hj.clear(); C->hx.clear(); C->pending.clear(); C->host_valid = true; C->iso_full = false; mat_invalidate_device(C); };
   GrB_Info info;
-  try { info = is_union ? GrB_Vector_eWiseAdd_BinaryOp(vc, vm, accum, op, va, vb, &d) : GrB_Vector_eWiseMult_BinaryOp(vc, vm, accum, op, va, vb, &d); if (info == GrB_SUCCESS) vec_to_device(vc); }
+  try { info = vector_ewise_call(vc, vm, accum, op, va, vb, &d, mode); if (info == GrB_SUCCESS) vec_to_device(vc); }
   catch (...) { c_left_empty(); throw; }
   if (info != GrB_SUCCESS) { std::string e = vc->err; c_left_empty(); fail(info, "eWise (batch): " + e); }
   if (vc->dval.borrowed || vc->dpres.borrowed || vc->dval.bytes < np * C->type->size || vc->dpres.bytes < np) { c_left_empty(); fail(GrB_PANIC, "eWise (batch): the result does not own its buffers"); }
   adopt_bitmap(C, std::move(vc->dval), std::move(vc->dpres), vc->facts.dnvals_known, vc->facts.dnvals);
-  g_last_plan = "ewise_batch<" + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + " as one vector> ";
+  g_last_plan = "ewise_batch<" + std::to_string(C->nrows) + " x " + std::to_string(C->ncols) + (mode.fills() ? " as one vector, union> " : " as one vector> ");
 }
 
 // C = f(A) on a batch matrix, no mask, no accumulator (`frontier.apply(BOOL.ONE, out=s)`, gap/bcmark.py:38-39): the values in one pass, the pattern copied

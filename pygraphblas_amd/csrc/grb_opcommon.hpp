@@ -189,6 +189,20 @@ inline SemiringRoute semiring_route(GrB_Semiring s) {
   return {is_user_semiring(s) ? SR_USER : SR_BUILTIN, s};
 }
 
+// ---- GxB_eWiseUnion: what its matrix and vector entry points share ------------------------------------------------------------------------------------------
+// The arguments, before a device is asked for and in this order: all there, all initialised, both scalars hold an entry (as GRB_SCALAR_OK of grb_apply_scalar.cpp).
+#define GRB_UNION_ARGS(C, M, op, A, B, alpha, beta) \
+  if (!(C) || !(op) || !(A) || !(B) || !(alpha) || !(beta)) return GrB_NULL_POINTER; \
+  if (!check_obj(C) || !check_obj(op) || !check_obj(A) || !check_obj(B) || ((M) && !check_obj(M)) || !check_obj(alpha) || !check_obj(beta)) return GrB_UNINITIALIZED_OBJECT; \
+  if (!(alpha)->has || !(beta)->has) return GrB_INVALID_VALUE
+// ... then, before the dimensions are looked at: no complex container and no complex scalar
+inline void union_refuse_complex(const NoLayout& nl, GxB_Scalar alpha, GxB_Scalar beta) {
+  if (nl.cplx || alpha->type->code >= T_FC32 || beta->type->code >= T_FC32) fail(GrB_DOMAIN_MISMATCH, "eWiseUnion: complex containers and scalars are out of scope");
+}
+inline void EwiseMode::cast_fill(int xcode, int ycode, uint8_t* a16, uint8_t* b16) const {
+  cast_scalar(xcode, a16, alpha->type->code, alpha->x); cast_scalar(ycode, b16, beta->type->code, beta->x);
+}
+
 // mask vector -> allow bytes.  Returns nullptr (= everything allowed) when there is no mask and no
 // complement; sets *nothing when there is no mask but the complement flag is set.
 inline const uint8_t* vector_allow(GrB_Vector mask, const DescView& dv, uint64_t n, DevBuf& tmp, bool* nothing) {

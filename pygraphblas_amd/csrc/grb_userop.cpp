@@ -14,11 +14,12 @@
 // run; do_ewise / vec_ewise_op call it in their general tail.  A block `if (user)` at the top of each driver refuses containers without an HBM layout
 // (user_needs_layout, here) and looks at the accumulator BEFORE the dimensions; such a call is never queued and completes deferred work first.  In
 // userop_run the definition is embedded in the text of ONE streaming kernel per (operator, kind, type) — every function of the definition made a device
-// function by `#pragma clang force_cuda_host_device`, the kind (apply | bind1st | bind2nd | eadd | emult) a constant of the text — compiled with hipRTC
+// function by `#pragma clang force_cuda_host_device`, the kind (apply | bind1st | bind2nd | eadd | emult | eunion) a constant of the text — compiled with hipRTC
 // through the chain compiler's build_kernel and its code-object cache on disk (grb_jit.hpp: source + architecture + hipRTC version + options; a second
 // process compiles nothing), at first use and outside the table's lock.  The kernel is entry-parallel: a lane owns four consecutive positions of the value
 // arrays, loaded and stored as one 16-byte pack (4-byte types; two for 8-byte ones), presence bytes as one 4-byte word.  Entries are computed by the
-// user's code only; where eWiseAdd finds an entry in one operand alone, the value is copied and the operator is not called.
+// user's code only; where eWiseAdd finds an entry in one operand alone, the value is copied and the operator is not called; GxB_eWiseUnion (eunion) calls it
+// there too, with alpha / beta — two scalar arguments of the kernel — in the missing operand's place.
 // A definition that does not compile, or a machine without hipRTC: the operation fails with an error code and the operator's name and the compiler's
 // log in the object's error string — there is no interpreter and no host route behind it.
 //
@@ -54,7 +55,7 @@ const char* c_type(int code) {
   }
 }
 const char* kind_name(int kind) {
-  switch (kind) { case UK_APPLY: return "apply"; case UK_BIND1ST: return "bind1st"; case UK_BIND2ND: return "bind2nd"; case UK_EADD: return "eadd"; default: return "emult"; }
+  switch (kind) { case UK_APPLY: return "apply"; case UK_BIND1ST: return "bind1st"; case UK_BIND2ND: return "bind2nd"; case UK_EADD: return "eadd"; case UK_EUNION: return "eunion"; default: return "emult"; }
 }
 
 // what the definition may assume, as <stdint.h>, <stdbool.h> and <math.h> would give it (hipRTC has no system headers; its built-in ones declare the math functions)
@@ -75,9 +76,10 @@ std::string generate(int kind, const char* name, const char* defn, int tcode) {
     << "struct __attribute__((aligned(" << (4 * ts > 16 ? 16 : 4 * ts) << "))) P4 { T v[4]; }; struct __attribute__((aligned(4))) B4 { unsigned char v[4]; };\n";
   if (unary) o << "__device__ __forceinline__ T grb_f(T a, T b) { T z; " << name << "(&z, &a); return z; }\n";
   else o << "__device__ __forceinline__ T grb_f(T a, T b) { T z; " << name << "(&z, &a, &b); return z; }\n";
-  // x / y: operand values; px / py: presence bytes (0 = all present); both: eadd over aligned values; s: the bound scalar; z / q: result values / presence
+  // x / y: operand values; px / py: presence bytes (0 = all present); both: eadd over aligned values; s: the bound scalar; z / q: result values / presence;
+  // eunion alone has s2: s / s2 stand in for x / y where the other operand alone has the entry
   o << "extern \"C\" __global__ void __launch_bounds__(256) grb_userop(const T* x, const unsigned char* px, const T* y, const unsigned char* py, const unsigned char* both,\n"
-       "    T s, T* z, unsigned char* q, unsigned long long n, int packed) {\n"
+       "    T s, " << (kind == UK_EUNION ? "T s2, " : "") << "T* z, unsigned char* q, unsigned long long n, int packed) {\n"
        "  const unsigned long long stride = (unsigned long long)gridDim.x * 1024ull;\n"
        "  for (unsigned long long base = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) * 4ull; base < n; base += stride) {\n"
        "    const int nv = n - base >= 4ull ? 4 : (int)(n - base);\n"
@@ -100,6 +102,7 @@ std::string generate(int kind, const char* name, const char* defn, int tcode) {
     case UK_BIND1ST: o << "      rp[h] = ap[h]; r[h] = ap[h] ? grb_f(s, a[h]) : (T)0;\n"; break;
     case UK_BIND2ND: o << "      rp[h] = ap[h]; r[h] = ap[h] ? grb_f(a[h], s) : (T)0;\n"; break;
     case UK_EMULT:   o << "      rp[h] = ap[h] && bp[h]; r[h] = rp[h] ? grb_f(a[h], b[h]) : (T)0;\n"; break;
+    case UK_EUNION:  o << "      rp[h] = ap[h] || bp[h]; r[h] = rp[h] ? grb_f(ap[h] ? a[h] : s, bp[h] ? b[h] : s2) : (T)0;\n"; break;      // the operator is called on every entry
     default:         o << "      const bool two = ap[h] && bp[h] && bo[h]; rp[h] = ap[h] || bp[h];\n"      // one operand alone has the entry: its value is copied, the operator is not called
                           "      r[h] = two ? grb_f(a[h], b[h]) : (ap[h] ? a[h] : (bp[h] ? b[h] : (T)0));\n"; break;
   }
@@ -213,17 +216,18 @@ void user_needs_layout(const char* opname, const char* extent, bool hyper, bool 
 }
 
 void userop_run(int kind, const char* name, const char* defn, int tcode, uint64_t n, const void* x, const uint8_t* px, const void* y, const uint8_t* py,
-                const uint8_t* both, const void* scalar, void* z, uint8_t* q) {
+                const uint8_t* both, const void* scalar, void* z, uint8_t* q, const void* scalar2) {
   if (!c_type(tcode) || !defn) fail(GrB_DOMAIN_MISMATCH, std::string("user-defined operator ") + name + ": not one of the real built-in types");
   hipFunction_t fn = kernel_of(generate(kind, name, defn, tcode), name, "grb_userop", "userop");
   g_last_plan = std::string("userop<name=") + name + ",kind=" + kind_name(kind) + ",type=" + type_by_code(tcode)->name + "> grb_userop ";
   if (!n) return;
   const size_t pa = pack_bytes(tcode);
   int packed = aligned(x, pa) && aligned(y, pa) && aligned(z, pa) && aligned(px, 4) && aligned(py, 4) && aligned(both, 4) && aligned(q, 4) ? 1 : 0;
-  uint8_t s[16] = {0}; if (scalar) memcpy(s, scalar, (size_t)type_size(tcode));
+  uint8_t s[16] = {0}, s2[16] = {0}; if (scalar) memcpy(s, scalar, (size_t)type_size(tcode)); if (scalar2) memcpy(s2, scalar2, (size_t)type_size(tcode));
   unsigned long long nn = n;
   void* args[] = {(void*)&x, (void*)&px, (void*)&y, (void*)&py, (void*)&both, (void*)s, (void*)&z, (void*)&q, (void*)&nn, (void*)&packed};
-  launch(fn, n, args);
+  void* uargs[] = {(void*)&x, (void*)&px, (void*)&y, (void*)&py, (void*)&both, (void*)s, (void*)s2, (void*)&z, (void*)&q, (void*)&nn, (void*)&packed};      // (the union's text has one parameter more)
+  launch(fn, n, kind == UK_EUNION ? uargs : args);
 }
 
 void userselect_run(const char* name, const char* defn, int xcode, int tcode, bool on_vector, uint64_t n, const uint32_t* rowidx, const uint32_t* col, const void* x,

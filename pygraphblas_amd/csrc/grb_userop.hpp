@@ -4,7 +4,7 @@
 
 namespace grb {
 
-enum UserKind { UK_APPLY = 0, UK_BIND1ST, UK_BIND2ND, UK_EADD, UK_EMULT };
+enum UserKind { UK_APPLY = 0, UK_BIND1ST, UK_BIND2ND, UK_EADD, UK_EMULT, UK_EUNION };
 
 inline bool is_user(const GrB_BinaryOp_opaque* op) { return op->opcode >= B_USER; }
 inline bool is_user(const GrB_UnaryOp_opaque* op) { return op->opcode >= U_USER; }
@@ -20,11 +20,12 @@ void user_needs_layout(const char* opname, const char* extent, bool hyper, bool 
 //   x / y        operand values of type tcode (y: nullptr for UK_APPLY / UK_BIND*)
 //   px / py      presence bytes of a bitmap operand, nullptr = every position holds an entry
 //   both         UK_EADD over aligned CSR values: 1 where both operands have the entry (else the value in x is copied); nullptr: decided by px / py
-//   scalar       the bound operand of UK_BIND1ST / UK_BIND2ND, already in tcode
+//   scalar       the bound operand of UK_BIND1ST / UK_BIND2ND, already in tcode; UK_EUNION: alpha, what stands in for x where only y has the entry
+//   scalar2      UK_EUNION: beta, what stands in for y where only x has the entry (px == py == nullptr, aligned CSR values: neither is ever used)
 //   z / q        result values and (when not nullptr) result presence bytes
 // Throws GrbError when hipRTC is missing or the definition does not compile (the message carries the operator's name and the compiler's log).
 void userop_run(int kind, const char* name, const char* defn, int tcode, uint64_t n, const void* x, const uint8_t* px, const void* y, const uint8_t* py,
-                const uint8_t* both, const void* scalar, void* z, uint8_t* q);
+                const uint8_t* both, const void* scalar, void* z, uint8_t* q, const void* scalar2 = nullptr);
 
 // keep[p] = present(p) && NAME(i, j, &x[p], &thunk) over n entries with the select operator's compiled kernel (`name`, `defn`, value type xcode, thunk type
 // tcode); sets the kernel plan.

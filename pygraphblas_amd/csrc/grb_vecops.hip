@@ -445,23 +445,25 @@ void reduce_values_f32_f64(uint64_t n, const void* val_f32, const uint8_t* pres,
 }
 
 // ---- element-wise union / intersection of two bitmap vectors ----------------------------------------------------
+// `mode` (an EwiseKind, wave-uniform): where one operand alone has the entry, EW_ADD copies it and EW_UNION computes op(u, beta) / op(alpha, v).
 template <class T, bool MATH> __global__ void k_vec_ewise(uint64_t n, const T* __restrict__ uval, const uint8_t* __restrict__ upres,
-                                               const T* __restrict__ vval, const uint8_t* __restrict__ vpres, int op, bool is_union,
+                                               const T* __restrict__ vval, const uint8_t* __restrict__ vpres, int op, int mode, T alpha, T beta,
                                                T* __restrict__ tval, uint8_t* __restrict__ tpres) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
     const bool a = upres[i] != 0, b = vpres[i] != 0;
-    if (a && b) { tval[i] = apply_binop<T, true, MATH>(op, uval[i], vval[i]); tpres[i] = 1; }
-    else if (is_union && a) { tval[i] = uval[i]; tpres[i] = 1; }
-    else if (is_union && b) { tval[i] = vval[i]; tpres[i] = 1; }
+    if ((a && b) || (mode == EW_UNION && (a || b))) { tval[i] = apply_binop<T, true, MATH>(op, a ? uval[i] : alpha, b ? vval[i] : beta); tpres[i] = 1; }
+    else if (mode && a) { tval[i] = uval[i]; tpres[i] = 1; }
+    else if (mode && b) { tval[i] = vval[i]; tpres[i] = 1; }
     else tpres[i] = 0;
   }
 }
 void vec_ewise(int code, uint64_t n, const void* uval, const uint8_t* upres, const void* vval, const uint8_t* vpres, int op,
-               bool is_union, void* tval, uint8_t* tpres) {
+               int mode, void* tval, uint8_t* tpres, const void* alpha, const void* beta) {
   if (!n) return;
   dispatch_type(code, [&]<class T>() {
-    if (binop_needs_math(op)) hipLaunchKernelGGL((k_vec_ewise<T, true>), dim3(grid_for(n)), dim3(256), 0, stream(), n, (const T*)uval, upres, (const T*)vval, vpres, op, is_union, (T*)tval, tpres);
-    else hipLaunchKernelGGL((k_vec_ewise<T, false>), dim3(grid_for(n)), dim3(256), 0, stream(), n, (const T*)uval, upres, (const T*)vval, vpres, op, is_union, (T*)tval, tpres);
+    T fa{}, fb{}; if (mode == EW_UNION) { memcpy(&fa, alpha, sizeof(T)); memcpy(&fb, beta, sizeof(T)); }
+    if (binop_needs_math(op)) hipLaunchKernelGGL((k_vec_ewise<T, true>), dim3(grid_for(n)), dim3(256), 0, stream(), n, (const T*)uval, upres, (const T*)vval, vpres, op, mode, fa, fb, (T*)tval, tpres);
+    else hipLaunchKernelGGL((k_vec_ewise<T, false>), dim3(grid_for(n)), dim3(256), 0, stream(), n, (const T*)uval, upres, (const T*)vval, vpres, op, mode, fa, fb, (T*)tval, tpres);
   });
 }
 
@@ -471,16 +473,16 @@ void vec_ewise(int code, uint64_t n, const void* uval, const uint8_t* upres, con
 // Element-wise, everything of position i is read before anything of position i is written: w may be u, v or the mask (no __restrict__ on those).
 // (The element-wise steps of the BC driver on its ns x n batches — `bcu.emult(paths, DIV, out=W, mask=S[i], desc=R)`, `W.emult(paths, TIMES, out=bcu, accum=PLUS)`,
 //  `paths.assign_matrix(frontier, accum=PLUS)` — are this; 155 -> ~60 us each at R-MAT-22, ns = 4.)
-template <class T, bool MATH> __global__ void k_vec_ewise_fused(uint64_t n, const T* uval, const uint8_t* upres, const T* vval, const uint8_t* vpres, int op, bool is_union,
+template <class T, bool MATH> __global__ void k_vec_ewise_fused(uint64_t n, const T* uval, const uint8_t* upres, const T* vval, const uint8_t* vpres, int op, int mode, T alpha, T beta,
                                                                 int mcode, const void* mval, const uint8_t* mpres, bool mstruct, bool mcomp, int accum, bool replace,
                                                                 T* wval, uint8_t* wpres) {
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
     const bool ok = mpres ? ((mpres[i] != 0 && mask_truth_at(mval, mcode, i, mstruct)) != mcomp) : true;
     if (ok) {
       const bool a = upres[i] != 0, b = vpres[i] != 0;
-      const bool tp = is_union ? (a || b) : (a && b);
+      const bool tp = mode ? (a || b) : (a && b);
       T tv{};
-      if (a && b) tv = apply_binop<T, true, MATH>(op, uval[i], vval[i]);
+      if ((a && b) || (mode == EW_UNION && tp)) tv = apply_binop<T, true, MATH>(op, a ? uval[i] : alpha, b ? vval[i] : beta);      // (a union: the scalar stands in for the operand without an entry)
       else if (tp) tv = a ? uval[i] : vval[i];
       if (accum >= 0) {
         if (tp) {
@@ -496,14 +498,15 @@ template <class T, bool MATH> __global__ void k_vec_ewise_fused(uint64_t n, cons
     }
   }
 }
-void vec_ewise_fused(int code, uint64_t n, const void* uval, const uint8_t* upres, const void* vval, const uint8_t* vpres, int op, bool is_union,
-                     int mcode, const void* mval, const uint8_t* mpres, bool mstruct, bool mcomp, int accum, bool replace, void* wval, uint8_t* wpres) {
+void vec_ewise_fused(int code, uint64_t n, const void* uval, const uint8_t* upres, const void* vval, const uint8_t* vpres, int op, int mode,
+                     int mcode, const void* mval, const uint8_t* mpres, bool mstruct, bool mcomp, int accum, bool replace, void* wval, uint8_t* wpres, const void* alpha, const void* beta) {
   if (!n) return;
   dispatch_type(code, [&]<class T>() {
+    T fa{}, fb{}; if (mode == EW_UNION) { memcpy(&fa, alpha, sizeof(T)); memcpy(&fb, beta, sizeof(T)); }
     if (binop_needs_math(op) || (accum >= 0 && binop_needs_math(accum)))
-      hipLaunchKernelGGL((k_vec_ewise_fused<T, true>), dim3(grid_for(n)), dim3(256), 0, stream(), n, (const T*)uval, upres, (const T*)vval, vpres, op, is_union, mcode, mval, mpres, mstruct, mcomp, accum, replace, (T*)wval, wpres);
+      hipLaunchKernelGGL((k_vec_ewise_fused<T, true>), dim3(grid_for(n)), dim3(256), 0, stream(), n, (const T*)uval, upres, (const T*)vval, vpres, op, mode, fa, fb, mcode, mval, mpres, mstruct, mcomp, accum, replace, (T*)wval, wpres);
     else
-      hipLaunchKernelGGL((k_vec_ewise_fused<T, false>), dim3(grid_for(n)), dim3(256), 0, stream(), n, (const T*)uval, upres, (const T*)vval, vpres, op, is_union, mcode, mval, mpres, mstruct, mcomp, accum, replace, (T*)wval, wpres);
+      hipLaunchKernelGGL((k_vec_ewise_fused<T, false>), dim3(grid_for(n)), dim3(256), 0, stream(), n, (const T*)uval, upres, (const T*)vval, vpres, op, mode, fa, fb, mcode, mval, mpres, mstruct, mcomp, accum, replace, (T*)wval, wpres);
   });
 }
 

@@ -4,6 +4,7 @@
 //   GrB_Matrix_reduce_<T>            <- Matrix.reduce_int              (pygraphblas/matrix.py:1782-1804)
 //   GrB_Vector_assign_<T>            <- Vector.assign_scalar           (pygraphblas/vector.py:1494-1524)
 //   GrB_Vector_eWiseAdd/eWiseMult_*  <- Vector.eadd / emult            (pygraphblas/vector.py:604-833)
+//   GxB_Vector_eWiseUnion            <- Vector.eunion                  (SuiteSparse 6: the union with fill values; not in the reference package)
 //   GrB_Vector_apply, GxB_Vector_apply_BinaryOp1st/2nd, GxB_Vector_select  (pygraphblas/vector.py:1204-1340)
 #include <algorithm>
 #include "grb_opcommon.hpp"
@@ -166,8 +167,10 @@ static void vec_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const 
 
 // eWiseAdd / eWiseMult.  A user-defined operator (grb_userop.cpp) runs on bitmap vectors in HBM only and is never queued: deferred work is completed first, then
 // its compiled kernel runs where a built-in operator's vec_ewise does.  The hypersparse route, the queue and the one-pass kernel serve built-in operators only.
+// GxB_eWiseUnion (mode.fills()) takes the same routes with its two scalars as kernel arguments; it is never queued either (deferred work is completed first), and
+// its plan string names it: "ewise_union<on=vector,op=...> k_vec_ewise_fused<union> " / "... k_vec_ewise<union> ", or the user operator's "kind=eunion".
 static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_BinaryOp op, GrB_Vector u, GrB_Vector v,
-                         GrB_Descriptor desc, bool is_union) {
+                         GrB_Descriptor desc, const EwiseMode& mode) {
   need_device();
   if (!check_obj(u) || !check_obj(v) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "eWise: uninitialised operand");
   const bool user = check_obj(op) && is_user(op);
@@ -177,16 +180,19 @@ static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_
     if (accum) check_binop(accum, "accum");
   } else {
     check_binop(op, "eWise");
-    if (is_hyper(w)) { hyper_vec_ewise(w, mask, accum, op, u, v, desc, is_union); return; }      // a size beyond the device layout
+    if (is_hyper(w)) { hyper_vec_ewise(w, mask, accum, op, u, v, desc, mode); return; }      // a size beyond the device layout
   }
   // (the prelude's steps one by one: the allow bytes cost a kernel, and the one-pass kernel below reads the mask in place)
   const DescView dv(desc); const uint64_t n = w->n;
   if (u->n != n || v->n != n || (mask && mask->n != n)) fail(GrB_DIMENSION_MISMATCH, "eWise: vector sizes differ");
-  if (user) lazy_flush();
+  if (user || mode.fills()) lazy_flush();
+  if (mode.fills()) g_last_plan.clear();
   if (!mask && dv.mask_comp) { if (dv.replace) GrB_Vector_clear(w); return; }      // no mask, complemented: nothing may be written
   const int xc = op->xtype->code;
+  const bool is_union = mode.whole();
+  uint8_t alpha[16] = {0}, beta[16] = {0}; if (mode.fills()) mode.cast_fill(xc, op->ytype->code, alpha, beta);
   if (!user) {
-    if (!mask && !accum && lazy_ewise(w, op, u, v, is_union)) return;      // queued: runs fused with its neighbours when a result is looked at
+    if (!mask && !accum && !mode.fills() && lazy_ewise(w, op, u, v, is_union)) return;      // queued: runs fused with its neighbours when a result is looked at
     // one pass when everything works in w's own type (round 6): the mask read in place, T(i) in a register, the write-back in the same store
     const char* fe = getenv("GRB_MI355X_EWISE_FUSED");
     const bool off = fe && atoi(fe) == 0;      // measurement / test hook (read per call, like GRB_MI355X_CHAIN_JIT)
@@ -200,9 +206,10 @@ static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_
       const bool uf = u->facts.dnvals_known && u->facts.dnvals == n, vf = v->facts.dnvals_known && v->facts.dnvals == n, wf = w->facts.dnvals_known && w->facts.dnvals == n;
       const bool t_full = is_union ? (uf || vf) : (uf && vf);
       const bool stays_full = !mask && accum && (wf || t_full);
-      vec_ewise_fused(wc, n, u->dval.p, u->dpres.as<uint8_t>(), v->dval.p, v->dpres.as<uint8_t>(), op->opcode, is_union,
+      vec_ewise_fused(wc, n, u->dval.p, u->dpres.as<uint8_t>(), v->dval.p, v->dpres.as<uint8_t>(), op->opcode, mode.kind,
                       mask ? mask->type->code : 0, mask ? mask->dval.p : nullptr, mask ? mask->dpres.as<uint8_t>() : nullptr, dv.mask_struct, dv.mask_comp,
-                      accum ? accum->opcode : -1, dv.replace, w->dval.p, w->dpres.as<uint8_t>());
+                      accum ? accum->opcode : -1, dv.replace, w->dval.p, w->dpres.as<uint8_t>(), alpha, beta);
+      if (mode.fills()) g_last_plan = std::string("ewise_union<on=vector,op=") + op->name + "> k_vec_ewise_fused<union> ";
       vec_invalidate_host(w, n, stays_full);
       return;
     }
@@ -213,8 +220,11 @@ static void vec_ewise_op(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_
   DevBuf uc, vc, tval(n * type_size(xc) + 16), tpres(n + 16);
   const void* uv = cast_values(xc, u->type->code, u->dval.p, n, uc);
   const void* vv = cast_values(xc, v->type->code, v->dval.p, n, vc);
-  if (user) userop_run(is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), nullptr, nullptr, tval.p, tpres.as<uint8_t>());
-  else vec_ewise(xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), op->opcode, is_union, tval.p, tpres.as<uint8_t>());
+  if (user) userop_run(mode.fills() ? UK_EUNION : is_union ? UK_EADD : UK_EMULT, op->name, op->defn, xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), nullptr, alpha, tval.p, tpres.as<uint8_t>(), beta);
+  else {
+    vec_ewise(xc, n, uv, u->dpres.as<uint8_t>(), vv, v->dpres.as<uint8_t>(), op->opcode, mode.kind, tval.p, tpres.as<uint8_t>(), alpha, beta);
+    if (mode.fills()) g_last_plan = std::string("ewise_union<on=vector,op=") + op->name + "> k_vec_ewise<union> ";
+  }
   // a comparison yields 0/1 in the operand type: identical to BOOL after the typecast into w
   const bool uf = u->facts.dnvals_known && u->facts.dnvals == n, vf = v->facts.dnvals_known && v->facts.dnvals == n;
   const uint64_t tn = (is_union ? (uf || vf) : (uf && vf)) ? n : ~0ull;          // a full operand makes the union full, two make the intersection full
@@ -303,17 +313,23 @@ static void vec_select(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GxB_Se
 extern "C" {
 
 GrB_Info GrB_Vector_eWiseAdd_BinaryOp(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
-  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op, u, v, desc, true); }); }
+  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op, u, v, desc, {EW_ADD}); }); }
 GrB_Info GrB_Vector_eWiseAdd_Monoid(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
-  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op->op, u, v, desc, true); }); }
+  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op->op, u, v, desc, {EW_ADD}); }); }
 GrB_Info GrB_Vector_eWiseAdd_Semiring(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
-  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { possr_refuse_elementwise(op, "eWiseAdd"); vec_ewise_op(w, mask, accum, op->add->op, u, v, desc, true); }); }
+  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { possr_refuse_elementwise(op, "eWiseAdd"); vec_ewise_op(w, mask, accum, op->add->op, u, v, desc, {EW_ADD}); }); }
 GrB_Info GrB_Vector_eWiseMult_BinaryOp(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
-  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op, u, v, desc, false); }); }
+  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op, u, v, desc, {EW_MULT}); }); }
 GrB_Info GrB_Vector_eWiseMult_Monoid(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Monoid op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
-  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op->op, u, v, desc, false); }); }
+  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { vec_ewise_op(w, mask, accum, op->op, u, v, desc, {EW_MULT}); }); }
 GrB_Info GrB_Vector_eWiseMult_Semiring(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_Semiring op, const GrB_Vector u, const GrB_Vector v, const GrB_Descriptor desc) {
-  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { possr_refuse_elementwise(op, "eWiseMult"); vec_ewise_op(w, mask, accum, op->mul, u, v, desc, false); }); }
+  VEC_GUARD(w); if (!op || !u || !v) return GrB_NULL_POINTER; if (!check_obj(op)) return GrB_UNINITIALIZED_OBJECT; return guarded(w, [&] { possr_refuse_elementwise(op, "eWiseMult"); vec_ewise_op(w, mask, accum, op->mul, u, v, desc, {EW_MULT}); }); }
+
+GrB_Info GxB_Vector_eWiseUnion(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, const GxB_Scalar alpha, const GrB_Vector v, const GxB_Scalar beta,
+                               const GrB_Descriptor desc) {
+  GRB_UNION_ARGS(w, mask, op, u, v, alpha, beta);
+  return guarded(w, [&] { union_refuse_complex(no_layout(w, mask, u, v), alpha, beta); vec_ewise_op(w, mask, accum, op, u, v, desc, {EW_UNION, alpha, beta}); });
+}
 
 // "Same size, same pattern, equal values" of two vectors of ONE built-in real type as a single pass (what pygraphblas/vector.py:188-235 `Vector.iseq` composes from
 // five calls).  GrB_NO_VALUE: not this function's case (types differ, complex, a size beyond the device layout, no device) — the caller composes it as before.

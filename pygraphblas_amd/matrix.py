@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _capi, types, descriptor as _d
 from ._capi import lib, u64
-from .base import check, NoValue, DomainMismatch
+from .base import check, eunion, NoValue, DomainMismatch
 from .types import current_semiring, current_accum, current_binop, current_monoid
 
 NULL = None
@@ -904,6 +904,20 @@ class Matrix:
     def emult(self, other, mult_op=None, cast=None, out=None, mask=None, accum=None, desc=None):
         """Element-wise intersection (reference: matrix.py:1264-1413)."""
         return self._ewise("eWiseMult", other, mult_op, cast, out, mask, accum, desc, lambda t: t._default_multop())
+
+    def eunion(self, other, op, alpha, beta, cast=None, out=None, mask=None, accum=None, desc=None):
+        """`GxB_Matrix_eWiseUnion`: on the union of the two patterns `op(A, B)` where both hold an entry, `op(A, beta)` where only `self` does and `op(alpha, B)`
+        where only `other` does — `A.eunion(B, T.MINUS, 0, 0)` is A - B, where `eadd` would copy B's lone entries unnegated.  `alpha` / `beta` are Python numbers
+        of the promoted type; `op=None` picks the default as `eadd` does; a binary operator only (there are no Monoid / Semiring forms)."""
+        typ = types.promote(self.type, other.type)
+        if op is None:
+            op = current_binop.get(None) or typ._default_addop()
+        if op.kind != "BinaryOp":
+            raise TypeError("eunion takes a binary operator")
+        if out is None:
+            out = Matrix.sparse(cast or typ, self.nrows, self.ncols)
+        mh, ah, dh = get_args(mask, accum, desc)
+        return eunion(lib.GxB_Matrix_eWiseUnion, out, mh, ah, op, self, alpha, other, beta, dh, typ)
 
     def iseq(self, other, eq_op=None):
         """True when both matrices have the same pattern and equal values (reference: matrix.py:1436-1453)."""

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi, types, descriptor as _d
 from ._capi import lib, u64
-from .base import check, NoValue
+from .base import check, eunion, NoValue
 from .matrix import get_args, _p
 from .types import current_semiring, current_binop, current_monoid
 
@@ -335,6 +335,19 @@ class Vector:
 
     def emult(self, other, mult_op=None, cast=None, out=None, mask=None, accum=None, desc=None):
         return self._ewise("eWiseMult", other, mult_op, cast, out, mask, accum, desc, lambda t: t._default_multop())
+
+    def eunion(self, other, op, alpha, beta, cast=None, out=None, mask=None, accum=None, desc=None):
+        """`GxB_Vector_eWiseUnion`: `op(u, v)` where both hold an entry, `op(u, beta)` where only `self` does, `op(alpha, v)` where only `other` does (see
+        `Matrix.eunion`); runs eagerly, after whatever is queued on its operands."""
+        typ = types.promote(self.type, other.type)
+        if op is None:
+            op = current_binop.get(None) or typ._default_addop()
+        if op.kind != "BinaryOp":
+            raise TypeError("eunion takes a binary operator")
+        if out is None:
+            out = Vector.sparse(cast or typ, self.size)
+        mh, ah, dh = get_args(mask, accum, desc)
+        return eunion(lib.GxB_Vector_eWiseUnion, out, mh, ah, op, self, alpha, other, beta, dh, typ)
 
     def iseq(self, other, eq_op=None):
         """Same pattern and equal values (reference: vector.py:188-235: size, nvals, eWiseMult(EQ) into BOOL, nvals, LAND-reduce).  Two vectors of one built-in

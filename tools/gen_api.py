@@ -606,6 +606,16 @@ GrB_Info GxB_Matrix_apply_BinaryOp1st(GrB_Matrix C, const GrB_Matrix Mask, const
 GrB_Info GxB_Matrix_apply_BinaryOp2nd(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Matrix A, const GxB_Scalar y, const GrB_Descriptor desc);
 GrB_Info GxB_Vector_apply_BinaryOp1st(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GxB_Scalar x, const GrB_Vector u, const GrB_Descriptor desc);
 GrB_Info GxB_Vector_apply_BinaryOp2nd(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp op, const GrB_Vector u, const GxB_Scalar y, const GrB_Descriptor desc);
+/* Element-wise union with fill values (the SuiteSparse 6 entry points): on the union of the two patterns T(i,j) = add(A(i,j), B(i,j)) where both operands hold an
+   entry, add(A(i,j), beta) where only A does, add(alpha, B(i,j)) where only B does — eWiseAdd copies the single entry there and never calls the operator, which is
+   wrong for MINUS, DIV and the comparisons.  Then C<Mask, replace> = accum(C, T) as in eWiseAdd; GrB_INP0 / GrB_INP1 transpose A / B (matrix form); C may be A or B.
+   alpha is typecast into add's x type and beta into its y type, A and B as in eWiseAdd; add may be user-defined (GxB_BinaryOp_new).  A NULL C, add, A, B, alpha or
+   beta: GrB_NULL_POINTER; an uninitialised object: GrB_UNINITIALIZED_OBJECT; a scalar without an entry: GrB_INVALID_VALUE — these three before a device is asked
+   for; a complex scalar or container: GrB_DOMAIN_MISMATCH; then the dimensions.  Runs eagerly (never queued in non-blocking mode; deferred work is completed
+   first).  GrBX_last_kernel_plan names the route: "ewise_union<on=matrix|vector,op=...> k_merge_fill<union> | k_vec_ewise_fused<union> | k_vec_ewise<union>",
+   "ewise_batch<... as one vector, union>", "ewise_rows<N x vector eWise union>", "userop<name=...,kind=eunion,...>".  No Monoid / Semiring forms. */
+GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp add, const GrB_Matrix A, const GxB_Scalar alpha, const GrB_Matrix B, const GxB_Scalar beta, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_eWiseUnion(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp add, const GrB_Vector u, const GxB_Scalar alpha, const GrB_Vector v, const GxB_Scalar beta, const GrB_Descriptor desc);
 extern double GxB_ALWAYS_HYPER;
 extern double GxB_NEVER_HYPER;
 extern double GxB_HYPER_DEFAULT;
