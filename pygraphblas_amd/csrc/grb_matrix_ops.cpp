@@ -15,6 +15,7 @@
 #include "grb_assign_scalar.hpp"
 #include "grb_lazy.hpp"
 #include "grb_hostmap.hpp"      // kind_name: the plan's word for an index argument
+#include "grb_spmm.hpp"
 
 using namespace grb;
 
@@ -146,6 +147,24 @@ void off_table_mxm(const SemiringRoute& route, GrB_Matrix C, GrB_Matrix M, GrB_B
   matrix_write_back(C, T, zc, M, dv, accum, t_masked);
 }
 
+// ---- the spmm_full route: op(B) holds every position (judged on the image operand() returned: pending edits applied, the cached transpose of a full matrix is
+// full).  GRB_MI355X_FULL (read per call: a test hook, and the yardstick of tools/spmm_probe.py): 0 never, 1 wherever legal.  By itself: no plain mask (the masked
+// product computes the wanted entries only), at least two columns, and SPMM_FULL_MIN_PRODUCTS products (grb_route.hpp).
+bool spmm_full_wanted(const DevCSR& Ad, const DevCSR& Bd, bool plain_mask) {
+  if (!spmm_is_full(Bd.nrows, Bd.ncols, Bd.nnz)) return false;
+  const int env = route_env("GRB_MI355X_FULL");
+  if (env >= 0) return env == 1;
+  return !plain_mask && Bd.ncols >= 2 && Ad.nnz * (uint64_t)Bd.ncols >= SPMM_FULL_MIN_PRODUCTS;
+}
+// false: T would not fit the 32-bit layout, the call goes on to the route it took before
+bool spmm_full_route(const SpgemmCall& call, const SemiringDesc& sd, bool cast, DevCSR& T) {
+  SpmmPlan p;
+  if (!spmm_full(call, sd, T, p)) return false;
+  g_last_plan = "spmm_full<k=" + std::to_string(p.k) + ",group=" + std::to_string(p.group) + ",slabs=" + std::to_string(p.slabs) + ",long=" + std::to_string(p.nlong) + ",cast=" + (cast ? "1" : "0") +
+                "> k_spmm_rowflags k_full_pattern " + (p.nlong ? "k_spmm_long_tasks " : "") + (p.group ? "k_spmm_narrow " : "k_spmm_wide ") + (p.nlong ? "k_spmm_fold " : "");
+  return true;
+}
+
 void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
   const SemiringRoute route = semiring_route(semiring);
   if (route.refuses_layout_by_name()) {      // (its layout refusal needs initialised operands, and comes before a device is asked for)
@@ -190,6 +209,8 @@ void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semirin
   }
   if (mxm_few_rows_wanted(Ad, Bd)) {            // a handful of output rows (batched BC frontiers): one vxm per row, see grb_mxm_rows.cpp
     mxm_few_rows(Ad, A->type, M, dv, semiring, B, sd.zcode, T); t_masked = true;
+  } else if (spmm_full_wanted(Ad, Bd, M && !dv.mask_comp) && spmm_full_route(call, sd, (uses_a && A->type->code != sd.zcode) || (uses_b && B->type->code != sd.zcode), T)) {
+    // a full right operand (feature propagation, k seeds at once): T's pattern is known in advance, one pass (grb_spmm.hpp); a plain mask is applied by the write-back
   } else if (M && !dv.mask_comp) {
     mat_to_device(M);
     call.M = &M->csr; call.mcode = M->type->code; call.mstruct = dv.mask_struct;

@@ -35,5 +35,8 @@ constexpr uint64_t DIAG_VECTOR_DEVICE_MIN_ENTRIES = 10000;      // GxB_Vector_di
 constexpr uint64_t SORT_DEVICE_MIN_ENTRIES = EXTRACT_DEVICE_MIN_ENTRIES;      // sort and top-k borrow extract's value: not measured on their own
 constexpr uint64_t CONCAT_DEVICE_MIN_ENTRIES = EXTRACT_DEVICE_MIN_ENTRIES;    // GxB_Matrix_concat, on the sum of the tiles' entries: provisional, extract's value, not measured
 constexpr uint64_t SPLIT_DEVICE_MIN_ENTRIES = EXTRACT_DEVICE_MIN_ENTRIES;     // GxB_Matrix_split, on A's entries: provisional, extract's value, not measured
+// Not a host / device threshold but one between two device routes of GrB_mxm: products (nnz(A) k) from which an unmasked product with a full right operand takes
+// the spmm_full route by itself instead of the two-pass hash product (GRB_MI355X_FULL: 0 never, 1 wherever legal).
+constexpr uint64_t SPMM_FULL_MIN_PRODUCTS = 1ull << 18;          // the work count batch_wanted uses; measured: from 2.3e5 products (R-MAT-14, k = 1) up the route never lost to GRB_MI355X_FULL=0, the crossover below was not searched (DESIGN.md "Products with a full operand")
 
 }  // namespace grb

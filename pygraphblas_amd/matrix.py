@@ -264,6 +264,39 @@ class Matrix:
         check(lib.GrBX_Matrix_build_at(m._h, args[0], args[1], args[2], u64(n), C.c_void_p(dup.get_op()) if dup is not None else None, location), m)
         return m
 
+    @classmethod
+    def from_dense(cls, X, typ=None):
+        """The FULL matrix whose entries are the 2-D array `X` (a numpy array, or a torch tensor on the CPU or on the library's GPU: read where it is), through
+        GrBX_Matrix_import_Full: one copy of the values and one fill kernel for the closed-form pattern, no tuples.  The type comes from the dtype when not given;
+        a numpy array of another dtype is cast, a tensor is not (use X.to(...) first).  `A.mxm(Matrix.from_dense(H))` is the product with a full operand."""
+        by_dtype = _types_by_dtype_name()
+        tensor = not isinstance(X, np.ndarray) and hasattr(X, "data_ptr")
+        if not tensor:
+            X = np.asarray(X)
+        if len(X.shape) != 2:
+            raise ValueError("from_dense takes a two-dimensional array")
+        name = str(X.dtype).replace("torch.", "")
+        if typ is None:
+            if name not in by_dtype:
+                raise TypeError(f"no GraphBLAS type for an array of dtype {X.dtype}")
+            typ = by_dtype[name]
+        location = 0
+        if tensor:
+            if name != str(np.dtype(typ._np)):
+                raise TypeError(f"values of dtype {X.dtype} for a {typ.__name__} container: from_dense does not cast a tensor (use X.to(...) first)")
+            X = X.contiguous()
+            if X.device.type == "cuda":
+                import torch
+                torch.cuda.current_stream(X.device).synchronize()      # whatever produced the tensor has finished before the library's stream reads it
+                location = 1
+            ptr = _tensor_ptr(X)
+        else:
+            X = np.ascontiguousarray(X, typ._np)
+            ptr = _p(X)
+        h = C.c_void_p()
+        check(lib.GrBX_Matrix_import_Full(C.byref(h), C.c_void_p(typ._h), u64(X.shape[0]), u64(X.shape[1]), ptr, C.c_int(location)))
+        return cls(h, typ)
+
     # ---- text formats (SURVEY.md §8f rank 3): one numpy parse + one bulk build instead of one setElement per entry -------------
     @staticmethod
     def _read_triples(path, skip, delimiter=None):
@@ -561,6 +594,25 @@ class Matrix:
             torch.cuda.current_stream(dev).synchronize()
         check(lib.GrBX_Matrix_export_CSR(self._h, _tensor_ptr(rp), _tensor_ptr(ci), _tensor_ptr(x), C.c_int(location)), self)
         return rp, ci, x
+
+    @property
+    def is_full(self):
+        """Every position holds an entry: what makes the matrix a full operand of `mxm` (and what `to_dense_tensor` needs)."""
+        return self.nvals == self.nrows * self.ncols
+
+    def to_dense_tensor(self):
+        """The values of a FULL matrix as a (nrows, ncols) torch tensor of the type's dtype on the library's GPU (CPU without one): one copy of the value array
+        through GrBX_Matrix_export_Full.  A matrix with a position that holds no entry raises InvalidValue."""
+        import torch
+        if not self.is_full:
+            check(lib.GrBX_Matrix_export_Full(self._h, None, C.c_int(0)), self)      # (the library's own refusal, before anything of that shape is allocated)
+        vdt = _torch_dtype(self.type)
+        dev, location = _tensor_target()
+        out = torch.empty((self.nrows, self.ncols), dtype=vdt, device=dev)
+        if location:
+            torch.cuda.current_stream(dev).synchronize()
+        check(lib.GrBX_Matrix_export_Full(self._h, _tensor_ptr(out), C.c_int(location)), self)
+        return out
 
     def to_scipy_sparse(self):
         import scipy.sparse as sp

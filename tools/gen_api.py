@@ -584,6 +584,14 @@ GrB_Info GrBX_build_thresholds(uint64_t *out);   /* three words: tuples from whi
 GrB_Info GrBX_Matrix_extractTuples_at(GrB_Index *I, GrB_Index *J, void *X, GrB_Index *n, const GrB_Matrix A, int location);
 GrB_Info GrBX_Vector_extractTuples_at(GrB_Index *I, void *X, GrB_Index *n, const GrB_Vector v, int location);
 GrB_Info GrBX_tuples_geometry(uint64_t *out);   /* out[0] entries per tile of the matrix kernel, out[1] positions per tile of the vector kernel, out[2] the grid cap in workgroups: what the tests take their edges from */
+/* full matrices (every position holds an entry): values is the row-major nrows x ncols array of the type's own values, location 0 = a host array, 1 = a device
+   array; the values are copied.  A full matrix is stored as the CSR whose row pointer and columns are closed form, built in HBM by one copy and one fill kernel
+   (no tuples, no host mirror).  import: a complex type is GrB_DOMAIN_MISMATCH, nrows * ncols >= 2^32 - 16 GrB_INVALID_VALUE, a zero dimension gives an empty
+   matrix.  export: one copy of the value array; GrB_INVALID_VALUE unless nvals == nrows * ncols.  GrB_mxm with such a matrix as its right operand may take the
+   one-pass "spmm_full<k=K,group=G,slabs=S,long=N,cast=0|1> ..." route (GRB_MI355X_FULL: 0 never, 1 wherever legal). */
+GrB_Info GrBX_Matrix_import_Full(GrB_Matrix *A, GrB_Type type, GrB_Index nrows, GrB_Index ncols, const void *values, int location);
+GrB_Info GrBX_Matrix_export_Full(const GrB_Matrix A, void *values, int location);   /* GrB_INVALID_VALUE unless nvals == nrows * ncols */
+GrB_Info GrBX_spmm_geometry(uint64_t *out);   /* out[0] L, out[1] columns per slab, out[2] waves per workgroup, out[3] grid cap in workgroups, out[4] SPMM_FULL_MIN_PRODUCTS */
 /* index-list extract / assign with a list that may lie in HBM: the arguments of the GrB_ namesake plus the location of each list.  location 0 = a host array, GrB_ALL
    or a GxB_RANGE / GxB_STRIDE / GxB_BACKWARDS triple: exactly the GrB_ call.  1 = `ni` 64-bit indices at a device address (or GrB_ALL; a range code as the count is
    GrB_INVALID_VALUE): parsed where they lie (grb_index.hip), the device route wherever it is legal, else the list is copied down once for the host route.
