@@ -20,6 +20,7 @@
 #include "grb_compact.hpp"
 #include "grb_semiring.hpp"
 #include "grb_spmv.hpp"
+#include "grb_spmv_xcd.hpp"
 #include <vector>
 
 namespace grb {
@@ -148,6 +149,85 @@ const std::string& xcd_mapping() {
 }  // namespace grb
 
 extern "C" GrB_Info GrBX_last_plan_build_ms(float* ms) { if (!ms) return GrB_NULL_POINTER; *ms = grb::g_xcd_plan_build_ms; return GrB_SUCCESS; }
+// ---- a read-only view of a matrix's kernel-X plan (tests/test_spmv_xcd_at_size_gpu.py asserts from it that a case reached the edge it was built for) ----
+// Nothing here builds or changes a plan: the scalars are the plan's own fields, the per-stream numbers come out of its argument block, the per-tile
+// words are copies of tinfo (16-bit column plane) or of trow plus the tiles' cold counts, counted from the 32-bit column words the plan keeps.
+namespace grb {
+constexpr uint64_t XF_HEAD = 24, XF_PER_STREAM = 4;
+static const XcdPlan* xcd_plan_of(GrB_Matrix A, int transposed) {
+  const DevCSR& R = transposed ? A->csc : A->csr;
+  const XcdPlan* P = R.valid ? static_cast<const XcdPlan*>(R.derived.xcd.get()) : nullptr;
+  return P && (P->tsize == 4 || P->tsize == 8) ? P : nullptr;
+}
+static uint32_t xcd_total_tiles(const XcdPlan* P) { return P->tbase[P->NS]; }
+// 32-bit format: index of every tile's first cold entry among the cold entries of all tiles (what tinfo[2t + 1] is in the 16-bit format); returns their number
+static uint64_t xcd_cold_prefix(const XcdPlan* P, std::vector<uint32_t>& first) {
+  const uint32_t ntiles = xcd_total_tiles(P);
+  first.assign((size_t)ntiles + 1, 0u);
+  if (!ntiles || !P->pcol.p) return 0;
+  DevBuf tcnt(((size_t)ntiles + 1) * 4);
+  unsigned nb = (ntiles + 3) / 4; if (nb > 16384) nb = 16384;
+  hipLaunchKernelGGL(k_xc_count, dim3(nb), dim3(256), 0, stream(), P->pcol.as<uint32_t>(), ntiles, 0u, tcnt.as<uint32_t>());
+  std::vector<uint32_t> cnt(ntiles);
+  GRB_HIP(hipMemcpyAsync(cnt.data(), tcnt.p, (size_t)ntiles * 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+  uint64_t tot = 0;
+  for (uint32_t t = 0; t < ntiles; t++) { first[t] = (uint32_t)tot; tot += cnt[t]; }
+  first[ntiles] = (uint32_t)tot;
+  return tot;
+}
+}  // namespace grb
+
+extern "C" GrB_Info GrBX_Matrix_xcd_plan_facts(const GrB_Matrix A, int transposed, uint64_t* out, GrB_Index nout) {
+  using namespace grb;
+  if (!A || !out) return GrB_NULL_POINTER;
+  if (!check_obj(A)) return GrB_UNINITIALIZED_OBJECT;
+  const XcdPlan* P = xcd_plan_of(A, transposed);
+  if (!P) return GrB_NO_VALUE;
+  if (nout < XF_HEAD + XF_PER_STREAM * (uint64_t)P->NS) return GrB_INVALID_VALUE;
+  try {
+    const bool c16 = P->tsize == 8 ? xt_fmt<uint64_t>::C16 : xt_fmt<uint32_t>::C16;
+    const uint64_t H = P->tsize == 8 ? (uint64_t)xt_hot<uint64_t>::H : (uint64_t)xt_hot<uint32_t>::H;
+    const uint64_t HOT0 = P->tsize == 8 ? (uint64_t)xt_hot<uint64_t>::HOT : (uint64_t)xt_hot<uint32_t>::HOT;
+    static_assert(sizeof(XtPanel<uint32_t>) == sizeof(XtPanel<uint64_t>), "the argument block has one layout for every value type");
+    std::vector<XtPanel<uint64_t>> ha(XPMAX);
+    GRB_HIP(hipMemcpyAsync((void*)ha.data(), P->args.p, sizeof(XtPanel<uint64_t>) * XPMAX, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
+    uint64_t ncold = P->ncold;
+    if (!c16) { std::vector<uint32_t> first; ncold = xcd_cold_prefix(P, first); }
+    const uint64_t head[XF_HEAD] = {H, P->sell && HOT0 == H ? H - 1 : HOT0, (uint64_t)P->S, (uint64_t)P->NP, (uint64_t)P->NS, P->own ? 1u : 0u, P->F, ncold,
+                                    (uint64_t)P->vbytes, P->has_vals ? 1u : 0u, P->m_ok ? 1u : 0u, P->m_wide ? 1u : 0u, P->m_nblocks, P->m_slots,
+                                    (uint64_t)WP_ENT, WP_CHUNK, XM_ROWS, XM_TARGET, XM_SLOTS, (uint64_t)P->tsize, xcd_total_tiles(P), c16 ? 1u : 0u, XP_RB, P->sell ? 1u : 0u};
+    for (uint64_t i = 0; i < XF_HEAD; i++) out[i] = head[i];
+    for (int k = 0; k < P->NS; k++) {
+      uint64_t* o = out + XF_HEAD + XF_PER_STREAM * (uint64_t)k;
+      o[0] = P->ne[k]; o[1] = P->ntiles[k]; o[2] = P->nhot[k]; o[3] = ha[k].tiles_per_chunk;
+    }
+  } catch (...) { return GrB_PANIC; }
+  return GrB_SUCCESS;
+}
+extern "C" GrB_Info GrBX_Matrix_xcd_plan_tiles(const GrB_Matrix A, int transposed, uint32_t* tiles, GrB_Index ntiles, uint32_t* bstart, GrB_Index nbstart) {
+  using namespace grb;
+  if (!A || !tiles) return GrB_NULL_POINTER;
+  if (!check_obj(A)) return GrB_UNINITIALIZED_OBJECT;
+  const XcdPlan* P = xcd_plan_of(A, transposed);
+  if (!P) return GrB_NO_VALUE;
+  const uint32_t nt = xcd_total_tiles(P);
+  if (ntiles != nt || (bstart && P->m_ok && nbstart != (GrB_Index)P->m_nblocks + 1)) return GrB_INVALID_VALUE;
+  try {
+    if (P->tinfo.p) {
+      if (nt) GRB_HIP(hipMemcpyAsync(tiles, P->tinfo.p, (size_t)nt * 8, hipMemcpyDeviceToHost, stream()));
+    } else {
+      if (!P->trow.p || !P->pcol.p) return GrB_NO_VALUE;
+      std::vector<uint32_t> first, trow(nt);
+      xcd_cold_prefix(P, first);
+      if (nt) GRB_HIP(hipMemcpyAsync(trow.data(), P->trow.p, (size_t)nt * 4, hipMemcpyDeviceToHost, stream()));
+      GRB_HIP(hipStreamSynchronize(stream()));
+      for (uint32_t t = 0; t < nt; t++) { tiles[2 * (size_t)t] = trow[t]; tiles[2 * (size_t)t + 1] = first[t]; }
+    }
+    if (bstart && P->m_ok) GRB_HIP(hipMemcpyAsync(bstart, P->m_bstart.p, ((size_t)P->m_nblocks + 1) * 4, hipMemcpyDeviceToHost, stream()));
+    GRB_HIP(hipStreamSynchronize(stream()));
+  } catch (...) { return GrB_PANIC; }
+  return GrB_SUCCESS;
+}
 extern "C" GrB_Info GrBX_xcd_mapping(char* buf, int len) {
   if (!buf || len <= 0) return GrB_NULL_POINTER;
   if (!grb::device_ok()) { snprintf(buf, len, "no device"); return GrB_NO_VALUE; }

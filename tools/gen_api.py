@@ -524,6 +524,16 @@ GrB_Info GrBX_device_info(char *name, int name_len, int *compute_units, size_t *
 GrB_Info GrBX_memory_in_use(size_t *bytes);
 GrB_Info GrBX_last_kernel_plan(char *buf, int len); /* which kernels the last hot-path call launched; the device route of an index-list extract leaves "extract_matrix<cols=all|range|table|bisect,rowsort=0|1,transpose=0|1> ...", "extract_col<...>" or "extract_vector<...>", that of an index-list assign "assign_matrix<rows=..,cols=..,rowsort=0|1,transpose=0|1,accum=..> ...", "assign_row<...>", "assign_col<...>" or "assign_vector<index=..,accum=..>", that of a Kronecker product "kronecker<op=..,transpose0=0|1,transpose1=0|1,accum=..> k_kron_rowptr k_kron_fill" */
 GrB_Info GrBX_last_plan_build_ms(float *milliseconds); /* device time of the most recent SpMV plan build (kernel X), 0 if none */
+/* A read-only view of the kernel-X plan a matrix carries (transposed 0: the plan of the by-row image, what GrB_mxv multiplies with; 1: of the cached transpose, GrB_vxm).
+   Neither call builds or changes a plan; GrB_NO_VALUE when there is none.  facts: out[0] H (slots of an LDS table), [1] HOT (columns a table serves), [2] S, [3] NP,
+   [4] NS (streams), [5] own, [6] F (sub-rows), [7] ncold (entries whose column no table serves), [8] vbytes, [9] has_vals, [10] m_ok, [11] m_wide, [12] m_nblocks,
+   [13] m_slots, [14] WP_ENT, [15] WP_CHUNK, [16] XM_ROWS, [17] XM_TARGET, [18] XM_SLOTS, [19] bytes of the value type, [20] tiles of all streams, [21] 1 = 16-bit column
+   plane, 0 = 32-bit words, [22] XP_RB (rows per block of the fallback merge), [23] 1 = lane-per-piece layout; then per stream k at [24 + 4 k]: ne, ntiles, nhot,
+   tiles_per_chunk.  nout >= 24 + 4 NS (280 always suffices), else GrB_INVALID_VALUE.  tiles: two words per tile in stream order, {sub-row of the tile's first entry,
+   index of its first cold entry among the cold entries of all tiles} (tinfo; with 32-bit words trow and the cold flags counted); ntiles must be out[20].  bstart (may be
+   NULL; written when m_ok): the first row of every merge block, nbstart = m_nblocks + 1. */
+GrB_Info GrBX_Matrix_xcd_plan_facts(const GrB_Matrix A, int transposed, uint64_t *out, GrB_Index nout);
+GrB_Info GrBX_Matrix_xcd_plan_tiles(const GrB_Matrix A, int transposed, uint32_t *tiles, GrB_Index ntiles, uint32_t *bstart, GrB_Index nbstart);
 GrB_Info GrBX_lazy_stats(uint64_t *chains, uint64_t *nodes, uint64_t *fills_folded, uint64_t *reduces_fused); /* non-blocking mode: element-wise chain kernels run, operations they carried, `w(:) = s` fills folded into a product's store, reductions fused into a chain */
 GrB_Info GrBX_chain_jit_stats(uint64_t *compiled, uint64_t *launched); /* deferred element-wise chains compiled with hipRTC (grb_chain_jit.cpp): kernels compiled, launches through them */
 GrB_Info GrBX_chain_jit_stats2(uint64_t *compiled, uint64_t *launched, uint64_t *loaded_from_disk); /* ... and the kernels whose code object came from the disk cache (GRB_MI355X_CACHE_DIR) instead of a compilation */
