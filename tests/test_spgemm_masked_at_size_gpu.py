@@ -37,6 +37,7 @@ import matrix_model as MM
 import product_model as PM
 import pygraphblas_amd as gb
 from helpers import TYPE, rand_values
+from spgemm_hash_cases import Pattern, hash_col, pick          # (shared with tests/test_spgemm_hash_at_size_gpu.py)
 from test_matrix_kernels_at_size_gpu import check, desc_of
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pygraphblas_amd", "csrc", "grb_spgemm_kernels.hpp")
@@ -66,11 +67,6 @@ def test_the_constants_are_the_headers():
 
 
 # ---- operands ---------------------------------------------------------------------------------------------------------------------------------------------------
-def hash_col(j, keys):
-    """hash_col of the header for a table of `keys` slots."""
-    return (((np.asarray(j, np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(7)).astype(np.int64) & (keys - 1)
-
-
 def values(rng, typ, n):
     x = rand_values(rng, typ, n)
     if typ.startswith("FP"): x[x == 0] = 0.125
@@ -78,31 +74,6 @@ def values(rng, typ, n):
         at = rng.random(n) < 0.06; i = np.iinfo(MM.NP[typ])
         x[at] = rng.choice(np.array([i.min, i.max, i.max - 1], MM.NP[typ]), size=int(at.sum()))
     return x
-
-
-class Pattern:
-    """Rows as {row: ascending columns}; every other row is empty."""
-
-    def __init__(self, nrows, ncols, rows):
-        self.nrows, self.ncols = nrows, ncols
-        at = sorted(r for r in rows if len(rows[r]))
-        self.lens = np.zeros(nrows, np.int64)
-        for r in at:
-            c = np.asarray(rows[r], np.int64); self.lens[r] = len(c)
-            assert np.all(np.diff(c) > 0) and 0 <= c[0] and c[-1] < ncols, r
-        self.keys = np.concatenate([np.int64(r) * ncols + np.asarray(rows[r], np.int64) for r in at]) if at else np.zeros(0, np.int64)
-        self.rp = np.concatenate(([0], np.cumsum(self.lens)))
-
-    def mat(self, vals):
-        return MM.Mat(self.nrows, self.ncols, self.keys, vals)
-
-    def cols(self, r):
-        return self.keys[self.rp[r]: self.rp[r + 1]] - np.int64(r) * self.ncols
-
-
-def pick(rng, pool, n):
-    """n distinct members of `pool` (an array, or a range end), ascending."""
-    return np.sort(rng.choice(pool, size=n, replace=False)).astype(np.int64)
 
 
 def expected_bins(A, M):
