@@ -16,6 +16,7 @@
 #include "grb_lazy.hpp"
 #include "grb_hostmap.hpp"      // kind_name: the plan's word for an index argument
 #include "grb_spmm.hpp"
+#include "grb_sddmm.hpp"
 
 using namespace grb;
 
@@ -165,6 +166,36 @@ bool spmm_full_route(const SpgemmCall& call, const SemiringDesc& sd, bool cast, 
   return true;
 }
 
+// ---- the sddmm route: a plain mask over the product of two FULL operands, S<M> = X (+).(x) Y' (attention and edge scores, link-prediction scores, the gradient of
+// spmm_full with respect to A's values).  T's pattern is the mask's and every entry is the dot product of two contiguous rows (grb_sddmm.hpp): nnz(M) k products
+// where the masked Gustavson route probes the mask's hash table m k n times.  GRB_MI355X_SDDMM (read per call: a test hook, and the yardstick of
+// tools/sddmm_probe.py): 0 never, 1 wherever legal.  By itself: from SDDMM_MIN_WORK = m k n (grb_route.hpp).  Fullness is judged on the operands' OWN images with
+// pending edits applied (a full matrix transposed is full), before any transpose is asked for: the kernel reads op(A) and op(B)' row-major, so a `desc = T1` call
+// reads B's own image and never builds its transpose.
+bool sddmm_wanted(uint64_t m, uint64_t k, uint64_t n) {
+  const int env = route_env("GRB_MI355X_SDDMM");
+  if (env >= 0) return env == 1;
+  return sddmm_by_default(m, k, n, SDDMM_MIN_WORK);
+}
+bool sddmm_operand_full(GrB_Matrix A) {
+  if (!dev_capable(A)) return false;
+  mat_to_device(A);
+  return spmm_is_full(A->csr.nrows, A->csr.ncols, A->csr.nnz);
+}
+// T = the product at every entry of M's pattern.  A structural mask has then been applied (t_masked); a valued one is left to the write-back's filter: T keeps the
+// false entries, the filter drops them, and the result is the masked route's.
+void sddmm_route(GrB_Matrix M, GrB_Matrix A, GrB_Matrix B, const DescView& dv, const SemiringDesc& sd, DevBuf& xcast, DevBuf& ycast, DevCSR& T) {
+  const DevCSR& X = operand(A, dv.tran0); const DevCSR& Y = operand(B, !dv.tran1);      // op(A), m x k, and op(B)', n x k: both row-major value arrays
+  mat_to_device(M);
+  const bool uses_x = binop_uses_x(sd.mulop), uses_y = binop_uses_y(sd.mulop);
+  const void* xv = uses_x ? cast_values(sd.zcode, A->type->code, X.val.p, X.nnz, xcast) : nullptr;
+  const void* yv = uses_y ? cast_values(sd.zcode, B->type->code, Y.val.p, Y.nnz, ycast) : nullptr;
+  const bool cast = (uses_x && A->type->code != sd.zcode) || (uses_y && B->type->code != sd.zcode);
+  SddmmPlan p;
+  sddmm_full(M->csr, xv, yv, X.ncols, sd, T, p);
+  g_last_plan = "sddmm<k=" + std::to_string(p.k) + ",group=" + std::to_string(p.group) + ",entries=" + std::to_string(p.entries) + ",cast=" + (cast ? "1" : "0") + "> " + (p.entries ? "k_sddmm " : "");
+}
+
 void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
   const SemiringRoute route = semiring_route(semiring);
   if (route.refuses_layout_by_name()) {      // (its layout refusal needs initialised operands, and comes before a device is asked for)
@@ -195,9 +226,17 @@ void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semirin
       matrix_write_back(C, T, sd.zcode, M, dv, accum, true); return;
     }
   }
+  DevBuf acast, bcast;
+  if (M && !dv.mask_comp && a.c >= 1 && dev_capable(M) && sddmm_operand_full(A) && sddmm_operand_full(B)) {
+    // two full operands under a plain mask: the routes in front decline first (they look at op(A)'s and op(B)'s shape and count only, known without a transpose)
+    DevCSR ah, bh; ah.nrows = (uint32_t)a.r; ah.ncols = (uint32_t)a.c; ah.nnz = A->csr.nnz; bh.nrows = (uint32_t)b.r; bh.ncols = (uint32_t)b.c; bh.nnz = B->csr.nnz;
+    if (!mxm_few_rows_wanted(ah, bh) && !spmm_full_wanted(ah, bh, true) && sddmm_wanted(a.r, a.c, b.c)) {
+      DevCSR T; sddmm_route(M, A, B, dv, sd, acast, bcast, T);
+      matrix_write_back(C, T, sd.zcode, M, dv, accum, dv.mask_struct); return;
+    }
+  }
   const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);
   const bool uses_a = binop_uses_x(sd.mulop), uses_b = binop_uses_y(sd.mulop);
-  DevBuf acast, bcast;
   SpgemmCall call{};
   call.A = &Ad; call.B = &Bd;
   call.aval = uses_a ? cast_values(sd.zcode, A->type->code, Ad.val.p, Ad.nnz, acast) : nullptr;

@@ -38,5 +38,8 @@ constexpr uint64_t SPLIT_DEVICE_MIN_ENTRIES = EXTRACT_DEVICE_MIN_ENTRIES;     //
 // Not a host / device threshold but one between two device routes of GrB_mxm: products (nnz(A) k) from which an unmasked product with a full right operand takes
 // the spmm_full route by itself instead of the two-pass hash product (GRB_MI355X_FULL: 0 never, 1 wherever legal).
 constexpr uint64_t SPMM_FULL_MIN_PRODUCTS = 1ull << 18;          // the work count batch_wanted uses; measured: from 2.3e5 products (R-MAT-14, k = 1) up the route never lost to GRB_MI355X_FULL=0, the crossover below was not searched (DESIGN.md "Products with a full operand")
+// Between two device routes of GrB_mxm as well: the work of the masked Gustavson route, m k n mask probes, from which a product of two full operands under a plain
+// mask takes the sddmm route by itself (GRB_MI355X_SDDMM: 0 never, 1 wherever legal).
+constexpr uint64_t SDDMM_MIN_WORK = 1ull << 16;                  // the smallest measured work count: from 6.6e4 (m = n = 256, k = 1: 0.016 ms against 0.177 ms) to 4.3e9 (m = n = 4096, k = 256: 0.141 against 1.496 ms) the route never lost to GRB_MI355X_SDDMM=0 in 100 points, the crossover below was not searched (DESIGN.md "Masked product of two full matrices")
 
 }  // namespace grb

@@ -1,9 +1,10 @@
 // grb_spmm_ops.cpp — full matrices across the C ABI: GrBX_Matrix_import_Full / GrBX_Matrix_export_Full (a row-major dense array in, the value array out) and
-// GrBX_spmm_geometry.  A full matrix has no format of its own: it is the CSR whose row pointer and columns are closed form (rowptr[i] = i ncols,
+// GrBX_spmm_geometry / GrBX_sddmm_geometry.  A full matrix has no format of its own: it is the CSR whose row pointer and columns are closed form (rowptr[i] = i ncols,
 // col[p] = p mod ncols) and whose value array IS the dense array, so the import is one value copy plus the fill kernel the spmm_full route of GrB_mxm uses for
 // T's pattern (grb_spmm.hip), and the export is one copy.  Nothing passes through tuples or a host mirror.
 #include "grb_container.hpp"
 #include "grb_spmm.hpp"
+#include "grb_sddmm.hpp"
 
 using namespace grb;
 
@@ -50,6 +51,12 @@ GrB_Info GrBX_Matrix_export_Full(const GrB_Matrix A, void* values, int location)
 GrB_Info GrBX_spmm_geometry(uint64_t* out) {
   if (!out) return GrB_NULL_POINTER;
   out[0] = SPMM_L; out[1] = SPMM_SLAB; out[2] = SPMM_WAVES; out[3] = SPMM_GRID_CAP; out[4] = SPMM_FULL_MIN_PRODUCTS; return GrB_SUCCESS;
+}
+
+// the shape of the masked product of two full matrices (grb_sddmm_geom.hpp): what its tests take their edges from
+GrB_Info GrBX_sddmm_geometry(uint64_t* out) {
+  if (!out) return GrB_NULL_POINTER;
+  out[0] = SDDMM_TILE; out[1] = SDDMM_WAVES; out[2] = SDDMM_GRID_CAP; out[3] = SDDMM_MIN_WORK; return GrB_SUCCESS;
 }
 
 }  // extern "C"

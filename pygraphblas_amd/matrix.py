@@ -854,6 +854,17 @@ class Matrix:
         check(lib.GrB_mxm(out._h, mh, ah, C.c_void_p(semiring.get_op()), self._h, other._h, dh), out)
         return out
 
+    def sddmm(self, X, Y, semiring=None, out=None, accum=None, structural=True):
+        """The sampled dense-dense product on this matrix's pattern: `S<self> = X (+).(x) Y'`, S(i, j) = (+)_l X(i, l) (x) Y(j, l) for the entries (i, j) of `self`
+        (m x n), with X m x k and Y n x k — attention / edge scores, link-prediction scores on candidate edges, the residual of a factorisation on the observed
+        entries.  Sugar for `X.mxm(Y, semiring, mask=self, out=out, accum=accum, desc=ST1)` (`T1` when `structural` is false: entries of `self` that hold a false
+        value are then left out).  With X and Y full (`Matrix.from_dense`) the call takes the one-pass `sddmm` route of GrB_mxm and reads Y as it lies."""
+        if semiring is None:
+            semiring = current_semiring.get(None)
+        if out is None:
+            out = Matrix.sparse(semiring.ztype if semiring is not None else types.promote(X.type, Y.type), self.nrows, self.ncols)
+        return X.mxm(Y, semiring=semiring, mask=self, out=out, accum=accum, desc=_d.ST1 if structural else _d.T1)
+
     def mxv(self, other, semiring=None, cast=None, out=None, mask=None, accum=None, desc=None):
         """Matrix-vector multiply `w<mask> = accum(w, self (+).(x) other)`  (reference: matrix.py:2586-2726)."""
         from .vector import Vector

@@ -602,6 +602,12 @@ GrB_Info GrBX_tuples_geometry(uint64_t *out);   /* out[0] entries per tile of th
 GrB_Info GrBX_Matrix_import_Full(GrB_Matrix *A, GrB_Type type, GrB_Index nrows, GrB_Index ncols, const void *values, int location);
 GrB_Info GrBX_Matrix_export_Full(const GrB_Matrix A, void *values, int location);   /* GrB_INVALID_VALUE unless nvals == nrows * ncols */
 GrB_Info GrBX_spmm_geometry(uint64_t *out);   /* out[0] L, out[1] columns per slab, out[2] waves per workgroup, out[3] grid cap in workgroups, out[4] SPMM_FULL_MIN_PRODUCTS */
+/* GrB_mxm of two FULL matrices under a plain mask, S<M> = X (+).(x) Y' (X m x k, Y n x k: C.mxm(X, Y, mask = M, desc = T1); sampled dense-dense product), may
+   take the one-pass "sddmm<k=K,group=G,entries=E,cast=0|1> k_sddmm" route: T's pattern is the mask's, every entry the dot product of two contiguous rows
+   (GRB_MI355X_SDDMM: 0 never, 1 wherever legal; by itself from SDDMM_MIN_WORK = m k n).  Fold order, a function of k alone: with G = pow2ceil(min(k, 64)) lane g
+   of an entry's group folds its products l = g, g + G, ... left to right from the first one, then p_g = p_g (+) p_{g + s} for s = G / 2 ... 1 where
+   g + s < min(k, G): the oracle's left-to-right order for k <= 2 only; the same bits on every run and wherever the entry lies in the mask. */
+GrB_Info GrBX_sddmm_geometry(uint64_t *out);   /* out[0] mask entries per tile (= per workgroup), out[1] waves per workgroup, out[2] grid cap in workgroups, out[3] SDDMM_MIN_WORK */
 /* index-list extract / assign with a list that may lie in HBM: the arguments of the GrB_ namesake plus the location of each list.  location 0 = a host array, GrB_ALL
    or a GxB_RANGE / GxB_STRIDE / GxB_BACKWARDS triple: exactly the GrB_ call.  1 = `ni` 64-bit indices at a device address (or GrB_ALL; a range code as the count is
    GrB_INVALID_VALUE): parsed where they lie (grb_index.hip), the device route wherever it is legal, else the list is copied down once for the host route.
