@@ -17,6 +17,7 @@
 #include "grb_hostmap.hpp"      // kind_name: the plan's word for an index argument
 #include "grb_spmm.hpp"
 #include "grb_sddmm.hpp"
+#include "grb_gemm.hpp"
 
 using namespace grb;
 
@@ -196,6 +197,28 @@ void sddmm_route(GrB_Matrix M, GrB_Matrix A, GrB_Matrix B, const DescView& dv, c
   g_last_plan = "sddmm<k=" + std::to_string(p.k) + ",group=" + std::to_string(p.group) + ",entries=" + std::to_string(p.entries) + ",cast=" + (cast ? "1" : "0") + "> " + (p.entries ? "k_sddmm " : "");
 }
 
+// ---- the gemm_full route: op(A) AND op(B) hold every position (judged like the sddmm route's operands: on their own images, before any transpose is asked for) —
+// the dense update H W of a GNN layer, a Gram matrix X X', all-pairs MIN_PLUS on a dense block.  T is full too: a closed-form pattern and one register-tiled
+// kernel that stages both operands in LDS and reads a transposed operand where it lies (grb_gemm.hpp); any mask is applied by the write-back.  GRB_MI355X_GEMM
+// (read per call: a test hook, and the yardstick of tools/gemm_probe.py): 0 never, 1 wherever legal, a plain mask included (the sddmm route then stands back).
+// By itself: exactly the calls spmm_full took when its left operand happened to be full — no plain mask, at least two columns, GEMM_FULL_MIN_WORK = m k n
+// (grb_route.hpp) — and none while GRB_MI355X_FULL is set: that hook keeps its meaning.
+bool gemm_full_wanted(int env, uint64_t m, uint64_t k, uint64_t n, bool plain_mask) {
+  if (env >= 0) return env == 1;
+  if (route_env("GRB_MI355X_FULL") >= 0) return false;
+  return gemm_by_default(m, k, n, plain_mask, GEMM_FULL_MIN_WORK);
+}
+void gemm_full_route(GrB_Matrix A, GrB_Matrix B, uint64_t m, uint64_t n, uint64_t k, const DescView& dv, const SemiringDesc& sd, DevBuf& acast, DevBuf& bcast, DevCSR& T) {
+  const bool uses_a = binop_uses_x(sd.mulop), uses_b = binop_uses_y(sd.mulop);
+  const void* av = uses_a ? cast_values(sd.zcode, A->type->code, A->csr.val.p, A->csr.nnz, acast) : nullptr;
+  const void* bv = uses_b ? cast_values(sd.zcode, B->type->code, B->csr.val.p, B->csr.nnz, bcast) : nullptr;
+  const bool cast = (uses_a && A->type->code != sd.zcode) || (uses_b && B->type->code != sd.zcode);
+  GemmPlan p;
+  gemm_full((uint32_t)m, (uint32_t)n, (uint32_t)k, av, dv.tran0, bv, dv.tran1, sd, T, p);
+  g_last_plan = "gemm_full<m=" + std::to_string(p.m) + ",n=" + std::to_string(p.n) + ",k=" + std::to_string(p.k) + ",tile=" + std::to_string(p.tm) + "x" + std::to_string(p.tn) +
+                ",layout=" + (p.ta ? "T" : "N") + (p.tb ? "T" : "N") + ",cast=" + (cast ? "1" : "0") + "> k_full_pattern k_gemm_full ";
+}
+
 void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Matrix B, GrB_Descriptor desc) {
   const SemiringRoute route = semiring_route(semiring);
   if (route.refuses_layout_by_name()) {      // (its layout refusal needs initialised operands, and comes before a device is asked for)
@@ -227,12 +250,20 @@ void do_mxm(GrB_Matrix C, GrB_Matrix M, GrB_BinaryOp accum, GrB_Semiring semirin
     }
   }
   DevBuf acast, bcast;
-  if (M && !dv.mask_comp && a.c >= 1 && dev_capable(M) && sddmm_operand_full(A) && sddmm_operand_full(B)) {
-    // two full operands under a plain mask: the routes in front decline first (they look at op(A)'s and op(B)'s shape and count only, known without a transpose)
+  if (a.c >= 1 && sddmm_operand_full(A) && sddmm_operand_full(B)) {
+    // two full operands: the routes in front decline first (they look at op(A)'s and op(B)'s shape and count only, known without a transpose)
     DevCSR ah, bh; ah.nrows = (uint32_t)a.r; ah.ncols = (uint32_t)a.c; ah.nnz = A->csr.nnz; bh.nrows = (uint32_t)b.r; bh.ncols = (uint32_t)b.c; bh.nnz = B->csr.nnz;
-    if (!mxm_few_rows_wanted(ah, bh) && !spmm_full_wanted(ah, bh, true) && sddmm_wanted(a.r, a.c, b.c)) {
-      DevCSR T; sddmm_route(M, A, B, dv, sd, acast, bcast, T);
-      matrix_write_back(C, T, sd.zcode, M, dv, accum, dv.mask_struct); return;
+    if (!mxm_few_rows_wanted(ah, bh)) {
+      const bool plain_mask = M && !dv.mask_comp;
+      const int gemm_env = route_env("GRB_MI355X_GEMM");
+      if (plain_mask && gemm_env != 1 && dev_capable(M) && !spmm_full_wanted(ah, bh, true) && sddmm_wanted(a.r, a.c, b.c)) {
+        DevCSR T; sddmm_route(M, A, B, dv, sd, acast, bcast, T);
+        matrix_write_back(C, T, sd.zcode, M, dv, accum, dv.mask_struct); return;
+      }
+      if (gemm_full_wanted(gemm_env, a.r, a.c, b.c, plain_mask) && !spmm_overflows(a.r, b.c)) {      // (T beyond the 32-bit layout: on to the route the call took before)
+        DevCSR T; gemm_full_route(A, B, a.r, b.c, a.c, dv, sd, acast, bcast, T);
+        matrix_write_back(C, T, sd.zcode, M, dv, accum, false); return;
+      }
     }
   }
   const DevCSR& Ad = operand(A, dv.tran0); const DevCSR& Bd = operand(B, dv.tran1);

@@ -41,5 +41,9 @@ constexpr uint64_t SPMM_FULL_MIN_PRODUCTS = 1ull << 18;          // the work cou
 // Between two device routes of GrB_mxm as well: the work of the masked Gustavson route, m k n mask probes, from which a product of two full operands under a plain
 // mask takes the sddmm route by itself (GRB_MI355X_SDDMM: 0 never, 1 wherever legal).
 constexpr uint64_t SDDMM_MIN_WORK = 1ull << 16;                  // the smallest measured work count: from 6.6e4 (m = n = 256, k = 1: 0.016 ms against 0.177 ms) to 4.3e9 (m = n = 4096, k = 256: 0.141 against 1.496 ms) the route never lost to GRB_MI355X_SDDMM=0 in 100 points, the crossover below was not searched (DESIGN.md "Masked product of two full matrices")
+// And a third: the multiply-adds m k n from which a product of two full operands without a plain mask takes the gemm_full route by itself, given at least two
+// columns and GEMM_MIN_TILES tiles of the result (grb_gemm_geom.hpp) — calls that took spmm_full before, which read the left operand as an ordinary CSR
+// (GRB_MI355X_GEMM: 0 never, 1 wherever legal; GRB_MI355X_FULL set: spmm_full's hook decides).
+constexpr uint64_t GEMM_FULL_MIN_WORK = 1ull << 18;              // the count SPMM_FULL_MIN_PRODUCTS compares nnz(A) k against; measured: of the 128 sweep points from 2^18 up (m = 2^10 .. 2^20, k = 16 .. 256, n = 2 .. 256) the route lost to GRB_MI355X_GEMM=0 only at 4 and 8 tall tiles with k = 256 (0.060 against 0.052 ms), which the tile condition now leaves to spmm_full; the other 126 took 0.13 - 0.78 of its time; the crossover below 2^18 was not searched (DESIGN.md "Product of two full matrices")
 
 }  // namespace grb

@@ -1,10 +1,11 @@
 // grb_spmm_ops.cpp — full matrices across the C ABI: GrBX_Matrix_import_Full / GrBX_Matrix_export_Full (a row-major dense array in, the value array out) and
-// GrBX_spmm_geometry / GrBX_sddmm_geometry.  A full matrix has no format of its own: it is the CSR whose row pointer and columns are closed form (rowptr[i] = i ncols,
+// GrBX_spmm_geometry / GrBX_sddmm_geometry / GrBX_gemm_geometry.  A full matrix has no format of its own: it is the CSR whose row pointer and columns are closed form (rowptr[i] = i ncols,
 // col[p] = p mod ncols) and whose value array IS the dense array, so the import is one value copy plus the fill kernel the spmm_full route of GrB_mxm uses for
 // T's pattern (grb_spmm.hip), and the export is one copy.  Nothing passes through tuples or a host mirror.
 #include "grb_container.hpp"
 #include "grb_spmm.hpp"
 #include "grb_sddmm.hpp"
+#include "grb_gemm.hpp"
 
 using namespace grb;
 
@@ -57,6 +58,13 @@ GrB_Info GrBX_spmm_geometry(uint64_t* out) {
 GrB_Info GrBX_sddmm_geometry(uint64_t* out) {
   if (!out) return GrB_NULL_POINTER;
   out[0] = SDDMM_TILE; out[1] = SDDMM_WAVES; out[2] = SDDMM_GRID_CAP; out[3] = SDDMM_MIN_WORK; return GrB_SUCCESS;
+}
+
+// the shape of the product of two full matrices (grb_gemm_geom.hpp): what its tests take their edges from
+GrB_Info GrBX_gemm_geometry(uint64_t* out) {
+  if (!out) return GrB_NULL_POINTER;
+  out[0] = GEMM_TM_WIDE; out[1] = GEMM_TN_WIDE; out[2] = GEMM_TM_TALL; out[3] = GEMM_TN_TALL; out[4] = GEMM_KT; out[5] = GEMM_WAVES; out[6] = GEMM_GRID_CAP;
+  out[7] = GEMM_FULL_MIN_WORK; out[8] = GEMM_TALL_MAX_N; return GrB_SUCCESS;
 }
 
 }  // extern "C"

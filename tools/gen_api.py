@@ -608,6 +608,12 @@ GrB_Info GrBX_spmm_geometry(uint64_t *out);   /* out[0] L, out[1] columns per sl
    of an entry's group folds its products l = g, g + G, ... left to right from the first one, then p_g = p_g (+) p_{g + s} for s = G / 2 ... 1 where
    g + s < min(k, G): the oracle's left-to-right order for k <= 2 only; the same bits on every run and wherever the entry lies in the mask. */
 GrB_Info GrBX_sddmm_geometry(uint64_t *out);   /* out[0] mask entries per tile (= per workgroup), out[1] waves per workgroup, out[2] grid cap in workgroups, out[3] SDDMM_MIN_WORK */
+/* GrB_mxm of two FULL matrices, T = op(A) (+).(x) op(B) (X.mxm(W), X.mxm(Y, desc = T1): the dense update of a GNN layer, a Gram matrix, all-pairs MIN_PLUS on a
+   dense block), may take the one-pass "gemm_full<m=M,n=N,k=K,tile=TMxTN,layout=NN|NT|TN|TT,cast=0|1> k_full_pattern k_gemm_full" route: a register-tiled kernel
+   that stages both operands in LDS and reads a transposed operand where it lies (GRB_MI355X_GEMM: 0 never, 1 wherever legal; by itself without a plain mask,
+   from 2 columns, GEMM_FULL_MIN_WORK = m k n and 16 tiles of the result, and not while GRB_MI355X_FULL is set).  Fold order: T(i, j) is the left-to-right fold of its products in
+   ascending l from the first one, for every k, whatever the tile, the tile shape, the layout, the grid or the run. */
+GrB_Info GrBX_gemm_geometry(uint64_t *out);   /* out[0], out[1] TM, TN of the wide tile, out[2], out[3] of the tall tile, out[4] KT, out[5] waves per workgroup, out[6] grid cap in workgroups, out[7] GEMM_FULL_MIN_WORK, out[8] the widest result (n) that takes the tall tile */
 /* index-list extract / assign with a list that may lie in HBM: the arguments of the GrB_ namesake plus the location of each list.  location 0 = a host array, GrB_ALL
    or a GxB_RANGE / GxB_STRIDE / GxB_BACKWARDS triple: exactly the GrB_ call.  1 = `ni` 64-bit indices at a device address (or GrB_ALL; a range code as the count is
    GrB_INVALID_VALUE): parsed where they lie (grb_index.hip), the device route wherever it is legal, else the list is copied down once for the host route.
