@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void k_sell_scatter(const uint32_t* __restrict
       else { c = gr.cbase[k] + gr.nc1[k] + (s - gr.g0[k]); const uint32_t ll = lc[c]; ln = o / ll; step = o - ln * ll; }
       const size_t dst = ((size_t)cstep[c] + step) * 64u + ln;
       scol[dst] = (w[j] & (XT_COLD | XT_IDXMASK)) | SW_VALID;
-      if (pval) sval[dst] = pval[q];
+      if (pval) sval[dst] = pval[xt_vpos<T>(q)];                 // (the tile pipeline's plane: 8-byte values lie in two halves per tile)
       if (o == 0) perm[(size_t)c * 64u + (s < gr.g0[k] ? ln : 0u)] = id;
     }
   }

@@ -182,6 +182,16 @@ template <class E, int N> __device__ __forceinline__ void xt_stream_load(__amdgp
   }
 }
 
+// 8-byte values: inside every tile of 256 entries the plan stores the value plane as two halves of 1 KB; half j holds, at lane * 16, the lane's entries 2 j
+// and 2 j + 1 (entry 4 lane + 2 j + i of the tile).  A lane's four values are then two 16-byte loads at `lane * 16` and `1024 + lane * 16`, each covering 8
+// consecutive 128-byte lines of the tile, where the entry order (32 bytes per lane) made each of the two walk all 16 lines and use half of every one.
+// xt_vpos: where entry q of the store (tiles are 256-aligned in it) lies in the plane.  Every reader of the plane goes through it; narrower planes keep
+// the entry order (a lane's values are ONE contiguous load there).
+template <class T> __host__ __device__ __forceinline__ uint64_t xt_vpos(uint64_t q) {
+  if constexpr (sizeof(T) == 8) { const uint64_t e = q & 255ull; return (q & ~255ull) | ((e & 2ull) << 6) | ((e >> 2) << 1) | (e & 1ull); }
+  else return q;
+}
+
 // one panel's share of the plan; the block of XP of these lives in HBM and never changes between calls
 template <class T> struct XtPanel {
   const uint32_t* pcol;      // 32-bit format: column words of the panel's entries (tile t = entries [256 t, 256 t + 256)); nullptr once packed
@@ -255,9 +265,10 @@ __global__ __launch_bounds__(W * 64, 1) void k_spmv_tiles(const XtCall<T> call, 
   const __amdgpu_buffer_rsrc_t c_rsrc = C16 ? __builtin_amdgcn_make_buffer_rsrc((void*)a.col16, (short)0, (int)(a.ntiles * (uint32_t)WP_ENT * 2u), 0x00020000)
                                             : __builtin_amdgcn_make_buffer_rsrc((void*)a.pcol, (short)0, (int)(a.nnz * 4u), 0x00020000);
   const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.extras, (short)0, (int)(C16 ? (a.nextras * 2u + 15u) & ~15ull : 0ull), 0x00020000);
-  const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.aval, (short)0, (int)(!a.aval ? 0u : (VB == (int)sizeof(T) ? a.nnz * (uint32_t)sizeof(T) : a.ntiles * (uint32_t)WP_ENT * (uint32_t)VB)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.aval, (short)0, (int)(!a.aval ? 0u : (VB == (int)sizeof(T) && VB != 8 ? a.nnz * (uint32_t)sizeof(T) : a.ntiles * (uint32_t)WP_ENT * (uint32_t)VB)), 0x00020000);
   // (narrow plane: the range covers whole tiles — the plan's padding is zeros — because a lane's four values are ONE 8-byte load and the range check would
-  //  cut the last lane's live values off with the panel's end; the wide plane's loads are checked dword by dword)
+  //  cut the last lane's live values off with the panel's end; the 4-byte plane's loads are checked dword by dword.  The 8-byte plane covers whole tiles
+  //  as well: a partial last tile's live values lie in both of its halves (xt_vpos), the second of which begins 1 KB into the tile)
   __syncthreads();                                      // (the chunk counter is zero for every wave: the first tiles below may already draw dynamic chunks.  The table is NOT filled yet)
   // Work split (see k_spmv_wavepipe): chunk ids [0, dyn0) are static ranges of s0 chunks dealt to (workgroup, wave), ids >= dyn0
   // are handed out one at a time by the workgroup's LDS counter; workgroup j of the panel owns those congruent to j.
@@ -323,7 +334,13 @@ __global__ __launch_bounds__(W * 64, 1) void k_spmv_tiles(const XtCall<T> call, 
     const bool ok = s.tile != WP_NONE;
     const uint32_t e0 = ok ? s.tile * (uint32_t)WP_ENT : 0u, left = a.nnz - e0, cnt = !ok ? 0u : (left < (uint32_t)WP_ENT ? left : (uint32_t)WP_ENT);
     if (use_a) {
-      if constexpr (VB == (int)sizeof(T)) xt_stream_load<T, WP_PER>(v_rsrc, ok ? (e0 + lane * WP_PER) * (uint32_t)sizeof(T) : 0xFFFFFFFFu, s.v);
+      if constexpr (VB == 8) {
+        static_assert(sizeof(T) == 8 && WP_PER == 4, "the 8-byte value plane holds a lane's four values as two pairs, one in each half of the tile (xt_vpos)");
+        const uint32_t o = e0 * 8u + (uint32_t)lane * 16u;
+        const xt_v4u lo = __builtin_amdgcn_raw_buffer_load_b128(v_rsrc, (int)(ok ? o : 0xFFFFFFFFu), 0, XT_STREAM_AUX);
+        const xt_v4u hi = __builtin_amdgcn_raw_buffer_load_b128(v_rsrc, (int)(ok ? o + 1024u : 0xFFFFFFFFu), 0, XT_STREAM_AUX);
+        __builtin_memcpy(&s.v[0], &lo, 16); __builtin_memcpy(&s.v[2], &hi, 16);
+      } else if constexpr (VB == (int)sizeof(T)) xt_stream_load<T, WP_PER>(v_rsrc, ok ? (e0 + lane * WP_PER) * (uint32_t)sizeof(T) : 0xFFFFFFFFu, s.v);
       else {
         static_assert(VB == 2 && WP_PER == 4, "the narrow value plane holds four int16 per lane: one 8-byte load");
         uint32_t q[2];

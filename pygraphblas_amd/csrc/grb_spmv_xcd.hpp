@@ -59,6 +59,7 @@ struct XcdPlan {          // lives in DevCSR::xcd (type-erased), built once per 
   uint64_t ne[XPMAX]; uint32_t tbase[XPMAX + 1]; uint32_t ntiles[XPMAX], nhot[XPMAX];      // per stream (NS of them: tile-aligned, one XtPanel and one LDS table each)
   uint64_t F = 0; int tsize = 0; bool has_vals = false; float build_ms = 0;
   int vbytes = 0;          // bytes per value of the panel-major value plane: sizeof(T), or 2 (int16: an integer matrix whose values all fit — pval then holds int16)
+  bool vinter = false;     // the value plane is lane-interleaved inside every tile (xt_vpos: two halves of 1 KB) — every 8-byte plane; the 4- and 2-byte ones are in entry order
   // round 4: S sub-panels per XCD (virtual panel vp = k * S + s lives in physical panel k).  When an XCD's eighth of the operand does not
   // fit its 4 MiB L2 (R-MAT-25 FP32: 16.8 MB; every rank of a row-partitioned run), the lines of u are dealt to XP * S virtual panels and a
   // physical panel's stream holds its S sub-panels one after the other, each in row-major order: the waves of an XCD walk the stream
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(XP_ST) void k_xp_sweep(const XpSweep<T> a) {
         const bool flag = prow != r || (a.vpoff[k] + rel) % a.chunk_entries[k] == 0;       // (prow == WP_NONE is never a row; chunks are cut on the physical stream)
         const uint64_t dest = a.ebase[k] + rel;
         a.pcol[dest] = code | (flag ? WP_ROWSTART : 0u);
-        if (a.pval) a.pval[dest] = a.val[p];
+        if (a.pval) a.pval[xt_vpos<T>(dest)] = a.val[p];             // (8-byte values: the two halves of a tile, grb_spmv_tiles.hpp)
         if (flag) a.rowtmp[dest] = r;
       }
     }
@@ -813,8 +814,10 @@ template <class T> static __global__ void k_xt_fits16(const T* __restrict__ v, u
   }
   if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, 1u);
 }
-template <class T> static __global__ void k_xt_narrow16(const T* __restrict__ v, uint64_t n, int16_t* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) out[i] = (int16_t)v[i];
+// (k_xt_fits16 looks at every stored value, in whatever order; k_xt_narrow16 writes the int16 plane in ENTRY order: it reads the `ntiled` entries of the
+//  whole tiles through xt_vpos and the zeros behind them as they lie)
+template <class T> static __global__ void k_xt_narrow16(const T* __restrict__ v, uint64_t n, uint64_t ntiled, int16_t* __restrict__ out) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) out[i] = (int16_t)v[i < ntiled ? xt_vpos<T>(i) : i];
 }
 
 template <class T> void build_xcd_plan(const DevCSR& M, int ncu, bool with_vals, int force_S = 0) {
@@ -1110,7 +1113,7 @@ template <class T> void build_xcd_plan(const DevCSR& M, int ncu, bool with_vals,
       uint32_t hf = 1; GRB_HIP(hipMemcpyAsync(&hf, flag.p, 4, hipMemcpyDeviceToHost, stream())); GRB_HIP(hipStreamSynchronize(stream()));
       if (hf == 0) {
         DevBuf narrow(nstore * 2 + 64);
-        hipLaunchKernelGGL((k_xt_narrow16<T>), dim3(g), dim3(256), 0, stream(), P->pval.as<T>(), (uint64_t)nstore, narrow.as<int16_t>());
+        hipLaunchKernelGGL((k_xt_narrow16<T>), dim3(g), dim3(256), 0, stream(), P->pval.as<T>(), (uint64_t)nstore, (uint64_t)ntiles * WP_ENT, narrow.as<int16_t>());
         P->pval = std::move(narrow); P->vbytes = 2;
       }
     }
@@ -1147,7 +1150,7 @@ template <class T> void build_xcd_plan(const DevCSR& M, int ncu, bool with_vals,
     P->s_args.alloc(sizeof(sa));
     GRB_HIP(hipMemcpyAsync(P->s_args.p, sa, sizeof(sa), hipMemcpyHostToDevice, stream()));      // (the stream is synchronised below, before this frame goes)
   }
-  P->tsize = (int)sizeof(T); P->has_vals = with_vals;
+  P->tsize = (int)sizeof(T); P->has_vals = with_vals; P->vinter = with_vals && P->vbytes == 8;
   GRB_HIP(hipEventRecord(ev1, stream()));
   GRB_HIP(hipStreamSynchronize(stream()));
   GRB_HIP(hipEventElapsedTime(&P->build_ms, ev0, ev1)); g_xcd_plan_build_ms = P->build_ms;
@@ -1222,7 +1225,7 @@ template <class T> bool run_xcd(const SpmvCall& c, const SemiringDesc& d, int nc
     } else
       hipLaunchKernelGGL((k_xp_combine<T, SR>), dim3(nblocks), dim3(XP_CT), 0, stream(), M.nrows, P->blockptr.as<uint32_t>(), P->lrow.as<uint16_t>(), P->partial.as<T>(),
                          (T*)c.tval, c.tpres, sr);
-    g_last_plan += std::string("k_spmv_xcd<") + (sr.is_static ? "static" : "dynamic") + (P->sell ? ",lane-per-piece" : "") + (P->vbytes == 2 && P->has_vals ? ",values=int16" : "") + ",subrows=" + std::to_string(P->F) + (P->S > 1 ? ",subpanels=" + std::to_string(P->S) + (P->own ? "/own-tables" : "") : std::string()) + "," + xcd_mapping() + "> ";
+    g_last_plan += std::string("k_spmv_xcd<") + (sr.is_static ? "static" : "dynamic") + (P->sell ? ",lane-per-piece" : "") + (P->vbytes == 2 && P->has_vals ? ",values=int16" : "") + (P->vinter ? ",values=lane-interleaved" : "") + ",subrows=" + std::to_string(P->F) + (P->S > 1 ? ",subpanels=" + std::to_string(P->S) + (P->own ? "/own-tables" : "") : std::string()) + "," + xcd_mapping() + "> ";
   });
   return true;
 }
