@@ -102,6 +102,7 @@ void relay(GrB_Info info, const std::string& err, const char* what) {
 
 // w<mask> = accum(w, A u) or accum(w, u A) with any of them hypersparse.  `tran` is the descriptor bit that transposes A
 // (INP0 for mxv, INP1 for vxm); the output runs over the rows of the matrix as used (A for mxv, A^T for vxm), the operand over its columns.
+extern thread_local bool g_mxv_compacted;      // grb_mxv.cpp
 void hyper_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u, GrB_Descriptor desc, bool is_vxm) {
   if (!check_obj(A) || !check_obj(u) || (mask && !check_obj(mask))) fail(GrB_UNINITIALIZED_OBJECT, "mxv/vxm: uninitialised operand");
   const DescView dv(desc);
@@ -118,6 +119,7 @@ void hyper_mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semir
   TempM a; TempV w2, m2, u2;
   if (tranA) compact(a, A, Cc, R); else compact(a, A, R, Cc);          // A itself is stored untransposed: its rows are op(A)'s columns when transposed
   compact(w2, w, Out); compact(m2, mask, Out); compact(u2, u, In);
+  g_mxv_compacted = true;                      // the compacted operand of a hypersparse call keeps the SpMV routes: no gemv_full (one-shot, cleared by the call)
   const GrB_Info info = is_vxm ? GrB_vxm(w2.v, m2.v, accum, semiring, u2.v, a.m, desc) : GrB_mxv(w2.v, m2.v, accum, semiring, a.m, u2.v, desc);
   relay(info, w2.v->err, "mxv/vxm");
   expand(w, w2.v, Out);

@@ -11,6 +11,8 @@
 #include "grb_spmv.hpp"
 #include "grb_lazy.hpp"
 #include "grb_bigholes.hpp"
+#include "grb_gemv.hpp"
+#include "grb_spmm_geom.hpp"      // spmm_is_full
 #include <cmath>
 #include <algorithm>
 
@@ -22,6 +24,8 @@ static int g_force_method = SPMV_AUTO;   // test hook: GRB_MI355X_SPMV=adaptive|
 // bytes there instead of into fresh buffers, and when the write-back makes w exactly T — the batch products' case — w ends up as a VIEW of that row: the
 // ns x (n values + n bytes) copies per product of the first bitmap version (3.8 of 14 ms of the BC driver at R-MAT-22) are gone.  One-shot: cleared by the call.
 namespace grb { thread_local void* g_mxv_dest_val = nullptr; thread_local uint8_t* g_mxv_dest_pres = nullptr; }
+// The next product on this thread is the compacted form of a hypersparse call (grb_hyper.cpp): it keeps the SpMV routes.  One-shot: cleared by the call.
+namespace grb { thread_local bool g_mxv_compacted = false; }
 
 // A semiring that does not run through SemiringDesc — user-defined, positional or comparison (SemiringRoute, grb_opcommon.hpp): one driver for all three.  What is refused before
 // a device is asked for was refused by the caller; a user-defined semiring's layout refusal comes here, then the accumulator is looked at BEFORE the dimensions;
@@ -122,8 +126,43 @@ static BigHoles plan_big_holes(bool eligible, const SemiringDesc& sd, GrB_Matrix
   return big;
 }
 
+// ---- the gemv_full route: A holds every position (judged on its own device image, queued edits applied) — a linear model's scores X w, the two halves X'(X w) of a
+// power iteration, GAT's logits H a.  One more producer of (tval, tpres): both layouts read A's OWN value array (grb_gemv.hpp) — no column words, no SpMV plan and,
+// for vxm and GrB_INP0, no transposed copy of a dense matrix.  T is computed at every position and the write-back filters it through the allow bytes; the fused
+// epilogues, the hole fills, the code bytes, the any_true word and the frontier-edge summary of the sparse path are not used and nothing of them is acquired.
+// GRB_MI355X_GEMV (read per call: a test hook, and the yardstick of tools/gemv_probe.py): 0 never, 1 wherever legal; by itself where gemv_by_default
+// admits the shape (grb_gemv_geom.hpp, GEMV_FULL_MIN_WORK of grb_route.hpp: the measured wins).  A kernel asked for by name (GRB_MI355X_SPMV, g_force_method), the Boolean `mask == u` form of the BFS loop and a product whose T goes into a
+// batch matrix's row keep their routes.
+static bool gemv_full_wanted(GrB_Matrix A, int method, bool mask_is_u, bool useT, bool compacted) {
+  if (compacted || method != SPMV_AUTO || mask_is_u || g_mxv_dest_val || g_mxv_dest_pres || !A->csr.valid) return false;
+  if (!spmm_is_full(A->csr.nrows, A->csr.ncols, A->csr.nnz)) return false;
+  const int env = route_env("GRB_MI355X_GEMV");
+  return env >= 0 ? env == 1 : gemv_by_default(A->csr.nrows, A->csr.ncols, useT, GEMV_FULL_MIN_WORK);
+}
+static void gemv_full_route(GrB_Vector w, const uint8_t* allow, GrB_BinaryOp accum, const SemiringDesc& sd, GrB_Matrix A, GrB_Vector u, bool useT, uint64_t mr, uint64_t mc, bool replace) {
+  if (w->lazy) vec_gate(w);                                   // a pending `w(:) = s`: written now, the write-back reads it
+  const uint64_t u_nvals = vec_dev_nvals(u);
+  const size_t zs = type_size(sd.zcode);
+  DevBuf tval(mr * zs + 16), tpres(mr + 16), ucast, acast;
+  GemvPlan p; p.m = mr; p.k = mc; p.layout = useT ? GEMV_T : GEMV_N; p.holes = u_nvals != u->n; p.chunks = 0;
+  bool cast = false;
+  if (u_nvals == 0) GRB_HIP(hipMemsetAsync(tpres.p, 0, mr, stream()));      // no product exists: T is empty, no launch
+  else {
+    const bool uses_a = sd.flip ? binop_uses_y(sd.mulop) : binop_uses_x(sd.mulop), uses_u = sd.flip ? binop_uses_x(sd.mulop) : binop_uses_y(sd.mulop);
+    const void* av = uses_a ? cast_values(sd.zcode, A->type->code, A->csr.val.p, A->csr.nnz, acast) : nullptr;
+    const void* uv = uses_u ? cast_values(sd.zcode, u->type->code, u->dval.p, u->n, ucast) : nullptr;
+    cast = (uses_a && A->type->code != sd.zcode) || (uses_u && u->type->code != sd.zcode);
+    gemv_full(p.layout, mr, mc, av, uv, u_nvals == u->n ? nullptr : u->dpres.as<uint8_t>(), sd, tval.p, p);
+    GRB_HIP(hipMemsetAsync(tpres.p, 1, mr, stream()));
+  }
+  g_last_plan = "gemv_full<m=" + std::to_string(p.m) + ",k=" + std::to_string(p.k) + ",layout=" + (p.layout == GEMV_T ? "T" : "N") + ",holes=" + (p.holes ? "1" : "0") +
+                ",chunks=" + std::to_string(p.chunks) + ",cast=" + (cast ? "1" : "0") + "> " + (u_nvals ? std::string(p.kernel) + " " + (p.chunks > 1 ? "k_gemv_fold " : "") : std::string());
+  vector_write_back(w, sd.zcode, tval, tpres, allow, accum, replace, /*t_only_allowed=*/false, u_nvals ? mr : 0);
+}
+
 static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semiring semiring, GrB_Matrix A, GrB_Vector u,
                      GrB_Descriptor desc, bool is_vxm) {
+  const bool compacted = g_mxv_compacted; g_mxv_compacted = false;
   const SemiringRoute route = semiring_route(semiring);
   const bool initialised = check_obj(w) && check_obj(A) && check_obj(u) && (!mask || check_obj(mask));
   if (route.off_table()) {
@@ -158,6 +197,7 @@ static void mxv_like(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, GrB_Semi
     return;
   }
   mat_to_device(A); vec_to_device(u);
+  if (mr && mc && gemv_full_wanted(A, method, mask_is_u, useT, compacted)) { gemv_full_route(w, allow, accum, sd, A, u, useT, mr, mc, dv.replace); return; }
   const auto [push, tiny, u_nvals, u_full] = choose_direction(method, sd, A, u, useT);
 
   // does the multiply read the matrix / vector values at all?

@@ -45,5 +45,8 @@ constexpr uint64_t SDDMM_MIN_WORK = 1ull << 16;                  // the smallest
 // columns and GEMM_MIN_TILES tiles of the result (grb_gemm_geom.hpp) — calls that took spmm_full before, which read the left operand as an ordinary CSR
 // (GRB_MI355X_GEMM: 0 never, 1 wherever legal; GRB_MI355X_FULL set: spmm_full's hook decides).
 constexpr uint64_t GEMM_FULL_MIN_WORK = 1ull << 18;              // the count SPMM_FULL_MIN_PRODUCTS compares nnz(A) k against; measured: of the 128 sweep points from 2^18 up (m = 2^10 .. 2^20, k = 16 .. 256, n = 2 .. 256) the route lost to GRB_MI355X_GEMM=0 only at 4 and 8 tall tiles with k = 256 (0.060 against 0.052 ms), which the tile condition now leaves to spmm_full; the other 126 took 0.13 - 0.78 of its time; the crossover below 2^18 was not searched (DESIGN.md "Product of two full matrices")
+// Between two device routes of GrB_mxv / GrB_vxm: the entries nrows ncols of a FULL matrix from which a product that is not transposed and has rows of at least
+// GEMV_DEFAULT_MIN_INNER values takes the gemv_full route by itself instead of the SpMV kernels (GRB_MI355X_GEMV: 0 never, 1 wherever legal; grb_gemv_geom.hpp holds the rule).
+constexpr uint64_t GEMV_FULL_MIN_WORK = 1ull << 24;              // measured, warm regime: the smallest work count from which layout N with rows of >= 2^16 values never lost to GRB_MI355X_GEMV=0 (256 x 2^16: 0.021 against 0.107 ms; 16 x 2^20, 64 x 2^20, 16 x 2^22 as well); 16 x 2^16 = 2^20 lost (0.017 against 0.012 ms), nothing between was measured (DESIGN.md "Full matrix times a vector")
 
 }  // namespace grb

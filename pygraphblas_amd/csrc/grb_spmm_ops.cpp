@@ -1,11 +1,12 @@
 // grb_spmm_ops.cpp — full matrices across the C ABI: GrBX_Matrix_import_Full / GrBX_Matrix_export_Full (a row-major dense array in, the value array out) and
-// GrBX_spmm_geometry / GrBX_sddmm_geometry / GrBX_gemm_geometry.  A full matrix has no format of its own: it is the CSR whose row pointer and columns are closed form (rowptr[i] = i ncols,
+// GrBX_spmm_geometry / GrBX_sddmm_geometry / GrBX_gemm_geometry / GrBX_gemv_geometry.  A full matrix has no format of its own: it is the CSR whose row pointer and columns are closed form (rowptr[i] = i ncols,
 // col[p] = p mod ncols) and whose value array IS the dense array, so the import is one value copy plus the fill kernel the spmm_full route of GrB_mxm uses for
 // T's pattern (grb_spmm.hip), and the export is one copy.  Nothing passes through tuples or a host mirror.
 #include "grb_container.hpp"
 #include "grb_spmm.hpp"
 #include "grb_sddmm.hpp"
 #include "grb_gemm.hpp"
+#include "grb_gemv.hpp"
 
 using namespace grb;
 
@@ -65,6 +66,13 @@ GrB_Info GrBX_gemm_geometry(uint64_t* out) {
   if (!out) return GrB_NULL_POINTER;
   out[0] = GEMM_TM_WIDE; out[1] = GEMM_TN_WIDE; out[2] = GEMM_TM_TALL; out[3] = GEMM_TN_TALL; out[4] = GEMM_KT; out[5] = GEMM_WAVES; out[6] = GEMM_GRID_CAP;
   out[7] = GEMM_FULL_MIN_WORK; out[8] = GEMM_TALL_MAX_N; return GrB_SUCCESS;
+}
+
+// the shape of a full matrix times a vector (grb_gemv_geom.hpp): what its tests take their edges from
+GrB_Info GrBX_gemv_geometry(uint64_t* out) {
+  if (!out) return GrB_NULL_POINTER;
+  out[0] = GEMV_LOAD_BYTES; out[1] = GEMV_N_GROUP_MAX; out[2] = GEMV_N_CHUNK; out[3] = GEMV_WAVES; out[4] = GEMV_GRID_CAP; out[5] = GEMV_T_CHUNK;
+  out[6] = GEMV_T_MAX_CHUNKS; out[7] = GEMV_FULL_MIN_WORK; out[8] = GEMV_N_UNROLL; out[9] = GEMV_MAX_PACK; return GrB_SUCCESS;
 }
 
 }  // extern "C"

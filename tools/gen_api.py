@@ -614,6 +614,12 @@ GrB_Info GrBX_sddmm_geometry(uint64_t *out);   /* out[0] mask entries per tile (
    from 2 columns, GEMM_FULL_MIN_WORK = m k n and 16 tiles of the result, and not while GRB_MI355X_FULL is set).  Fold order: T(i, j) is the left-to-right fold of its products in
    ascending l from the first one, for every k, whatever the tile, the tile shape, the layout, the grid or the run. */
 GrB_Info GrBX_gemm_geometry(uint64_t *out);   /* out[0], out[1] TM, TN of the wide tile, out[2], out[3] of the tall tile, out[4] KT, out[5] waves per workgroup, out[6] grid cap in workgroups, out[7] GEMM_FULL_MIN_WORK, out[8] the widest result (n) that takes the tall tile */
+/* GrB_mxv / GrB_vxm with a FULL matrix (X.mxv(w), y.vxm(X): a linear model's scores, the halves X'(X w) of a power iteration, attention logits) may take the
+   one-pass "gemv_full<m=M,k=K,layout=N|T,holes=0|1,chunks=C,cast=0|1> k_gemv_n_short|k_gemv_n_wave|k_gemv_t [k_gemv_fold]" route (m the outer length, k the
+   inner): a stream over A's own value array in either orientation — no column words, no SpMV plan, no transposed copy (GRB_MI355X_GEMV: 0 never, 1 wherever
+   legal; by itself from GEMV_FULL_MIN_WORK = nrows ncols; not when GRB_MI355X_SPMV names a kernel).  Fold order: a function of k, the layout, the value size and
+   u's pattern alone; every fold starts from its first existing product; the oracle's left-to-right order for k <= 2 (N) and k <= 65 (T). */
+GrB_Info GrBX_gemv_geometry(uint64_t *out);   /* out[0] bytes per lane load, out[1] the longest row (N) that shares a wave, out[2] products per chunk (N), out[3] waves per workgroup, out[4] grid cap in workgroups, out[5] fewest rows per chunk (T), out[6] most chunks per column (T), out[7] GEMV_FULL_MIN_WORK, out[8] packets in flight per lane (N), out[9] values per packet at most */
 /* index-list extract / assign with a list that may lie in HBM: the arguments of the GrB_ namesake plus the location of each list.  location 0 = a host array, GrB_ALL
    or a GxB_RANGE / GxB_STRIDE / GxB_BACKWARDS triple: exactly the GrB_ call.  1 = `ni` 64-bit indices at a device address (or GrB_ALL; a range code as the count is
    GrB_INVALID_VALUE): parsed where they lie (grb_index.hip), the device route wherever it is legal, else the list is copied down once for the host route.
